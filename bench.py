@@ -251,6 +251,27 @@ def gpu_parity(torch, dev, pv, abi, cam, film, smp, first, stream):
             "ok": bool(perr.max() <= 1e-4 and (end == first["end_draws"]).all())}
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: data bytes of all arrays together (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(path, arrays, seed=2024):
+    """--dump-outputs: the arrays the timed path handed its caller in the last timed step, as float32 DIR/<name>.npy.  All arrays
+    share their leading row axis (pixel or sample).  When the whole set exceeds DUMP_BYTES, every array is cut to the same fixed,
+    seeded set of rows (in increasing order), so two builds run with the same arguments are compared row for row."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[0].numel() * 4 for a in arrays.values())
+    idx = None
+    if n * row_bytes > DUMP_BYTES:
+        rows = np.unique(np.random.default_rng(seed).integers(0, n, DUMP_BYTES // row_bytes))
+        idx = torch.from_numpy(rows).to(next(iter(arrays.values())).device)
+    for name, a in arrays.items():
+        a = a.float() if idx is None else a.float().index_select(0, idx)
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+    return {"dir": path, "arrays": sorted(arrays), "rows": n if idx is None else int(len(idx)), "of_rows": n, "seed": None if idx is None else seed}
+
+
 def spawn_ranks(n):
     """`bench.py --gpus N` started plainly: launch N ranks (one per GPU) as a CHILD torchrun job before this process touches
     the GPU, and pass its output and exit code through.  Never an exec: the box forbids replacing a process that may own a GPU."""
@@ -356,7 +377,15 @@ def main():
                     help="tile driver: also run the scene's SurfaceIntegrator \"photonmap\" (nused 300, maxdist .15, 5000 caustic photons kept by the "
                          "device shooter, indirectphotons 0) in front of the volume term: Ls = T * Lsurface + Lvi as SamplerRenderer::Li composes it")
     ap.add_argument("--save-image", default="", help="tile driver: write the resolved RGB film of the last step as .npy")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as float32 DIR/<name>.npy (rank 0; at most 64 MB in all, "
+                         "a fixed seeded row sample beyond that): tile driver film_rgb (resolved film) and film_pixels (the film's "
+                         "weighted XYZ sums + filter weight per pixel), batch driver li_xyzT (Lv as XYZ, T.y() per ray)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.emulate_ranks:
+        ap.error("--dump-outputs needs the timed steps; --emulate-ranks replaces them")
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.dry_run:
@@ -495,6 +524,12 @@ def main():
             np.save(args.save_image, d_rgb.cpu().numpy())
     else:
         checksum = float(d_out[:, :3].double().sum().item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if args.driver == "tile":
+            dumped = dump_outputs(args.dump_outputs, {"film_rgb": d_rgb, "film_pixels": d_pixels})
+        else:
+            dumped = dump_outputs(args.dump_outputs, {"li_xyzT": d_out})
 
     rc = 0
     if rank == 0:
@@ -534,6 +569,8 @@ def main():
                            "total_s": t_map + ms_per_step * 1e-3,
                            "note": "photon map is shot once per frame and replicated per rank; render_step_s includes the film all-reduce when N > 1"},
         }
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         cpu, ctr, first = (None, None, None)
         if not args.no_cpu_baseline and world == 1:   # the CPU baseline is a rank-0, N=1 leg
             if args.driver == "tile":
