@@ -121,6 +121,7 @@ struct pvol_ctx {
     uint32_t *dSpecLink = 0;        // per primary ray of a render batch
     size_t specLinkBytes = 0;
     float *specSurfOut = 0;         // set by the render driver around pvol_launch_batch: where the composition reports the surface term
+    double exchangeSeconds = 0.0;   // last pvol_preprocess_ranks: time in its all-gathers (part of prepSeconds[0])
     double prepSeconds[2] = {0.0, 0.0};   // last pvol_preprocess: shooting (all rounds + merges), search-structure build
     // tile driver work buffers (grown on demand, pvol_tile.hip)
     void *dTile[6] = {0, 0, 0, 0, 0, 0};

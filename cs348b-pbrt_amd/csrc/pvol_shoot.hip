@@ -52,6 +52,8 @@ struct ShootArgs {
     int init;                 // 1: seed RNG + Halton tables instead of shooting
     uint32_t blockPaths;      // paths per task and round (4096: PhotonShootingTask::Run's block, photonshooter.cpp:247)
     int gridVolume;           // the medium is a VolumeGrid: the kernel takes GRID_KMAX x 64 more LDS words (march_grid)
+    const uint32_t *taskIds;  // [nTasks] global task number of each slot (one rank's share, pvol_preprocess_ranks), or null:
+                              // slot == task.  Every array above is indexed by slot; the RNG seed and Halton permutation by task
 };
 
 // ------------------------------------------------------------------------------------------ spectra: lane b == bin b
@@ -720,9 +722,10 @@ __device__ void follow_photon(PathCtx &C, V3 rayO, V3 rayD, float rayMint, float
 template <int WPE>
 __global__ __launch_bounds__(LANES, WPE) void shoot_kernel(ShootArgs A) {
     extern __shared__ __align__(16) unsigned char lds[];
-    const uint32_t task = blockIdx.x;
+    const uint32_t task = blockIdx.x;   // the slot; the seed below takes the global task number
     const int lane = threadIdx.x;
     if (task >= A.nTasks) return;
+    const uint32_t globalTask = A.taskIds ? A.taskIds[task] : task;
     const DevScene &S = *A.scene;
     const DevShootScene &H = *A.shoot;
     uint32_t *mt = reinterpret_cast<uint32_t *>(lds);
@@ -737,7 +740,7 @@ __global__ __launch_bounds__(LANES, WPE) void shoot_kernel(ShootArgs A) {
     rng.draws = 0;
     if (A.init) {
         // RNG rng(31 * taskNum) (photonshooter.cpp:235), then PermutedHalton(6, rng) (montecarlo.cpp:380-397)
-        mt_seed(mt, 31u * task, lane);
+        mt_seed(mt, 31u * globalTask, lane);
         rng.mti = MT_N;
         const uint32_t bases[6] = {2, 3, 5, 7, 11, 13};
         uint32_t off = 0;
@@ -926,5 +929,42 @@ extern "C" hipError_t pvol_launch_shoot(const ShootArgs *a, hipStream_t stream) 
 extern "C" hipError_t pvol_launch_merge(const MergeArgs *m, hipStream_t stream) {
     if (!m->nSeg) return hipSuccess;
     hipLaunchKernelGGL(merge_kernel, dim3(std::min<uint32_t>(m->nSeg, 4096u)), dim3(256), 0, stream, *m);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------ sharded shoot (pvol_preprocess_ranks)
+// After the last round every rank holds the all-gathered local arrays of all ranks: rank r's block is `rankStride` floats, field f
+// of it (p, wi|wo, alpha; or the radiance record) `fieldOff[f]` floats in, `width[f]` floats per row, rows in that rank's append
+// order.  A segment (src rank, local row, global row, count) is one task's contribution at its turn in the merge; the segments are
+// in global order and cover [0, nRows) without gaps, so global row g finds its segment by binary search over segGlobal.
+struct PlaceArgs {
+    const float *recv;
+    uint64_t rankStride;
+    uint64_t fieldOff;
+    uint32_t width;
+    const uint32_t *segSrc, *segLocal, *segGlobal;
+    uint32_t nSeg;
+    uint64_t nRows;
+    float *dst;   // [nRows][width]
+};
+__global__ __launch_bounds__(256) void place_rows_kernel(PlaceArgs P) {
+    const uint64_t nWords = P.nRows * P.width;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nWords; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t g = i / P.width;
+        const uint32_t k = (uint32_t)(i - g * P.width);
+        uint32_t lo = 0, hi = P.nSeg;   // last segment whose global row <= g
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if ((uint64_t)P.segGlobal[mid] <= g) lo = mid; else hi = mid;
+        }
+        const uint64_t row = (uint64_t)P.segLocal[lo] + (g - P.segGlobal[lo]);
+        P.dst[i] = P.recv[(uint64_t)P.segSrc[lo] * P.rankStride + P.fieldOff + row * P.width + k];
+    }
+}
+extern "C" hipError_t pvol_launch_place_rows(const PlaceArgs *a, hipStream_t stream) {
+    if (!a->nSeg || !a->nRows) return hipSuccess;
+    const uint64_t nWords = a->nRows * a->width;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((nWords + 255) / 256, 16384);
+    hipLaunchKernelGGL(place_rows_kernel, dim3(blocks), dim3(256), 0, stream, *a);
     return hipGetLastError();
 }

@@ -380,7 +380,8 @@ static nccl_reduce_fn bind_nccl_reduce() {
 
 // One rank of an N-GPU frame: its share of the render tasks into its own full-frame film, ONE ncclReduce(sum) of the film to rank 0
 // (the Gaussian filter splats across tile borders, film/image.cpp:82-134, so tiles cannot simply be gathered), resolve on rank 0.
-// The photon map is replicated: every rank runs pvol_preprocess with the same seeds beforehand -- nothing else crosses GPUs.
+// Every rank holds the whole photon map beforehand: pvol_preprocess with the same seeds on each rank, or pvol_preprocess_ranks,
+// which shares the shoot and leaves the same map on all of them.
 extern "C" int pvol_render_frame_ranks(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *smp,
                                        uint32_t rank, uint32_t nRanks, void *ncclComm, float *dPixels, float *dRgb, void *hipStream) {
     if (!c || !smp || !film_ok(film) || !dPixels || !nRanks || rank >= nRanks) return PVOL_E_INVALID;

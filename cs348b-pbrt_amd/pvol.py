@@ -23,6 +23,31 @@ class PvolError(RuntimeError):
         RuntimeError.__init__(self, "%s: %s (%d)" % (where, lib().pvol_strerror(status).decode(), status))
 
 
+# pvol_shoot_comm: how the ranks of pvol_preprocess_ranks exchange data (exactly one of nccl_comm / allgather set)
+ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+
+
+class ShootComm(C.Structure):
+    _fields_ = [("nccl_comm", C.c_void_p), ("allgather", ALLGATHER_FN), ("user", C.c_void_p)]
+
+
+def gloo_allgather(group=None):
+    """A host all-gather for PhotonVolume.preprocess_ranks over torch.distributed (gloo: CPU tensors): bytes -> list of bytes,
+    one entry per rank in rank order."""
+    import torch
+    import torch.distributed as dist
+
+    def allgather(data):
+        n = dist.get_world_size(group)
+        if not data:
+            return [b""] * n
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8)
+        out = [torch.empty_like(t) for _ in range(n)]
+        dist.all_gather(out, t, group=group)
+        return [o.numpy().tobytes() for o in out]
+    return allgather
+
+
 _lib = None
 
 
@@ -47,6 +72,8 @@ def lib():
         L.pvol_upload_photons.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_preprocess.argtypes = [C.c_void_p, C.c_uint32]
         L.pvol_preprocess_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.pvol_preprocess_ranks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ShootComm)]
+        L.pvol_get_exchange_seconds.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.pvol_photon_count.argtypes = [C.c_void_p, _u32p]
         L.pvol_download_photons.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_li_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, _f32p, _u32p]
@@ -95,7 +122,8 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_film_add_samples_device", "pvol_film_resolve_device", "pvol_march_kernel_name", "pvol_check_errors", "pvol_get_preprocess_seconds", "pvol_get_accel_info", "pvol_surface_photon_count",
            "pvol_download_surface_photons", "pvol_radiance_photon_count", "pvol_download_radiance_photons",
            "pvol_set_surface_integrator", "pvol_enable_phase_timing", "pvol_get_phase_ms",
-           "pvol_partition_tasks", "pvol_render_frame_ranks", "pvol_preprocess_blocks"]
+           "pvol_partition_tasks", "pvol_render_frame_ranks", "pvol_preprocess_blocks",
+           "pvol_preprocess_ranks", "pvol_get_exchange_seconds"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -157,6 +185,42 @@ class PhotonVolume:
             _check(lib().pvol_preprocess(self._h, n_tasks), "pvol_preprocess")
         else:
             _check(lib().pvol_preprocess_blocks(self._h, n_tasks, block_paths), "pvol_preprocess_blocks")
+
+    def preprocess_ranks(self, n_tasks, rank, n_ranks, *, allgather=None, nccl_comm=None, block_paths=4096):
+        """This rank's share of preprocess(n_tasks, block_paths) sharded over n_ranks ranks (pvol_preprocess_ranks): every rank
+        ends with the single-rank map, bit for bit.  Exactly one transport: `allgather`, a callable bytes -> list of n_ranks bytes
+        (e.g. gloo_allgather()), or `nccl_comm`, an ncclComm_t (integer) of n_ranks ranks."""
+        comm = ShootComm()
+        err = []
+        cb = None
+        if allgather is not None:
+            def _cb(user, send, recv, nbytes):
+                try:
+                    parts = allgather(C.string_at(send, nbytes) if nbytes else b"")
+                    if len(parts) != n_ranks or any(len(p) != nbytes for p in parts):
+                        raise ValueError("allgather returned %d parts of %s bytes, wanted %d of %d"
+                                         % (len(parts), sorted({len(p) for p in parts}), n_ranks, nbytes))
+                    if nbytes:
+                        C.memmove(recv, b"".join(parts), nbytes * n_ranks)
+                    return 0
+                except BaseException as e:   # noqa: B902 -- must not unwind through C; re-raised below
+                    err.append(e)
+                    return 1
+            cb = ALLGATHER_FN(_cb)   # kept alive by this frame for the whole call
+            comm.allgather = cb
+        if nccl_comm is not None:
+            comm.nccl_comm = nccl_comm
+        rc = lib().pvol_preprocess_ranks(self._h, n_tasks, block_paths, rank, n_ranks, C.byref(comm))
+        del cb
+        if err:
+            raise PvolError(rc, "pvol_preprocess_ranks") from err[0]
+        _check(rc, "pvol_preprocess_ranks")
+
+    def exchange_seconds(self):
+        """Seconds the last preprocess_ranks() spent in its all-gathers (part of preprocess_times()[0])."""
+        v = C.c_double()
+        _check(lib().pvol_get_exchange_seconds(self._h, C.byref(v)), "pvol_get_exchange_seconds")
+        return float(v.value)
 
     def preprocess_times(self):
         """(shoot seconds, search-structure build seconds) of the last preprocess()."""

@@ -307,6 +307,35 @@ int pvol_preprocess(pvol_ctx *ctx, uint32_t n_tasks);
  * oracle photon for photon when the oracle runs the same block size. */
 int pvol_preprocess_blocks(pvol_ctx *ctx, uint32_t n_tasks, uint32_t block_paths);
 
+/* How the ranks of a sharded shoot (pvol_preprocess_ranks) exchange data.  Exactly one of the two is set:
+ * nccl_comm, an ncclComm_t of n_ranks ranks made by the caller with RCCL (ncclCommInitRank), whose ncclAllGather moves device
+ * buffers on the null stream; or allgather, a host all-gather: every rank passes `bytes` bytes at `send` and receives
+ * n_ranks x bytes at `recv`, rank-major, returning 0 on success (for gloo or a test's own transport).  `user` is handed to it. */
+typedef struct pvol_shoot_comm {
+    void *nccl_comm;
+    int (*allgather)(void *user, const void *send, void *recv, uint64_t bytes);
+    void *user;
+} pvol_shoot_comm;
+
+/* pvol_preprocess_blocks sharded over n_ranks ranks (one GPU each): rank `rank` shoots only the virtual tasks
+ * pvol_partition_tasks(n_tasks, rank, n_ranks) deals it (task t keeps RNG(31*t) and its Halton permutation wherever it runs).
+ * Each round the ranks all-gather one count row per task and a status word per rank, and every rank runs the single-rank merge
+ * rule on the gathered table; after the last round one all-gather of every rank's taken rows per store places them where
+ * pvol_preprocess_blocks puts them.  Every rank ends with the same photon map (and, with keep_surface_photons, the same surface
+ * stores) as pvol_preprocess_blocks(ctx, n_tasks, block_paths) on one GPU, bit for bit, and the same pvol_get_shoot_stats.
+ * All ranks call it with the same scene, parameters, n_tasks and block_paths; n_ranks = 1 runs the whole protocol too.
+ * A rank's own failure (PVOL_E_NO_MEMORY, PVOL_E_LIMIT: a block outgrew the largest pool, PVOL_E_NO_DEVICE) is reported at the
+ * next exchange and every rank returns the lowest-ranked rank's code, so no rank is left waiting in a collective; only a failed
+ * exchange itself (PVOL_E_NO_DEVICE) can leave the ranks disagreeing.  PVOL_E_INVALID: a NULL ctx or comm, rank >= n_ranks,
+ * n_tasks or block_paths out of pvol_preprocess_blocks' range, or not exactly one of nccl_comm and allgather set (all checked
+ * before the device is touched).  RCCL is bound at run time as for pvol_render_frame_ranks, and only when nccl_comm is given. */
+int pvol_preprocess_ranks(pvol_ctx *ctx, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, uint32_t n_ranks,
+                          const pvol_shoot_comm *comm);
+
+/* Seconds the last pvol_preprocess_ranks spent in its all-gathers, host staging included (part of the shooting time that
+ * pvol_get_preprocess_seconds reports in out[0]). */
+int pvol_get_exchange_seconds(pvol_ctx *ctx, double *out);
+
 /* Work counters of the last pvol_preprocess (the figures SURVEY 6 reports for the reference shooter):
  * out[12] = paths, followPhoton calls, calls ending without a surface hit, transmittance-march steps,
  * volume interactions, absorbed, stored volume / caustic / direct / indirect photons, spectral-split
@@ -440,7 +469,8 @@ int pvol_partition_tasks(uint32_t n_tasks, uint32_t rank, uint32_t n_ranks, uint
  * rendered into it (pvol_render_tasks_device), ONE ncclReduce(sum, root 0) over `nccl_comm` (an ncclComm_t of n_ranks ranks made by
  * the caller with RCCL: ncclCommInitRank; ignored when n_ranks == 1) adds the ranks' films -- the Gaussian filter splats across tile
  * borders (film/image.cpp:82-134), so the films are summed, not gathered -- and rank 0 resolves into d_rgb (x*y*3 floats; may be
- * NULL on the other ranks).  The photon map is replicated: every rank calls pvol_preprocess with the same task count first.
+ * NULL on the other ranks).  Every rank needs the whole photon map first: either each runs pvol_preprocess with the same task
+ * count (replicated), or the ranks share the shoot with pvol_preprocess_ranks, which leaves the same map on every rank.
  * RCCL is bound at run time (the copy already in the process, else librccl.so.1): PVOL_E_NO_DEVICE if none is in reach. */
 int pvol_render_frame_ranks(pvol_ctx *ctx, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *sampler,
                             uint32_t rank, uint32_t n_ranks, void *nccl_comm, float *d_pixels, float *d_rgb, void *hip_stream);

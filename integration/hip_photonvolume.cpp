@@ -77,11 +77,8 @@ public:
 
     // core/integrator.h:55-57 hook; replaces PhotonShooter::Preprocess for the volume map
     void Preprocess(const Scene *scene, const Camera *, const Renderer *) {
-        HipFlatScene flat;
-        const char *why = HipFlattenScene(scene, &flat);
-        if (why) Severe("photonvolume_hip: %s", why);
-        int rc = pvol_set_scene(ctx, &flat.scene);
-        if (rc != PVOL_OK) Severe("photonvolume_hip: pvol_set_scene: %s", pvol_strerror(rc));
+        SetScene(scene);
+        int rc;
         if (mapSource) {   // `volumeMap = new KdTree<Photon>(volumePhotons)` already happened (photonshooter.cpp:502-503)
             const KdTree<Photon> *map = mapSource->volumeMap;
             rc = UploadPhotons(map ? map->nodeData : NULL, map ? map->nNodes : 0);
@@ -97,6 +94,28 @@ public:
         rc = pvol_preprocess(ctx, 16384);
         if (rc == PVOL_E_SHOOT_FAILED) Error("Unable to store enough photons.  Giving up.\n");   // photonshooter.cpp:292
         else if (rc != PVOL_OK) Severe("photonvolume_hip: pvol_preprocess: %s", pvol_strerror(rc));
+    }
+
+    // The scene half of Preprocess: flatten the reference's Scene into the library's (a multi-GPU renderer calls this and then
+    // PreprocessRanks instead of Preprocess).
+    void SetScene(const Scene *scene) {
+        HipFlatScene flat;
+        const char *why = HipFlattenScene(scene, &flat);
+        if (why) Severe("photonvolume_hip: %s", why);
+        int rc = pvol_set_scene(ctx, &flat.scene);
+        if (rc != PVOL_OK) Severe("photonvolume_hip: pvol_set_scene: %s", pvol_strerror(rc));
+    }
+
+    // The shoot half of Preprocess shared by the ranks of a multi-GPU render (pvol_preprocess_ranks): rank `rank` of `nRanks`
+    // shoots its share of the 16384 virtual tasks and every rank ends with the map Preprocess builds on one GPU, bit for bit.
+    // `ncclComm` is the caller's ncclComm_t of nRanks ranks (ncclCommInitRank), the one RenderFrameRanks takes.  Every rank
+    // returns the same status (PVOL_E_SHOOT_FAILED: the reference's "Unable to store enough photons").
+    int PreprocessRanks(int rank, int nRanks, void *ncclComm) {
+        pvol_shoot_comm comm;
+        comm.nccl_comm = ncclComm; comm.allgather = NULL; comm.user = NULL;
+        const int rc = pvol_preprocess_ranks(ctx, 16384, 4096, (uint32_t)rank, (uint32_t)nRanks, &comm);
+        if (rc == PVOL_E_SHOOT_FAILED) Error("Unable to store enough photons.  Giving up.\n");   // photonshooter.cpp:292
+        return rc;
     }
 
     // Photon records (core/photonshooter.h:20-27, 152-B AoS) -> the three SoA arrays of pvol_upload_photons.
@@ -146,7 +165,7 @@ public:
 
     // One rank of a multi-GPU render (north_star: pixel tiles partitioned over the GPUs of one node, one RCCL reduce of the film):
     // what a renderer calls on rank `rank` of `nRanks` INSTEAD of SamplerRenderer::Render's task loop, after every rank ran
-    // Preprocess (same seeds: identical photon maps, nothing to exchange).  `ncclComm` is the caller's ncclComm_t (ncclCommInitRank);
+    // Preprocess (same seeds: identical photon maps, nothing to exchange) or SetScene + PreprocessRanks (the shoot shared).  `ncclComm` is the caller's ncclComm_t (ncclCommInitRank);
     // dPixels / dRgb are buffers on this rank's device; rank 0 ends up with the resolved frame.
     int RenderFrameRanks(const PerspectiveCamera *camera, const ImageFilm *film, const LDSampler *sampler, const Sample *origSample,
                          int nTasks, int rank, int nRanks, void *ncclComm, float *dPixels, float *dRgb, void *hipStream) const {
