@@ -791,7 +791,7 @@ int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_s
     a.out = dOut; a.draws = dDraws; a.initState = dInit; a.finalState = dFinal; a.counters = c->dCounters;
     a.transmittanceOnly = transOnly;
     a.chunkCounter = c->dWords; a.needSeq = c->dWords + 1; a.gated = 0;
-    a.tauOut = c->dTauNext;   // render driver with the surface integrator on: li_group_kernel also reports the optical length
+    a.tauOut = c->dTauNext;   // render driver with the surface integrator on: the march kernels also report every sample's *T
     // li_group_kernel bucket radius^2 = this x the guessed k-th distance^2 (measured at 64 spp: 1.3 55.5, 1.2 57.5, 1.12 58.0,
     // 1.06 56.6, 1.0 51.0 Msamples/s)
     { const char *gs = getenv("PVOL_GROUP_GUESS"); a.grpGuess = gs ? (float)atof(gs) : 1.15f; if (!(a.grpGuess >= 1.f)) a.grpGuess = 1.15f; }
@@ -818,6 +818,8 @@ int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_s
     // scenes where drawn values matter: sequential RESOLVE pre-pass + ray-parallel REPLAY, slice by slice
     const bool sliced = !par && !c->forceSeq && !transOnly && (c->hs.volKind != PVOL_VOLUME_NONE || tile);
     if (tile && !par && !sliced && !tileCount) return PVOL_E_UNSUPPORTED;
+    // *T of a VolumeGrid is a product of stepped taus with drawn offsets: not a TauRec (the surface term is refused there)
+    if (a.tauOut && c->hs.volKind == PVOL_VOLUME_GRID) return PVOL_E_UNSUPPORTED;
     uint32_t sliceM = 0, nSlices = 0;
     if (sliced) {
         uint32_t maxRays = maxRaysPerStream;
@@ -874,7 +876,6 @@ int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_s
         // homogeneous isotropic medium with a photon map and k <= 64: one ray per lane, gathers of 64 rays share a bucket
         const bool group = !c->noGroup && c->hs.volKind == PVOL_VOLUME_HOMOGENEOUS && c->hs.g == 0.f && c->hs.nPhotons > 0 &&
                            c->hs.nUsed >= 10 && c->hs.nUsed <= 64 && c->hs.candCap <= 4 * 64;
-        if (a.tauOut && !group) return PVOL_E_UNSUPPORTED;
         if (group) {
             unsigned long long gchunks = ((unsigned long long)nRays + 511ull) / 512ull;   // GRP_CH rays per chunk
             uint32_t gWaves = (uint32_t)std::min<unsigned long long>(gchunks, (unsigned long long)c->nCU * (unsigned long long)c->groupWavesPerCU);
@@ -904,8 +905,6 @@ int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_s
             int rc = spec_finish(c, a, specCap, false, nRays, dOut, c->specSurfOut, stream);
             if (rc != PVOL_OK) return rc;
         }
-    } else if (a.tauOut && (!sliced || c->hs.volKind != PVOL_VOLUME_HOMOGENEOUS)) {
-        return PVOL_E_UNSUPPORTED;   // the surface term needs li_group_kernel's optical length of a homogeneous medium
     } else if (sliced) {
         c->lastKernel = "li_replay_kernel";
         e = hipSuccess;
@@ -938,7 +937,6 @@ int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_s
             { const char *ew = getenv("PVOL_FXG_WIDEN"), *ea = getenv("PVOL_FXG_AIM"); a.fxgWiden = ew ? (float)atof(ew) : 0.f; a.fxgAim = ea ? (float)atof(ea) : 0.f; }   // measurement knobs
             c->lastKernel = "li_group_kernel";
         }
-        if (a.tauOut && !groupForm) return PVOL_E_UNSUPPORTED;
         if (spec && !(tile && !tileGridCount && a.liteResolve)) return PVOL_E_UNSUPPORTED;   // the FUSED pre-pass walks the segments (geo_ray + lite_ray)
         if (spec) specCap = spec_pool_cap((size_t)sliceM * nStreams);
         if (tileGridCount) {   // sampler + camera + draw COUNT for the whole batch, once

@@ -140,6 +140,13 @@ struct DevCounters {
 };
 
 // surface_kernel (pvol_surface_dev.h)
+// The *T that PhotonVolumeIntegrator::Li leaves for SamplerRenderer::Li's T * Ls + Lvi (photonvolume.cpp:150-160, 219), per
+// camera sample of a render batch: T = scale * exp(-sigma_t * len).  `len` is the tau() length of the LAST march step (Tr is
+// assigned per step, not accumulated); `scale` is 1, 2 when that step survived the Russian roulette (Tr /= .5), or 0 when the
+// roulette ended the ray.  A ray that misses the medium: {0, 1}.  Analytic media only (homogeneous, rainbow).
+struct TauRec {
+    float len, scale;
+};
 // ---- specular recursion of the surface integrator (pvol_spec_dev.h)
 #define SPEC_MAX_DEPTH 5          // "maxspeculardepth" values up to this are walked (the reference's default); more is refused on the host
 #define SPEC_LINK_DONE 0x80000000u // the sample's segments have been folded in (their pool slots may be reused by the next slice)
@@ -157,7 +164,7 @@ struct SpecComposeArgs {
     uint32_t *link;           // per primary ray of the range: (first segment << 6) | count, 0 = none; SPEC_LINK_DONE is set once composed
     const SegInfo *info;
     const float *segOut;      // 60 floats per segment: Lv[30] (volume term + T (.) matte surface term), T[30]
-    const float *tau;         // per primary ray: optical length of Li()'s last march step
+    const TauRec *tau;        // per primary ray: Li()'s *T
     float *out;               // per primary ray X, Y, Z, T.y: the specular surface term is ADDED to X, Y, Z
     float *surfOut;           // optional: the surface integrator's Li as X, Y, Z (3 floats per ray)
     uint32_t first, nRays;    // the range of primary rays
@@ -178,7 +185,7 @@ struct SurfArgs {
     const pvol_ray *rays;
     uint32_t nRays;
     float *out;            // per ray X, Y, Z, T.y of the volume term: the surface term is ADDED to X, Y, Z
-    const float *tau;      // per ray: optical length of the last march step (T = exp(-sigma_t * tau))
+    const TauRec *tau;     // per ray: Li()'s *T
     float *surfOut;        // optional: the surface integrator's Li as X, Y, Z (3 floats per ray)
     DevCounters *counters;
     const uint32_t *link;  // optional: per ray the specular-recursion link (pvol_spec_dev.h); linked samples keep the surfOut the composition wrote

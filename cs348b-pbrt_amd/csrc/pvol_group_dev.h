@@ -975,7 +975,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                         *reinterpret_cast<f4 *>(A.out + ri * 4) = make_float4(accX * scale, accY * scale, accZ * scale, ty * 300.f / (106.856895f * 30));
                     }
                     if (!REPLAY && A.draws) A.draws[ri] = draws;
-                    if (A.tauOut) A.tauOut[ri] = hit ? lenLast : 0.f;   // T = exp(-sigma_t * this): what the surface term is attenuated by
+                    if (A.tauOut) A.tauOut[ri] = TauRec{hit ? lenLast : 0.f, 1.f};   // no roulette reaches this kernel's results
                 }
             }
             if (!REPLAY) {   // stream positions: one atomic per group when all its rays belong to one stream (the usual case)

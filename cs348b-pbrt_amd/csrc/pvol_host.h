@@ -105,9 +105,9 @@ struct pvol_ctx {
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     float4 *dCPos4 = 0, *dCAlpha4 = 0, *dCWi4 = 0;
     uint32_t *dCCellStart = 0;
-    float *dTau = 0;       // per sample of a render batch: optical length the surface term is attenuated over
+    TauRec *dTau = 0;      // per sample of a render batch: the T the surface term is attenuated by
     size_t tauBytes = 0;
-    float *dTauNext = 0;   // set by the render driver around pvol_launch_batch when the surface integrator is on
+    TauRec *dTauNext = 0;   // set by the render driver around pvol_launch_batch when the surface integrator is on
     // specular recursion of the surface integrator (pvol_spec_dev.h): segments of the camera samples that meet glass
     bool specOn = false;            // the scene holds a specular material and the surface integrator is on
     pvol_ray *dSegRays = 0;

@@ -419,11 +419,22 @@ __device__ __forceinline__ RayRec ray_rec(unsigned char *slot, int maxSteps, boo
     return r;
 }
 
+// tau() length of a homogeneous extent along a general segment (homogeneous.h:80-84): Distance(ray(t0), ray(t1))
+__device__ __forceinline__ float analytic_tau_length(const DevScene &S, V3 o, V3 d, float mint, float maxt) {
+    RayD r;
+    r.o = o; r.d = d; r.mint = mint; r.maxt = maxt;
+    float t0, t1;
+    if (!vol_intersect(S, r, &t0, &t1)) return 0.f;
+    V3 a = o + d * t0, b = o + d * t1;
+    return len(a - b);
+}
+
 // One call of PhotonVolumeIntegrator::Li (or Transmittance).  Returns false only in MODE_PAR when the ray
 // needs a drawn VALUE (Russian roulette): the caller must redo the batch sequentially.
+// `tauRec` (optional): *T as a TauRec (pvol_dev.h); its length is only taken where the caller wants it (A.tauOut).
 template <bool STATS, int MODE, int NREG>
 __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr, Rng &rng, MarchLds &M, int lane,
-                          WaveCounters &wc, f4 *LvOut, f4 *TrOut, RayRec rec) {
+                          WaveCounters &wc, f4 *LvOut, f4 *TrOut, RayRec rec, TauRec *tauRec = nullptr) {
     constexpr bool RNGON = (MODE == MODE_SEQ || MODE == MODE_RESOLVE);
     constexpr bool RADIANCE = (MODE != MODE_RESOLVE);
     const int q = lane & 7;
@@ -439,6 +450,7 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
     ray.mint = pr.mint;
     ray.maxt = pr.maxt;
     f4 Lv = mk4(0.f), Tr = mk4(1.f);
+    float tLen = 0.f, tScale = 1.f;   // Tr as {length of the last step, roulette factor}
     ++wc.rays;   // rays and march steps are counted in every build (wave-uniform adds, one atomic per wave at the end)
     if (A.transmittanceOnly) {
         *TrOut = transmittance<RNGON>(S, ray, rng, sigT, lane);
@@ -520,25 +532,31 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
                 // (homogeneous.h:80-84 -> Distance(ray(0), ray(1)) * sigma_t)
                 V3 dseg = p - pPrev;
                 V3 a = pPrev + dseg * 0.f, b = pPrev + dseg * 1.f;
-                stepTau = sigT * len(a - b);
+                const float lenAB = len(a - b);
+                stepTau = sigT * lenAB;
+                tLen = lenAB;
             } else {
                 RayD tauRay;
                 tauRay.o = pPrev; tauRay.d = p - pPrev; tauRay.mint = 0.f; tauRay.maxt = 1.f;
                 stepTau = vol_tau(S, tauRay, .5f * S.stepSize, uTau, sigT);
+                if (A.tauOut && analytic) tLen = analytic_tau_length(S, pPrev, tauRay.d, 0.f, 1.f);   // vol_tau's own length
             }
             inPrev = inP;
             Tr = exp4(neg4(stepTau));   // assigned, not accumulated (photonvolume.cpp:155)
+            tScale = 1.f;
             if (MODE == MODE_REPLAY) {
-                if (recByte & 0x80u) Tr = Tr / .5f;
+                if (recByte & 0x80u) { Tr = Tr / .5f; tScale = 2.f; }
             } else if (spec_y(Tr, Y) < 1e-3) {
                 if (MODE == MODE_PAR) return false;  // the roulette compares a drawn value
                 const float continueProb = .5f;
                 if (rng_float<RNGON>(rng, lane) > continueProb) {
                     Tr = mk4(0.f);
+                    tScale = 0.f;
                     if (MODE == MODE_RESOLVE) { nEff = i; killed = true; }
                     break;
                 }
                 Tr = Tr / continueProb;
+                tScale = 2.f;
                 recByte |= 0x80u;
             }
             const float dens = analytic ? (inP ? 1.f : 0.f) : grid_density(S, pv);   // homogeneous.h:64-75 / volume.h:81-92
@@ -637,11 +655,12 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
                 Lv = (sa * (le * dens) * step) + (ss * L_i * step) + (Tr * Lv);
             }
         }
-        if (MODE == MODE_REPLAY && killed) Tr = mk4(0.f);
+        if (MODE == MODE_REPLAY && killed) { Tr = mk4(0.f); tScale = 0.f; }
     }
     if (MODE == MODE_RESOLVE && lane == 0) { rec.hdr[0] = (uint32_t)nEff; rec.hdr[1] = killed ? 1u : 0u; }
     *LvOut = Lv;
     *TrOut = Tr;
+    if (tauRec) *tauRec = TauRec{tLen, tScale};
     return true;
 }
 
@@ -651,15 +670,6 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
 // one step per lane; the serial loop that follows only does the spectral arithmetic and the gather, reading
 // each step's scalars back with wave-uniform lane reads.  Returns 0 = done, 1 = the ray needs the roulette
 // (MODE_PAR: redo sequentially), 2 = not applicable (the caller runs march_ray).
-// tau() length of a homogeneous extent along a general segment (homogeneous.h:80-84): Distance(ray(t0), ray(t1))
-__device__ __forceinline__ float analytic_tau_length(const DevScene &S, V3 o, V3 d, float mint, float maxt) {
-    RayD r;
-    r.o = o; r.d = d; r.mint = mint; r.maxt = maxt;
-    float t0, t1;
-    if (!vol_intersect(S, r, &t0, &t1)) return 0.f;
-    V3 a = o + d * t0, b = o + d * t1;
-    return len(a - b);
-}
 __device__ __forceinline__ bool lane_occluded(const DevScene &S, const RayD &vis) {
     if (S.nSpheres && spheres_occluded(S, vis.o, vis.d, vis.mint, vis.maxt)) return true;
     if (S.bvhNodes) return bvh_occluded(S, vis.o, vis.d, vis.mint, vis.maxt);
@@ -670,7 +680,7 @@ __device__ __forceinline__ bool lane_occluded(const DevScene &S, const RayD &vis
 
 template <bool STATS, int MODE, int NREG>
 __device__ int march_ray_blocked(const DevScene &S, const LiArgs &A, const pvol_ray &pr, Rng &rng, MarchLds &M, int lane,
-                                 WaveCounters &wc, f4 *LvOut, f4 *TrOut, RayRec rec) {
+                                 WaveCounters &wc, f4 *LvOut, f4 *TrOut, RayRec rec, TauRec *tauRec = nullptr) {
     static_assert(MODE == MODE_PAR || MODE == MODE_REPLAY, "ray-parallel modes only");
     if (S.volKind == PVOL_VOLUME_GRID || S.volKind == PVOL_VOLUME_NONE || A.transmittanceOnly) return 2;
     const int q = lane & 7;
@@ -685,6 +695,7 @@ __device__ int march_ray_blocked(const DevScene &S, const LiArgs &A, const pvol_
     ray.mint = pr.mint;
     ray.maxt = pr.maxt;
     f4 Lv = mk4(0.f), Tr = mk4(1.f);
+    float tLen = 0.f, tScale = 1.f;   // Tr as {length of the last step, roulette factor}
     float t0, t1;
     bool hit = vol_intersect(S, ray, &t0, &t1) && (t1 - t0) != 0.f;
     int nSamples = hit ? (int)ceilf((t1 - t0) / S.stepSize) : 0;
@@ -799,9 +810,11 @@ __device__ int march_ray_blocked(const DevScene &S, const LiArgs &A, const pvol_
                 const bool litJ = lane_i(lit ? 1 : 0, j) != 0;
                 const V3 pJ = v3(lane_f(p.x, j), lane_f(p.y, j), lane_f(p.z, j));
                 Tr = exp4(neg4(sigT * lenJ));   // assigned, not accumulated (photonvolume.cpp:155)
+                tLen = lenJ;
+                tScale = 1.f;
                 if (MODE == MODE_REPLAY) {
                     const unsigned int rb = (unsigned int)lane_i((int)recByte, j);
-                    if (rb & 0x80u) Tr = Tr / .5f;
+                    if (rb & 0x80u) { Tr = Tr / .5f; tScale = 2.f; }
                 }
                 const float dens = inJ ? 1.f : 0.f;
                 f4 ss = sigS * dens, sa = sigA * dens;
@@ -833,10 +846,11 @@ __device__ int march_ray_blocked(const DevScene &S, const LiArgs &A, const pvol_
                 Lv = (sa * (le * dens) * step) + (ss * L_i * step) + (Tr * Lv);
             }
         }
-        if (MODE == MODE_REPLAY && killed) Tr = mk4(0.f);
+        if (MODE == MODE_REPLAY && killed) { Tr = mk4(0.f); tScale = 0.f; }
     }
     *LvOut = Lv;
     *TrOut = Tr;
+    if (tauRec) *tauRec = TauRec{tLen, tScale};
     return 0;
 }
 
@@ -928,8 +942,10 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
         const unsigned long long d0 = rng.draws;
         f4 Lv, Tr;
         RayRec none = {0, 0, 0};
-        march_ray<STATS, MODE_SEQ, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, none);
+        TauRec tr = {0.f, 1.f};
+        march_ray<STATS, MODE_SEQ, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, none, &tr);
         write_outputs(S, A, ri, Lv, Tr, lane);
+        if (A.tauOut && lane == 0) A.tauOut[ri] = tr;
         if (A.draws && lane == 0) A.draws[ri] = (uint32_t)(rng.draws - d0);
     }
     if (lane == 0) A.streams[sidx].end_draw = rng.draws;
@@ -997,14 +1013,16 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
             rng.draws = 0;
             f4 Lv, Tr;
             RayRec none = {0, 0, 0};
-            int brc = march_ray_blocked<STATS, MODE_PAR, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, none);
+            TauRec tr = {0.f, 1.f};
+            int brc = march_ray_blocked<STATS, MODE_PAR, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, none, &tr);
             bool okRay = (brc == 0);
-            if (brc == 2) { rng.draws = 0; okRay = march_ray<STATS, MODE_PAR, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, none); }
+            if (brc == 2) { rng.draws = 0; okRay = march_ray<STATS, MODE_PAR, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, none, &tr); }
             if (!okRay) {
                 if (lane == 0) atomicOr(A.needSeq, 1u);
                 continue;
             }
             write_outputs(S, A, ri, Lv, Tr, lane);
+            if (A.tauOut && lane == 0) A.tauOut[ri] = tr;
             if (A.draws && lane == 0) A.draws[ri] = (uint32_t)rng.draws;
             acc += rng.draws + pr.rng_skip;
         }
@@ -1113,9 +1131,11 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
             const pvol_ray pr = A.rays[ri];
             RayRec rec = ray_rec(A.records + ((size_t)sidx * A.sliceM + l) * A.recStride, S.maxSteps, grid);
             f4 Lv, Tr;
-            if (march_ray_blocked<STATS, MODE_REPLAY, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec) == 2)
-                march_ray<STATS, MODE_REPLAY, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec);
+            TauRec tr = {0.f, 1.f};
+            if (march_ray_blocked<STATS, MODE_REPLAY, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec, &tr) == 2)
+                march_ray<STATS, MODE_REPLAY, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec, &tr);
             write_outputs(S, A, ri, Lv, Tr, lane);
+            if (A.tauOut && lane == 0) A.tauOut[ri] = tr;
         }
     }
     flush_counters<STATS>(A.counters, wc, tk0, lane);

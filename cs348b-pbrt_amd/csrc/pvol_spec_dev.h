@@ -121,7 +121,8 @@ __global__ __launch_bounds__(256) void spec_compose_kernel(SpecComposeArgs A) {
     A.link[ri] = link | SPEC_LINK_DONE;
     const DevScene &S = *A.scene;
     const uint32_t base = link >> SPEC_LINK_COUNT_BITS, n = link & ((1u << SPEC_LINK_COUNT_BITS) - 1u);
-    const float kT = -1.442695041f * A.tau[ri];
+    const TauRec tr = A.tau[ri];
+    const float kT = -1.442695041f * tr.len;
     float x = 0.f, y = 0.f, z = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
     for (int b = 0; b < 30; ++b) {
         float acc[SPEC_MAX_DEPTH + 1];   // acc[D]: what the children of the pending depth-(D-1) ray have brought in so far
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(256) void spec_compose_kernel(SpecComposeArgs A) {
             for (int dd = 1; dd <= SPEC_MAX_DEPTH; ++dd) if (dd == D) acc[dd] += add;
         }
         const float Ls = acc[1];
-        const float Tb = __builtin_amdgcn_exp2f((S.sigA[b] + S.sigS[b]) * kT);
+        const float Tb = tr.scale * __builtin_amdgcn_exp2f((S.sigA[b] + S.sigS[b]) * kT);
         const float v = Tb * Ls;
         x += S.cieX[b] * v; y += S.cieY[b] * v; z += S.cieZ[b] * v;
         sx += S.cieX[b] * Ls; sy += S.cieY[b] * Ls; sz += S.cieZ[b] * Ls;

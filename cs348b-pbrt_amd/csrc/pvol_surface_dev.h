@@ -123,7 +123,10 @@ __device__ uint32_t surf_count_draws(const DevScene &S, const SurfHit &h, V3 d, 
     const bool lambert = m.kind == PVOL_MATERIAL_MATTE && m.nBxdf > 0;   // MatteMaterial::GetBSDF adds the Lambertian only for a non-black Kd
     const V3 wo = -d;
     uint32_t n = 0;
-    for (int ln = 0; ln < S.nLights; ++ln) n += surf_light(S, ln, h.p, h.rayEps, h.nn, wo, lambert, blackMask).take ? 1u : 0u;
+    // one offset per unoccluded light sample, drawn by the shadow ray's Transmittance -- which returns 1 without drawing when the
+    // scene has no volume region (photonvolume.cpp:18-26)
+    if (S.volKind != PVOL_VOLUME_NONE)
+        for (int ln = 0; ln < S.nLights; ++ln) n += surf_light(S, ln, h.p, h.rayEps, h.nn, wo, lambert, blackMask).take ? 1u : 0u;
     if (S.surf.nPhotons > 0u && lambert) n += 144u;     // LPhoton(causticMap): two BSDF::rho(wo, rng)
     if (depth + 1 < S.surf.maxSpecularDepth) n += 6u;   // SpecularReflect + SpecularTransmit: BSDFSample(rng) each
     return n;
@@ -543,11 +546,12 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
 #pragma unroll
             for (int b = 0; b < 30; ++b) op[b] += op[30 + b] * Ls[b];
         } else if (hit) {
-            const float kT = -1.442695041f * A.tau[ri];
+            const TauRec tr = A.tau[ri];
+            const float kT = -1.442695041f * tr.len;
             float x = 0.f, y = 0.f, z = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
 #pragma unroll
-            for (int b = 0; b < 30; ++b) {
-                const float Tb = __builtin_amdgcn_exp2f((S.sigA[b] + S.sigS[b]) * kT);
+            for (int b = 0; b < 30; ++b) {   // sigma_t of the rainbow kind too: RainbowVolume is a HomogeneousVolumeDensity
+                const float Tb = tr.scale * __builtin_amdgcn_exp2f((S.sigA[b] + S.sigS[b]) * kT);
                 const float v = Tb * Ls[b];
                 x += S.cieX[b] * v; y += S.cieY[b] * v; z += S.cieZ[b] * v;
                 sx += S.cieX[b] * Ls[b]; sy += S.cieY[b] * Ls[b]; sz += S.cieZ[b] * Ls[b];

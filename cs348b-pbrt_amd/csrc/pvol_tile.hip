@@ -306,7 +306,7 @@ extern "C" int pvol_render_tasks_device(pvol_ctx *c, const pvol_camera *camera, 
             c->specSurfOut = debug && debug->d_surf_xyz ? debug->d_surf_xyz + 3 * doneRays : 0;
         }
         if (surfOn && nRays) {
-            const size_t want = 4 * nRays;
+            const size_t want = sizeof(TauRec) * nRays;
             if (want > c->tauBytes) {
                 hipStreamSynchronize(stream);
                 if (c->dTau) hipFree(c->dTau);

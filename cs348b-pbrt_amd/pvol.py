@@ -316,7 +316,9 @@ class PhotonVolume:
                                from_preprocess=False, off=False, n_indirect=0):
         """PhotonIntegrator in front of the volume term (CreatePhotonMapSurfaceIntegrator, photonmap.cpp:336-363: nused 50,
         maxdist .1, maxspeculardepth 5).  `caustic` = (p[n,3], wo[n,3], alpha[n,30]) with `n_paths`, or from_preprocess=True to
-        take the caustic photons the last preprocess() kept; off=True disables."""
+        take the caustic photons the last preprocess() kept; off=True disables.  Any medium but a VolumeGrid (for which
+        render_tasks raises PVOL_E_UNSUPPORTED): none, homogeneous or rainbow, at any nused and phase function, with or without
+        a volume photon map, dense enough for the Russian roulette included."""
         if off:
             _check(lib().pvol_set_surface_integrator(self._h, None, None, None, None, 0), "pvol_set_surface_integrator")
             return

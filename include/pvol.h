@@ -451,12 +451,16 @@ int pvol_render_tasks_device(pvol_ctx *ctx, const pvol_camera *camera, const pvo
  * SamplerRendererTask::Run then computes Ls = surface Li, and the film receives T * Ls + Lvi
  * (samplerrenderer.cpp:95-97,239-251).  p/wo/alpha: the caustic map's n photons (p 3, wo 3, alpha 30
  * floats each; n == 0: no caustic map, as when the shooter stored no caustic photon).
- * PVOL_E_UNSUPPORTED: a triangle of the scene carries a non-matte material, or an indirect photon map exists
- * (sp->n_indirect_photons > 0, or use_preprocess_store and the shooter kept indirect photons) (here), or the volume /
- * nused lie outside li_group_kernel's domain (from pvol_render_tasks_device).  A
- * lookup with more than 2048 caustic photons within maxdist of ONE hit point is counted as an error
- * (pvol_check_errors), never truncated.  PVOL_E_INVALID: use_preprocess_store without a pvol_preprocess that ran with
- * params.keep_surface_photons.  pvol_set_scene disables the surface integrator again. */
+ * Media covered: none, homogeneous and rainbow, at any nused and Henyey-Greenstein g, with or without a volume photon
+ * map, with any number of lights, and dense enough for the Russian roulette (T is the last march step's Tr, doubled by a
+ * survival, 0 after a kill: photonvolume.cpp:150-160).  Glass (the specular recursion, maxspeculardepth <= 5) composes
+ * its T the same way.
+ * PVOL_E_UNSUPPORTED: a triangle of the scene carries a material other than matte or glass, maxspeculardepth > 5 with
+ * glass present, or an indirect photon map exists (sp->n_indirect_photons > 0, or use_preprocess_store and the shooter kept
+ * indirect photons) (here); a VolumeGrid medium, whose T is a product of stepped taus with drawn offsets, or glass in a
+ * medium dense enough for the roulette (from pvol_render_tasks_device).  PVOL_E_INVALID:
+ * use_preprocess_store without a pvol_preprocess that ran with params.keep_surface_photons.  pvol_set_scene disables the
+ * surface integrator again. */
 int pvol_set_surface_integrator(pvol_ctx *ctx, const pvol_surface_params *sp, const float *p, const float *wo,
                                 const float *alpha, uint32_t n);
 

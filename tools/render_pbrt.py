@@ -7,12 +7,14 @@ image film) -> RGB.
 
 The file's own Film / Sampler / integrator parameters are used unless overridden.  The surface integrator (direct lighting +
 caustic estimate on matte surfaces) is switched on when the scene asks for "photonmap" and the device path
-covers it (matte and glass surfaces -- the specular recursion included --, homogeneous isotropic medium, no indirect map); otherwise
-Ls = 0 and the image holds the volume term alone -- the tool says which."""
+covers it (matte and glass surfaces -- the specular recursion included --, a homogeneous or rainbow medium at any nused and
+phase function, or no medium; no indirect map); otherwise (a VolumeGrid, an indirect map) Ls = 0 and the image holds the
+volume term alone -- the tool says which.  info["render_s"]: wall seconds of the frame's render_tasks (shoot excluded)."""
 import argparse
 import importlib
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -60,8 +62,11 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
         dev = torch.device("cuda:0")
         px = torch.zeros((yres, xres, 4), dtype=torch.float32, device=dev)
         rgb = torch.zeros((yres, xres, 3), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
         try:
             pv.render_tasks(cam, film, smp, ids, px.data_ptr())
+            torch.cuda.synchronize()
         except pvol.PvolError as e:
             if not used_surface:
                 raise
@@ -69,12 +74,16 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
             pv.set_surface_integrator(off=True)
             used_surface = False
             px.zero_()
+            t0 = time.perf_counter()
             pv.render_tasks(cam, film, smp, ids, px.data_ptr())
+            torch.cuda.synchronize()
+        render_s = time.perf_counter() - t0
         pv.film_resolve(film, px.data_ptr(), rgb.data_ptr())
         torch.cuda.synchronize()
         pv.check_errors()
         return rgb.cpu().numpy(), {"xres": xres, "yres": yres, "spp": spp, "surface_integrator": used_surface, "kernel": pv.march_kernel_name(),
-                                   "photons": int(st["stored_volume"]), "caustic_photons": int(st["stored_caustic"])}
+                                   "photons": int(st["stored_volume"]), "caustic_photons": int(st["stored_caustic"]),
+                                   "render_s": render_s}
     finally:
         pv.close()
 
