@@ -121,7 +121,7 @@ struct pvol_ctx {
     uint32_t *dSpecLink = 0;        // per primary ray of a render batch
     size_t specLinkBytes = 0;
     float *specSurfOut = 0;         // set by the render driver around pvol_launch_batch: where the composition reports the surface term
-    double exchangeSeconds = 0.0;   // last pvol_preprocess_ranks: time in its all-gathers (part of prepSeconds[0])
+    double exchangeSeconds = 0.0;   // last pvol_preprocess: time in its all-gathers (part of prepSeconds[0]; 0 after pvol_preprocess_blocks)
     double prepSeconds[2] = {0.0, 0.0};   // last pvol_preprocess: shooting (all rounds + merges), search-structure build
     // tile driver work buffers (grown on demand, pvol_tile.hip)
     void *dTile[6] = {0, 0, 0, 0, 0, 0};
@@ -142,5 +142,7 @@ void pvol_free_photons(pvol_ctx *c);
 void pvol_free_surface_stores(pvol_ctx *c);
 void pvol_free_caustic_map(pvol_ctx *c);
 int pvol_push_scene(pvol_ctx *c);
+// an RCCL function by name, bound at run time once per process (pvol_tile.hip); 0 when no RCCL is in reach
+void *pvol_rccl_symbol(const char *name);
 }
 #endif

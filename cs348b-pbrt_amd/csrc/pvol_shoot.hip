@@ -22,39 +22,13 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "pvol_rng_dev.h"
+#include "pvol_shoot_args.h"
 
 #define SH_MAX_DEPTH 24   // frames; deeper recursion aborts the path and is counted
 #define NBIN 30
 #define SH_STATE_WORDS 640   // per task in global memory: mt[624], mti, totalPaths, pad
 
 // BxDFType bits, core/reflection.h:107-121
-
-struct ShootArgs {
-    const DevScene *scene;
-    const DevShootScene *shoot;
-    uint32_t nTasks;
-    const uint32_t *stateIn;  // [nTasks][SH_STATE_WORDS]
-    uint32_t *stateOut;       // same layout; a round that has to be redone (block buffer too small) restarts from stateIn
-    uint32_t *halton;         // [nTasks][48] permutation tables (bases 2,3,5,7,11,13: 41 entries)
-    const uint32_t *flags;    // [nTasks] bit0 causticDone, bit1 indirectDone, bit2 volumeDone, bit3 finished
-    float *localPhotons;      // [nTasks][cap][36]: p(3) wi(3) alpha(30)
-    uint32_t *localCounts;    // [nTasks][8]: volume, caustic, direct, indirect deposits of this block, surface records kept, radiance photons kept
-    uint32_t cap;
-    // the surface stores of photonshooter.cpp:148-189, kept only on request (pvol_params.keep_surface_photons): every deposit
-    // is one record Photon(p, alpha, wo) with its kind (0 caustic, 1 direct, 2 indirect), in deposit order
-    float *localSurf;         // [nTasks][capS][36]: p(3) wo(3) alpha(30)
-    uint32_t *localSurfKind;  // [nTasks][capS]
-    uint32_t capS;
-    float *localRad;          // [nTasks][capR][8]: p(3) n(3) material index, pad  (RadiancePhoton + whose rho it carries)
-    uint32_t capR;
-    int keepSurface;
-    unsigned long long *stats;  // paths, follow_calls, no_hit, march_steps, interactions, absorbed, split_children, overflow
-    int init;                 // 1: seed RNG + Halton tables instead of shooting
-    uint32_t blockPaths;      // paths per task and round (4096: PhotonShootingTask::Run's block, photonshooter.cpp:247)
-    int gridVolume;           // the medium is a VolumeGrid: the kernel takes GRID_KMAX x 64 more LDS words (march_grid)
-    const uint32_t *taskIds;  // [nTasks] global task number of each slot (one rank's share, pvol_preprocess_ranks), or null:
-                              // slot == task.  Every array above is indexed by slot; the RNG seed and Halton permutation by task
-};
 
 // ------------------------------------------------------------------------------------------ spectra: lane b == bin b
 __device__ __forceinline__ float sp_y(float a, float cieYl) {   // core/spectrum.h:433-439, the serial sum
@@ -840,18 +814,6 @@ __global__ __launch_bounds__(LANES, WPE) void shoot_kernel(ShootArgs A) {
     }
 }
 
-// merge of one task's block into the global photon arrays: alpha /= float(nshot) with the RUNNING nshot
-// of that task's turn (photonshooter.cpp:333)
-struct MergeArgs {
-    const float *localPhotons;
-    uint32_t cap;
-    const uint32_t *srcTask;   // per merged segment: task, count, destination offset, nshot
-    const uint32_t *count;
-    const uint32_t *dstOff;
-    const float *nshot;
-    uint32_t nSeg;
-    float *p, *wi, *alpha;     // destination raw arrays
-};
 __global__ void merge_kernel(MergeArgs M) {
     for (uint32_t seg = blockIdx.x; seg < M.nSeg; seg += gridDim.x) {
         const uint32_t cnt = M.count[seg];
@@ -868,17 +830,7 @@ __global__ void merge_kernel(MergeArgs M) {
     }
 }
 
-// merge of one task's surface records into the per-kind arrays, in deposit order (photonshooter.cpp:303-327), and of its
-// radiance photons (:341-349).  One wave per segment; `take` has bit k set when kind k is merged at this task's turn.
-struct SurfMergeArgs {
-    const float *localSurf; const uint32_t *localSurfKind; uint32_t capS;
-    const float *localRad; uint32_t capR;
-    const uint32_t *srcTask, *nSurf, *take, *dstOff;   // dstOff: [nSeg][4] = caustic, direct, indirect, radiance
-    const uint32_t *nRad;
-    uint32_t nSeg;
-    float *p[3], *wo[3], *alpha[3];
-    float *rad;   // [n][8]
-};
+// one wave per segment (SurfMergeArgs)
 __global__ __launch_bounds__(64) void merge_surface_kernel(SurfMergeArgs M) {
     const int lane = threadIdx.x;
     for (uint32_t seg = blockIdx.x; seg < M.nSeg; seg += gridDim.x) {
@@ -933,20 +885,7 @@ extern "C" hipError_t pvol_launch_merge(const MergeArgs *m, hipStream_t stream) 
 }
 
 // ------------------------------------------------------------------------------------------ sharded shoot (pvol_preprocess_ranks)
-// After the last round every rank holds the all-gathered local arrays of all ranks: rank r's block is `rankStride` floats, field f
-// of it (p, wi|wo, alpha; or the radiance record) `fieldOff[f]` floats in, `width[f]` floats per row, rows in that rank's append
-// order.  A segment (src rank, local row, global row, count) is one task's contribution at its turn in the merge; the segments are
-// in global order and cover [0, nRows) without gaps, so global row g finds its segment by binary search over segGlobal.
-struct PlaceArgs {
-    const float *recv;
-    uint64_t rankStride;
-    uint64_t fieldOff;
-    uint32_t width;
-    const uint32_t *segSrc, *segLocal, *segGlobal;
-    uint32_t nSeg;
-    uint64_t nRows;
-    float *dst;   // [nRows][width]
-};
+// global row g of PlaceArgs finds its segment by binary search over segGlobal
 __global__ __launch_bounds__(256) void place_rows_kernel(PlaceArgs P) {
     const uint64_t nWords = P.nRows * P.width;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nWords; i += (uint64_t)gridDim.x * blockDim.x) {

@@ -1,99 +1,50 @@
 // pvol_shoot_host.hip -- host side of PhotonShooter::Preprocess (core/photonshooter.cpp:457-526):
 // rounds of one 4096-path block per live virtual task on the device, merged in task order with the
 // reference's bookkeeping (running nshot, per-task *Done flags, the "unable to store enough photons"
-// abort, photonshooter.cpp:280-356), then the search-structure build.
+// abort, photonshooter.cpp:280-356), then the search-structure build.  One driver serves the single-GPU
+// shoot and the shoot sharded over ranks (see "the shoot driver" below).
 #include <math.h>
 #include <string.h>
 #include <chrono>
 #include <algorithm>
 #include <vector>
 
-#include <dlfcn.h>
 #include <stdlib.h>
 #include <mutex>
-#include <rccl/rccl.h>   // types and enums only: the library is bound at run time (pvol_preprocess_ranks)
+#include <rccl/rccl.h>   // types and enums only: the library is bound at run time (pvol_rccl_symbol)
 
 #include "pvol_host.h"
-
-struct ShootArgs {
-    const DevScene *scene;
-    const DevShootScene *shoot;
-    uint32_t nTasks;
-    const uint32_t *stateIn;
-    uint32_t *stateOut;
-    uint32_t *halton;
-    const uint32_t *flags;
-    float *localPhotons;
-    uint32_t *localCounts;
-    uint32_t cap;
-    float *localSurf;
-    uint32_t *localSurfKind;
-    uint32_t capS;
-    float *localRad;
-    uint32_t capR;
-    int keepSurface;
-    unsigned long long *stats;
-    int init;
-    uint32_t blockPaths;      // paths per task and round (4096: PhotonShootingTask::Run's block, photonshooter.cpp:247)
-    int gridVolume;           // the medium is a VolumeGrid: the kernel takes GRID_KMAX x 64 more LDS words (march_grid)
-    const uint32_t *taskIds;  // [nTasks] global task number of each slot, or null: slot == task
-};
-struct SurfMergeArgs {
-    const float *localSurf; const uint32_t *localSurfKind; uint32_t capS;
-    const float *localRad; uint32_t capR;
-    const uint32_t *srcTask, *nSurf, *take, *dstOff;
-    const uint32_t *nRad;
-    uint32_t nSeg;
-    float *p[3], *wo[3], *alpha[3];
-    float *rad;
-};
-extern "C" hipError_t pvol_launch_merge_surface(const SurfMergeArgs *m, hipStream_t stream);
-struct MergeArgs {
-    const float *localPhotons;
-    uint32_t cap;
-    const uint32_t *srcTask;
-    const uint32_t *count;
-    const uint32_t *dstOff;
-    const float *nshot;
-    uint32_t nSeg;
-    float *p, *wi, *alpha;
-};
-extern "C" hipError_t pvol_launch_shoot(const ShootArgs *a, hipStream_t stream);
-extern "C" size_t pvol_shoot_state_words(void);
-extern "C" hipError_t pvol_launch_merge(const MergeArgs *m, hipStream_t stream);
+#include "pvol_shoot_args.h"
 
 static bool ok(hipError_t e) { return e == hipSuccess; }
 
 namespace {
-struct DevArr {   // device array of floats that grows geometrically, keeping its contents
+struct DevArr {   // device array of floats that grows geometrically, keeping the `used` floats it holds
     float *d = 0;
-    size_t cap = 0;
-    bool need(size_t used, size_t want) {
-        if (want <= cap) return true;
-        size_t nc = std::max(want, cap * 2 + 1024);
-        float *nd = 0;
-        if (!ok(hipMalloc(&nd, sizeof(float) * nc))) return false;
-        if (used && d) hipMemcpy(nd, d, sizeof(float) * used, hipMemcpyDeviceToDevice);
-        hipFree(d);
-        d = nd; cap = nc;
+    size_t cap = 0, used = 0;
+    bool resize(size_t n) {
+        if (n > cap) {
+            size_t nc = std::max(n, cap * 2 + 1024);
+            float *nd = 0;
+            if (!ok(hipMalloc(&nd, sizeof(float) * nc))) return false;
+            if (used && d) hipMemcpy(nd, d, sizeof(float) * used, hipMemcpyDeviceToDevice);
+            hipFree(d);
+            d = nd; cap = nc;
+        }
+        used = n;
         return true;
     }
 };
-struct Buffers {
+struct Buffers {   // one rank's block pools and round tables
     uint32_t *stateA = 0, *stateB = 0, *halton = 0, *flags = 0, *localCounts = 0, *localSurfKind = 0;
     float *localPhotons = 0, *localSurf = 0, *localRad = 0;
     unsigned long long *stats = 0;
     uint32_t *seg = 0;         // host-built segment tables of a round: 3 words per task for the volume merge, 8 for the surface merge
     float *segNshot = 0;
-    DevArr p, wi, alpha;       // merged volume map
-    DevArr sp[3], swo[3], salpha[3], rad;   // merged surface stores (kept on request)
-    void release(bool keepMaps) {
+    uint32_t *taskIds = 0;     // slot -> task (ShootArgs::taskIds), only with a communicator
+    void release() {
         hipFree(stateA); hipFree(stateB); hipFree(halton); hipFree(flags); hipFree(localCounts); hipFree(localSurfKind);
-        hipFree(localPhotons); hipFree(localSurf); hipFree(localRad); hipFree(stats); hipFree(seg); hipFree(segNshot);
-        if (!keepMaps) {
-            hipFree(p.d); hipFree(wi.d); hipFree(alpha.d); hipFree(rad.d);
-            for (int k = 0; k < 3; ++k) { hipFree(sp[k].d); hipFree(swo[k].d); hipFree(salpha[k].d); }
-        }
+        hipFree(localPhotons); hipFree(localSurf); hipFree(localRad); hipFree(stats); hipFree(seg); hipFree(segNshot); hipFree(taskIds);
     }
 };
 }  // namespace
@@ -105,256 +56,6 @@ extern "C" void pvol_free_surface_stores(pvol_ctx *c) {
     }
     hipFree(c->dRad); c->dRad = 0; c->nRad = 0;
     c->surfKept = false;
-}
-
-extern "C" int pvol_preprocess(pvol_ctx *c, uint32_t n_tasks) { return pvol_preprocess_blocks(c, n_tasks, 4096); }
-
-extern "C" int pvol_preprocess_blocks(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths) {
-    if (!c || n_tasks == 0 || n_tasks > 65536 || block_paths == 0 || block_paths > 4096) return PVOL_E_INVALID;
-    if (!c->haveScene) return PVOL_E_NO_SCENE;
-    std::lock_guard<std::recursive_mutex> api(c->apiMu);
-    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    hipDeviceSynchronize();
-    pvol_free_photons(c);
-    pvol_free_surface_stores(c);
-    DevScene &h = c->hs;
-    h.nPhotons = 0; h.cellStart = 0; h.subStart = 0; h.pos4 = 0; h.alpha4 = 0; h.wi4 = 0;
-    memset(c->shootStats, 0, sizeof(c->shootStats));
-    if (c->hs.nLights == 0) return pvol_push_scene(c);   // photonshooter.cpp:459
-    int rc = pvol_push_scene(c);
-    if (rc != PVOL_OK) return rc;
-
-    const auto tShoot0 = std::chrono::steady_clock::now();
-    c->prepSeconds[0] = c->prepSeconds[1] = 0.0;
-    const uint32_t T = n_tasks;
-    const uint32_t blockSize = block_paths;
-    const uint32_t giveUpShot = 4096;   // the reference's constant in its give-up test (photonshooter.cpp:283-290), whatever the block
-    const size_t SW = pvol_shoot_state_words();
-    const bool keep = c->params.keep_surface_photons != 0;
-    // Room for one block of one task.  Spectral splitting stores up to ~3 photons per path (SURVEY 6) but the usual yield is
-    // ~10 photons per 4096-path block, so the pools start small (T x 256 x 144 B) and a round in which some task outgrew
-    // one is REDONE with a larger pool from the saved RNG states (the round is a pure function of them): nothing is dropped
-    // and nothing is sized for the worst case.
-    uint32_t cap = 256, capS = keep ? 256 : 1, capR = keep ? 64 : 1;
-    const uint32_t capMax = (uint32_t)std::min<size_t>(65536, std::max<size_t>(256, ((size_t)48 << 30) / ((size_t)T * 144)));
-    Buffers B;
-    bool good = ok(hipMalloc(&B.stateA, sizeof(uint32_t) * SW * (size_t)T)) && ok(hipMalloc(&B.stateB, sizeof(uint32_t) * SW * (size_t)T)) &&
-                ok(hipMalloc(&B.halton, sizeof(uint32_t) * 48 * (size_t)T)) && ok(hipMalloc(&B.flags, sizeof(uint32_t) * T)) &&
-                ok(hipMalloc(&B.localCounts, sizeof(uint32_t) * 8 * (size_t)T)) &&
-                ok(hipMalloc(&B.localPhotons, sizeof(float) * 36 * (size_t)cap * T)) && ok(hipMalloc(&B.stats, sizeof(unsigned long long) * 8)) &&
-                ok(hipMalloc(&B.localSurf, sizeof(float) * 36 * (size_t)capS * T)) && ok(hipMalloc(&B.localSurfKind, sizeof(uint32_t) * (size_t)capS * T)) &&
-                ok(hipMalloc(&B.localRad, sizeof(float) * 8 * (size_t)capR * T)) &&
-                ok(hipMalloc(&B.seg, sizeof(uint32_t) * 11 * (size_t)T)) && ok(hipMalloc(&B.segNshot, sizeof(float) * T)) &&
-                ok(hipMemset(B.stats, 0, sizeof(unsigned long long) * 8));
-    if (!good) { B.release(false); return PVOL_E_NO_MEMORY; }
-
-    ShootArgs A;
-    A.scene = c->ds; A.shoot = c->dsh; A.nTasks = T; A.stateIn = B.stateA; A.stateOut = B.stateA; A.halton = B.halton; A.flags = B.flags;
-    A.localPhotons = B.localPhotons; A.localCounts = B.localCounts; A.cap = cap; A.stats = B.stats; A.init = 1;
-    A.localSurf = B.localSurf; A.localSurfKind = B.localSurfKind; A.capS = capS; A.localRad = B.localRad; A.capR = capR; A.keepSurface = keep ? 1 : 0;
-    A.gridVolume = c->hs.volKind == PVOL_VOLUME_GRID ? 1 : 0;
-    A.blockPaths = blockSize;
-    A.taskIds = 0;
-    if (!ok(pvol_launch_shoot(&A, 0)) || !ok(hipDeviceSynchronize())) { B.release(false); return PVOL_E_NO_DEVICE; }
-    A.init = 0;
-    A.stateOut = B.stateB;
-
-    const pvol_params &P = c->params;
-    std::vector<uint32_t> flags(T), counts(8 * (size_t)T);
-    // segment tables of a round: volume {task, count, offset} and surface {task, nSurf, take, off[4], nRad}
-    std::vector<uint32_t> vTask, vCount, vOff, sTask, sN, sTake, sOff, sRad;
-    std::vector<float> vNshot;
-    unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    flags.assign(T, (P.n_caustic_photons == 0 ? 1u : 0u) | (P.n_indirect_photons == 0 ? 2u : 0u) | (P.n_volume_photons == 0 ? 4u : 0u));
-    uint32_t nshot = 0;
-    uint64_t nCaustic = 0, nIndirect = 0, nDirect = 0, nRadTotal = 0;
-    uint32_t nCausticPaths = 0, nIndirectPaths = 0, nDirectPaths = 0;
-    size_t nVolume = 0;
-    bool abortTasks = false;
-    uint32_t stallRounds = 0;
-    rc = PVOL_OK;
-    auto unsuccessful = [](uint32_t needed, uint64_t found, uint32_t shot) { return (found < needed && (found == 0 || found < shot / 1024)); };   // photonshooter.cpp:37-39
-    for (;;) {
-        bool anyLive = false;
-        for (uint32_t t = 0; t < T; ++t) anyLive = anyLive || !(flags[t] & 8u);
-        if (!anyLive) break;
-        if (!ok(hipMemcpy(B.flags, flags.data(), sizeof(uint32_t) * T, hipMemcpyHostToDevice))) { rc = PVOL_E_NO_DEVICE; break; }
-        bool redo = false;
-        do {   // one 4096-path block per live task; redone from the same states if a task's block outgrew a buffer
-            redo = false;
-            unsigned long long rs[8];
-            if (!ok(hipMemset(B.stats, 0, sizeof(rs))) || !ok(pvol_launch_shoot(&A, 0)) ||
-                !ok(hipMemcpy(counts.data(), B.localCounts, sizeof(uint32_t) * 8 * (size_t)T, hipMemcpyDeviceToHost)) ||
-                !ok(hipMemcpy(rs, B.stats, sizeof(rs), hipMemcpyDeviceToHost))) { rc = PVOL_E_NO_DEVICE; break; }
-            uint32_t most = 0, mostS = 0, mostR = 0;
-            for (uint32_t t = 0; t < T; ++t) {
-                if (flags[t] & 8u) continue;
-                if (!(flags[t] & 4u)) most = std::max(most, counts[8 * (size_t)t]);
-                mostS = std::max(mostS, counts[8 * (size_t)t + 4]);
-                mostR = std::max(mostR, counts[8 * (size_t)t + 5]);
-            }
-            if (most > cap) {
-                if (most > capMax) { rc = PVOL_E_LIMIT; break; }
-                cap = std::min<uint32_t>(capMax, std::max<uint32_t>(most + most / 4, cap * 4));
-                hipFree(B.localPhotons); B.localPhotons = 0;
-                if (!ok(hipMalloc(&B.localPhotons, sizeof(float) * 36 * (size_t)cap * T))) { rc = PVOL_E_NO_MEMORY; break; }
-                A.localPhotons = B.localPhotons; A.cap = cap;
-                redo = true;
-            }
-            if (keep && mostS > capS) {
-                if (mostS > capMax) { rc = PVOL_E_LIMIT; break; }
-                capS = std::min<uint32_t>(capMax, std::max<uint32_t>(mostS + mostS / 4, capS * 4));
-                hipFree(B.localSurf); hipFree(B.localSurfKind); B.localSurf = 0; B.localSurfKind = 0;
-                if (!ok(hipMalloc(&B.localSurf, sizeof(float) * 36 * (size_t)capS * T)) || !ok(hipMalloc(&B.localSurfKind, sizeof(uint32_t) * (size_t)capS * T))) { rc = PVOL_E_NO_MEMORY; break; }
-                A.localSurf = B.localSurf; A.localSurfKind = B.localSurfKind; A.capS = capS;
-                redo = true;
-            }
-            if (keep && mostR > capR) {
-                capR = std::max<uint32_t>(mostR + mostR / 4, capR * 4);
-                hipFree(B.localRad); B.localRad = 0;
-                if (!ok(hipMalloc(&B.localRad, sizeof(float) * 8 * (size_t)capR * T))) { rc = PVOL_E_NO_MEMORY; break; }
-                A.localRad = B.localRad; A.capR = capR;
-                redo = true;
-            }
-            if (!redo) for (int i = 0; i < 8; ++i) st[i] += rs[i];
-        } while (redo);
-        if (rc != PVOL_OK) break;
-        { const uint32_t *tmp = A.stateIn; A.stateIn = A.stateOut; A.stateOut = const_cast<uint32_t *>(tmp); }   // the round stands
-        // merge in task order (photonshooter.cpp:280-351)
-        vTask.clear(); vCount.clear(); vOff.clear(); vNshot.clear();
-        sTask.clear(); sN.clear(); sTake.clear(); sOff.clear(); sRad.clear();
-        const size_t volBefore = nVolume;
-        const uint64_t surfBefore[4] = {nCaustic, nDirect, nIndirect, nRadTotal};
-        for (uint32_t t = 0; t < T; ++t) {
-            uint32_t &fl = flags[t];
-            if (fl & 8u) continue;
-            if (abortTasks) { fl |= 8u; continue; }
-            if (nshot > 500000 && (unsuccessful(P.n_caustic_photons, nCaustic, giveUpShot) || unsuccessful(P.n_indirect_photons, nIndirect, giveUpShot) ||
-                                   unsuccessful(P.n_volume_photons, nVolume, giveUpShot))) {
-                nVolume = 0; nCaustic = nIndirect = 0; nRadTotal = 0;   // photonshooter.cpp:292-298 erases caustic, indirect, volume, radiance
-                vTask.clear(); vCount.clear(); vOff.clear(); vNshot.clear();
-                sTask.clear(); sN.clear(); sTake.clear(); sOff.clear(); sRad.clear();
-                abortTasks = true;
-                fl |= 8u;
-                rc = PVOL_E_SHOOT_FAILED;
-                continue;
-            }
-            nshot += blockSize;
-            const uint32_t *lc = &counts[8 * (size_t)t];
-            uint32_t take = 0;
-            const uint32_t off[4] = {(uint32_t)nCaustic, (uint32_t)nDirect, (uint32_t)nIndirect, (uint32_t)nRadTotal};
-            if (!(fl & 2u)) {
-                take |= 2u | 4u;
-                nIndirectPaths += blockSize; nDirectPaths += blockSize;
-                nIndirect += lc[3];
-                if (nIndirect >= P.n_indirect_photons) fl |= 2u;
-                nDirect += lc[2];
-            }
-            if (!(fl & 1u)) {
-                take |= 1u;
-                nCausticPaths += blockSize;
-                nCaustic += lc[1];
-                if (nCaustic >= P.n_caustic_photons) fl |= 1u;
-            }
-            if (keep && (lc[4] || lc[5])) {
-                sTask.push_back(t); sN.push_back(lc[4]); sTake.push_back(take); sRad.push_back(lc[5]);
-                sOff.push_back(off[0]); sOff.push_back(off[1]); sOff.push_back(off[2]); sOff.push_back(off[3]);
-            }
-            nRadTotal += keep ? lc[5] : 0;
-            if (!(fl & 4u)) {
-                if (lc[0]) {
-                    vTask.push_back(t); vCount.push_back(lc[0]); vOff.push_back((uint32_t)nVolume); vNshot.push_back(float(nshot));
-                    nVolume += lc[0];
-                }
-                if (nVolume >= P.n_volume_photons) fl |= 4u;
-            }
-            if ((fl & 7u) == 7u) fl |= 8u;
-        }
-        if (!vTask.empty() && !abortTasks) {
-            if (!B.p.need(3 * volBefore, 3 * nVolume) || !B.wi.need(3 * volBefore, 3 * nVolume) || !B.alpha.need(30 * volBefore, 30 * nVolume)) { rc = PVOL_E_NO_MEMORY; break; }
-            MergeArgs M;
-            const size_t n = vTask.size();
-            M.localPhotons = B.localPhotons; M.cap = cap; M.srcTask = B.seg; M.count = B.seg + T; M.dstOff = B.seg + 2 * (size_t)T; M.nshot = B.segNshot;
-            M.nSeg = (uint32_t)n; M.p = B.p.d; M.wi = B.wi.d; M.alpha = B.alpha.d;
-            bool g2 = ok(hipMemcpy(B.seg, vTask.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
-                      ok(hipMemcpy(B.seg + T, vCount.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
-                      ok(hipMemcpy(B.seg + 2 * (size_t)T, vOff.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
-                      ok(hipMemcpy(B.segNshot, vNshot.data(), sizeof(float) * n, hipMemcpyHostToDevice)) &&
-                      ok(pvol_launch_merge(&M, 0)) && ok(hipDeviceSynchronize());
-            if (!g2) { rc = PVOL_E_NO_DEVICE; break; }
-        }
-        if (keep && !sTask.empty() && !abortTasks) {
-            const uint64_t after[3] = {nCaustic, nDirect, nIndirect};
-            bool g3 = true;
-            for (int k = 0; k < 3 && g3; ++k)
-                g3 = B.sp[k].need(3 * surfBefore[k], 3 * after[k]) && B.swo[k].need(3 * surfBefore[k], 3 * after[k]) && B.salpha[k].need(30 * surfBefore[k], 30 * after[k]);
-            g3 = g3 && B.rad.need(8 * surfBefore[3], 8 * nRadTotal);
-            if (!g3) { rc = PVOL_E_NO_MEMORY; break; }
-            SurfMergeArgs M;
-            const size_t n = sTask.size();
-            uint32_t *d = B.seg + 3 * (size_t)T;
-            M.localSurf = B.localSurf; M.localSurfKind = B.localSurfKind; M.capS = capS; M.localRad = B.localRad; M.capR = capR;
-            M.srcTask = d; M.nSurf = d + T; M.take = d + 2 * (size_t)T; M.nRad = d + 3 * (size_t)T; M.dstOff = d + 4 * (size_t)T;
-            M.nSeg = (uint32_t)n;
-            for (int k = 0; k < 3; ++k) { M.p[k] = B.sp[k].d; M.wo[k] = B.swo[k].d; M.alpha[k] = B.salpha[k].d; }
-            M.rad = B.rad.d;
-            g3 = ok(hipMemcpy(d, sTask.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
-                 ok(hipMemcpy(d + T, sN.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
-                 ok(hipMemcpy(d + 2 * (size_t)T, sTake.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
-                 ok(hipMemcpy(d + 3 * (size_t)T, sRad.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
-                 ok(hipMemcpy(d + 4 * (size_t)T, sOff.data(), sizeof(uint32_t) * 4 * n, hipMemcpyHostToDevice)) &&
-                 ok(pvol_launch_merge_surface(&M, 0)) && ok(hipDeviceSynchronize());
-            if (!g3) { rc = PVOL_E_NO_DEVICE; break; }
-        }
-        if (rc == PVOL_E_LIMIT || rc == PVOL_E_NO_DEVICE) break;
-        // The reference has no exit for a store that stops growing after a good start (its `unsuccessful` test, photonshooter.cpp:37-39,
-        // passes once found >= 4): e.g. a matte scene whose "caustic" photons all come through the medium, after the volume map is
-        // full -- it would shoot forever.  Here 256 rounds in a row without a single photon for any store still wanted end the
-        // pass the way the reference's own abort does (stores erased, PVOL_E_SHOOT_FAILED).
-        if (!abortTasks) {
-            const bool progress = nCaustic != surfBefore[0] || nIndirect != surfBefore[2] || nVolume != volBefore;
-            stallRounds = progress ? 0u : stallRounds + 1u;
-            if (stallRounds >= 256u) {
-                nVolume = 0; nCaustic = nIndirect = 0; nRadTotal = 0;
-                for (uint32_t t = 0; t < T; ++t) flags[t] |= 8u;
-                abortTasks = true;
-                rc = PVOL_E_SHOOT_FAILED;
-            }
-        }
-    }
-    // paths, follow_calls, no_hit, march_steps, interactions, absorbed, stored_volume, caustic, direct, indirect, split_children, nshot
-    c->shootStats[0] = st[0]; c->shootStats[1] = st[1]; c->shootStats[2] = st[2]; c->shootStats[3] = st[3]; c->shootStats[4] = st[4];
-    c->shootStats[5] = st[5]; c->shootStats[6] = nVolume; c->shootStats[7] = nCaustic; c->shootStats[8] = nDirect; c->shootStats[9] = nIndirect;
-    c->shootStats[10] = st[6]; c->shootStats[11] = nshot;
-    c->prepSeconds[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - tShoot0).count();
-    if (rc == PVOL_OK && st[7] != 0) rc = PVOL_E_LIMIT;   // a frame stack overflowed: never silently drop photons
-    if (rc == PVOL_OK && keep) {   // the surface stores go to the context whatever happens to the volume map
-        const uint64_t cnt[3] = {nCaustic, nDirect, nIndirect};
-        const uint32_t paths[3] = {nCausticPaths, nDirectPaths, nIndirectPaths};
-        for (int k = 0; k < 3; ++k) {
-            c->surf[k].p = B.sp[k].d; c->surf[k].wo = B.swo[k].d; c->surf[k].alpha = B.salpha[k].d;
-            c->surf[k].n = (uint32_t)cnt[k]; c->surf[k].nPaths = paths[k];
-            B.sp[k].d = B.swo[k].d = B.salpha[k].d = 0;
-        }
-        c->dRad = B.rad.d; c->nRad = (uint32_t)nRadTotal;
-        B.rad.d = 0;
-        c->surfKept = true;
-    }
-    if (rc != PVOL_OK || nVolume == 0) {
-        B.release(false);
-        return rc;
-    }
-    // hand the merged arrays to the context and build the search structure
-    std::vector<float> hostP(3 * nVolume);
-    if (!ok(hipMemcpy(hostP.data(), B.p.d, sizeof(float) * 3 * nVolume, hipMemcpyDeviceToHost))) { B.release(false); return PVOL_E_NO_DEVICE; }
-    c->dRawP = B.p.d; c->dRawWi = B.wi.d; c->dRawAlpha = B.alpha.d;
-    B.p.d = B.wi.d = B.alpha.d = 0;
-    B.release(false);
-    const auto tBuild0 = std::chrono::steady_clock::now();
-    rc = pvol_finish_map(c, (uint32_t)nVolume, hostP.data());
-    hipDeviceSynchronize();
-    c->prepSeconds[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - tBuild0).count();
-    return rc;
 }
 
 extern "C" int pvol_surface_photon_count(pvol_ctx *c, int kind, uint32_t *n, uint32_t *nPaths) {
@@ -410,47 +111,25 @@ extern "C" int pvol_get_shoot_stats(pvol_ctx *c, uint64_t *out12) {
     return PVOL_OK;
 }
 
-// ------------------------------------------------------------------------------------------ sharded shoot
-// pvol_preprocess_ranks: rank r shoots only the tasks pvol_partition_tasks deals it.  Every merge decision of the loop above is a
-// pure function of the round's count table, so after one all-gather of the count rows per round every rank runs the same merge
-// and builds the same plan; its own taken rows go to a rank-local array in global merge order (alpha already divided by the
-// running nshot), and one all-gather of those arrays at the end lets every rank place all rows where the single-rank merge put them.
+// ------------------------------------------------------------------------------------------ the shoot driver
+// One driver runs both pvol_preprocess_ranks and pvol_preprocess_blocks.  Rank r shoots only the tasks pvol_partition_tasks deals
+// it.  Every merge decision is a pure function of the round's count table, so after one all-gather of the count rows per round every
+// rank runs the same merge and builds the same plan; its own taken rows go to a rank-local array in global merge order (alpha already
+// divided by the running nshot), and one all-gather of those arrays at the end lets every rank place all rows where the single-rank
+// merge puts them.  pvol_preprocess_blocks is the one-rank case with no communicator: its exchanges are plain copies, shoot_kernel
+// gets no task list, and its rank-local arrays, which hold every task's rows, are the stores.
 extern "C" int pvol_partition_tasks(uint32_t nTasks, uint32_t rank, uint32_t nRanks, uint32_t *outIds, uint32_t capacity, uint32_t *nOut);
-struct PlaceArgs {
-    const float *recv;
-    uint64_t rankStride;
-    uint64_t fieldOff;
-    uint32_t width;
-    const uint32_t *segSrc, *segLocal, *segGlobal;
-    uint32_t nSeg;
-    uint64_t nRows;
-    float *dst;
-};
-extern "C" hipError_t pvol_launch_place_rows(const PlaceArgs *a, hipStream_t stream);
 
 namespace {
-// RCCL is bound at run time, as for pvol_render_frame_ranks: a single-GPU user never loads it
 typedef ncclResult_t (*nccl_allgather_fn)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t);
-nccl_allgather_fn bind_nccl_allgather() {
-    static nccl_allgather_fn fn = 0;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        if (void *sym = dlsym(RTLD_DEFAULT, "ncclAllGather")) { fn = (nccl_allgather_fn)sym; return; }
-        const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-        for (const char *nm : names)
-            if (void *h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL))
-                if (void *sym = dlsym(h, "ncclAllGather")) { fn = (nccl_allgather_fn)sym; break; }
-    });
-    return fn;
-}
 
 // One all-gather: every rank gives `bytes` bytes and receives n_ranks x bytes, rank-major.  Host exchanges (count rows, status,
 // counters) stage through device memory on the RCCL branch; device exchanges (photon rows) stage through host memory on the
-// callback branch only.
+// callback branch only.  With no communicator a host exchange is an untimed copy and no device exchange takes place.
 struct Exchange {
-    const pvol_shoot_comm *comm;
+    const pvol_shoot_comm *comm = 0;   // 0: the single-GPU shoot, rank 0 of 1
     nccl_allgather_fn gather = 0;
-    uint32_t nRanks;
+    uint32_t nRanks = 1;
     void *dStage = 0;
     size_t dStageBytes = 0;
     std::vector<unsigned char> hSend, hRecv;
@@ -460,6 +139,7 @@ struct Exchange {
         return gather(dSend, dRecv, bytes, ncclUint8, (ncclComm_t)comm->nccl_comm, 0) == ncclSuccess && ok(hipStreamSynchronize(0));
     }
     bool host(const void *send, void *recv, size_t bytes) {
+        if (!comm) { memcpy(recv, send, bytes); return true; }
         const auto t0 = std::chrono::steady_clock::now();
         bool good;
         if (gather) {
@@ -507,32 +187,51 @@ struct Plan {
     uint64_t most() const { uint64_t m = 0; for (uint64_t v : localRows) m = std::max(m, v); return m; }
 };
 
-// All-gathers every rank's local rows of one store (fields of `widths` floats; srcs[f] the rank's own field arrays holding
-// `mine` rows) and places them in global order into freshly allocated dst[f] ([plan.rows][width]).  All ranks call it with the
-// same plan, hence the same sizes, and all return the same code unless the exchange itself fails (PVOL_E_NO_DEVICE).
-int gather_store(Exchange &X, const Plan &plan, uint32_t rank, int nFields, const uint32_t *widths, float *const *srcs, float **dst) {
-    for (int f = 0; f < nFields; ++f) dst[f] = 0;
+// One store of the shoot (volume, caustic, direct, indirect or radiance): this rank's rows in global merge order, one array per
+// field (p, wi|wo, alpha; or the radiance record) of `width` floats a row, and the plan of every rank's rows.
+struct Store {
+    int nFields;
+    uint32_t width[3];
+    DevArr f[3];
+    Plan plan;
+    bool reserve(uint32_t rank) {   // room for this rank's rows of the plan, keeping those merged before
+        for (int i = 0; i < nFields; ++i)
+            if (!f[i].resize(width[i] * plan.localRows[rank])) return false;
+        return true;
+    }
+};
+
+// All-gathers every rank's local rows of one store and places them in global order into freshly allocated dst[f]
+// ([plan.rows][width]).  All ranks call it with the same plan, hence the same sizes, and all return the same code unless the
+// exchange itself fails (PVOL_E_NO_DEVICE).  With no communicator the rank's own arrays are the store and move to dst.
+int gather_store(Exchange &X, Store &s, uint32_t rank, float **dst) {
+    if (!X.comm) {
+        for (int f = 0; f < s.nFields; ++f) { dst[f] = s.f[f].d; s.f[f].d = 0; }
+        return PVOL_OK;
+    }
+    for (int f = 0; f < s.nFields; ++f) dst[f] = 0;
+    const Plan &plan = s.plan;
     if (!plan.rows) return PVOL_OK;
     const uint64_t M = plan.most(), mine = plan.localRows[rank];
     uint32_t rowWords = 0;
-    for (int f = 0; f < nFields; ++f) rowWords += widths[f];
+    for (int f = 0; f < s.nFields; ++f) rowWords += s.width[f];
     const size_t sendBytes = sizeof(float) * (size_t)M * rowWords;
     // the plan's bounds, checked before any device index is formed from it
-    for (size_t s = 0; s < plan.src.size(); ++s) {
-        const uint64_t end = s + 1 < plan.src.size() ? plan.global[s + 1] : plan.rows;
-        if (plan.src[s] >= X.nRanks || (uint64_t)plan.local[s] + (end - plan.global[s]) > plan.localRows[plan.src[s]]) return PVOL_E_INVALID;
+    for (size_t i = 0; i < plan.src.size(); ++i) {
+        const uint64_t end = i + 1 < plan.src.size() ? plan.global[i + 1] : plan.rows;
+        if (plan.src[i] >= X.nRanks || (uint64_t)plan.local[i] + (end - plan.global[i]) > plan.localRows[plan.src[i]]) return PVOL_E_INVALID;
     }
     float *send = 0, *recv = 0;
     uint32_t *dSeg = 0;
     const size_t nSeg = plan.src.size();
     int rc = PVOL_OK;
     if (!ok(hipMalloc(&send, sendBytes)) || !ok(hipMalloc(&recv, sendBytes * X.nRanks)) || !ok(hipMalloc(&dSeg, sizeof(uint32_t) * 3 * nSeg))) rc = PVOL_E_NO_MEMORY;
-    for (int f = 0; f < nFields && rc == PVOL_OK; ++f)
-        if (!ok(hipMalloc(&dst[f], sizeof(float) * (size_t)plan.rows * widths[f]))) rc = PVOL_E_NO_MEMORY;
+    for (int f = 0; f < s.nFields && rc == PVOL_OK; ++f)
+        if (!ok(hipMalloc(&dst[f], sizeof(float) * (size_t)plan.rows * s.width[f]))) rc = PVOL_E_NO_MEMORY;
     uint64_t fieldOff = 0;
-    for (int f = 0; f < nFields && rc == PVOL_OK; ++f) {   // the rank's block: field f's M x width floats, then the next field
-        if (mine && !ok(hipMemcpy(send + fieldOff, srcs[f], sizeof(float) * (size_t)mine * widths[f], hipMemcpyDeviceToDevice))) rc = PVOL_E_NO_DEVICE;
-        fieldOff += M * widths[f];
+    for (int f = 0; f < s.nFields && rc == PVOL_OK; ++f) {   // the rank's block: field f's M x width floats, then the next field
+        if (mine && !ok(hipMemcpy(send + fieldOff, s.f[f].d, sizeof(float) * (size_t)mine * s.width[f], hipMemcpyDeviceToDevice))) rc = PVOL_E_NO_DEVICE;
+        fieldOff += M * s.width[f];
     }
     if (rc == PVOL_OK && !(ok(hipMemcpy(dSeg, plan.src.data(), sizeof(uint32_t) * nSeg, hipMemcpyHostToDevice)) &&
                            ok(hipMemcpy(dSeg + nSeg, plan.local.data(), sizeof(uint32_t) * nSeg, hipMemcpyHostToDevice)) &&
@@ -547,30 +246,20 @@ int gather_store(Exchange &X, const Plan &plan, uint32_t rank, int nFields, cons
     for (uint32_t r = 0; r < X.nRanks && rc == PVOL_OK; ++r) rc = (int)(int32_t)all[r];
     if (rc == PVOL_OK && !X.device(send, recv, sendBytes)) rc = PVOL_E_NO_DEVICE;
     fieldOff = 0;
-    for (int f = 0; f < nFields && rc == PVOL_OK; ++f) {
+    for (int f = 0; f < s.nFields && rc == PVOL_OK; ++f) {
         PlaceArgs P;
-        P.recv = recv; P.rankStride = M * rowWords; P.fieldOff = fieldOff; P.width = widths[f];
+        P.recv = recv; P.rankStride = M * rowWords; P.fieldOff = fieldOff; P.width = s.width[f];
         P.segSrc = dSeg; P.segLocal = dSeg + nSeg; P.segGlobal = dSeg + 2 * nSeg; P.nSeg = (uint32_t)nSeg; P.nRows = plan.rows; P.dst = dst[f];
         if (!ok(pvol_launch_place_rows(&P, 0))) rc = PVOL_E_NO_DEVICE;
-        fieldOff += M * widths[f];
+        fieldOff += M * s.width[f];
     }
     if (rc == PVOL_OK && !ok(hipDeviceSynchronize())) rc = PVOL_E_NO_DEVICE;
     hipFree(send); hipFree(recv); hipFree(dSeg);
-    if (rc != PVOL_OK) for (int f = 0; f < nFields; ++f) { hipFree(dst[f]); dst[f] = 0; }
+    if (rc != PVOL_OK) for (int f = 0; f < s.nFields; ++f) { hipFree(dst[f]); dst[f] = 0; }
     return rc;
 }
-}  // namespace
 
-extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, uint32_t n_ranks,
-                                     const pvol_shoot_comm *comm) {
-    // argument checks first: none of them touches the context or the device
-    if (!c || n_tasks == 0 || n_tasks > 65536 || block_paths == 0 || block_paths > 4096 || n_ranks == 0 || rank >= n_ranks || !comm)
-        return PVOL_E_INVALID;
-    if ((comm->nccl_comm != 0) == (comm->allgather != 0)) return PVOL_E_INVALID;   // exactly one of the two
-    if (!c->haveScene) return PVOL_E_NO_SCENE;
-    Exchange X;
-    X.comm = comm; X.nRanks = n_ranks;
-    if (comm->nccl_comm && !(X.gather = bind_nccl_allgather())) return PVOL_E_NO_DEVICE;   // no RCCL in reach
+int shoot(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, Exchange &X) {
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
     hipDeviceSynchronize();
@@ -586,9 +275,9 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
     if (rc != PVOL_OK) return rc;
 
     const auto tShoot0 = std::chrono::steady_clock::now();
-    const uint32_t T = n_tasks, R = n_ranks;
+    const uint32_t T = n_tasks, R = X.nRanks;
     const uint32_t blockSize = block_paths;
-    const uint32_t giveUpShot = 4096;
+    const uint32_t giveUpShot = 4096;   // the reference's constant in its give-up test (photonshooter.cpp:283-290), whatever the block
     const size_t SW = pvol_shoot_state_words();
     const bool keep = c->params.keep_surface_photons != 0;
     uint32_t L = 0;   // this rank's tasks: ids[i] = rank + i * R lives in slot i
@@ -597,12 +286,16 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
     pvol_partition_tasks(T, rank, R, ids.data(), L, &L);
     const uint32_t Lpad = (T + R - 1) / R;   // rank 0's share, the largest
     const uint32_t Ls = std::max<uint32_t>(L, 1);
+    // Room for one block of one task.  Spectral splitting stores up to ~3 photons per path (SURVEY 6) but the usual yield is
+    // ~10 photons per 4096-path block, so the pools start small (L x 256 x 144 B) and a round in which some task outgrew
+    // one is REDONE with a larger pool from the saved RNG states (the round is a pure function of them): nothing is dropped
+    // and nothing is sized for the worst case.
     uint32_t capMax = (uint32_t)std::min<size_t>(65536, std::max<size_t>(256, ((size_t)48 << 30) / ((size_t)Ls * 144)));
-    // PVOL_SHOOT_RANK_CAP_MAX lowers this rank's largest block pool: a test sets it on one rank to make that rank alone fail
+    // PVOL_SHOOT_RANK_CAP_MAX lowers this rank's largest block pool, on a single GPU too: a test sets it on one rank to make that
+    // rank alone fail
     if (const char *e = getenv("PVOL_SHOOT_RANK_CAP_MAX")) { const long v = atol(e); if (v > 0) capMax = std::min<uint32_t>(capMax, (uint32_t)v); }
     uint32_t cap = std::min<uint32_t>(256, capMax), capS = keep ? std::min<uint32_t>(256, capMax) : 1, capR = keep ? 64 : 1;
     Buffers B;
-    uint32_t *dIds = 0;
     int localRc = PVOL_OK;   // this rank's own error, reported to all at the next exchange
     bool good = ok(hipMalloc(&B.stateA, sizeof(uint32_t) * SW * (size_t)Ls)) && ok(hipMalloc(&B.stateB, sizeof(uint32_t) * SW * (size_t)Ls)) &&
                 ok(hipMalloc(&B.halton, sizeof(uint32_t) * 48 * (size_t)Ls)) && ok(hipMalloc(&B.flags, sizeof(uint32_t) * Ls)) &&
@@ -611,7 +304,7 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
                 ok(hipMalloc(&B.localSurf, sizeof(float) * 36 * (size_t)capS * Ls)) && ok(hipMalloc(&B.localSurfKind, sizeof(uint32_t) * (size_t)capS * Ls)) &&
                 ok(hipMalloc(&B.localRad, sizeof(float) * 8 * (size_t)capR * Ls)) &&
                 ok(hipMalloc(&B.seg, sizeof(uint32_t) * 11 * (size_t)Ls)) && ok(hipMalloc(&B.segNshot, sizeof(float) * Ls)) &&
-                ok(hipMalloc(&dIds, sizeof(uint32_t) * Ls)) && ok(hipMemset(B.stats, 0, sizeof(unsigned long long) * 8));
+                (!X.comm || ok(hipMalloc(&B.taskIds, sizeof(uint32_t) * Ls))) && ok(hipMemset(B.stats, 0, sizeof(unsigned long long) * 8));
     if (!good) localRc = PVOL_E_NO_MEMORY;
 
     ShootArgs A;
@@ -620,26 +313,24 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
     A.localSurf = B.localSurf; A.localSurfKind = B.localSurfKind; A.capS = capS; A.localRad = B.localRad; A.capR = capR; A.keepSurface = keep ? 1 : 0;
     A.gridVolume = c->hs.volKind == PVOL_VOLUME_GRID ? 1 : 0;
     A.blockPaths = blockSize;
-    A.taskIds = dIds;
-    if (localRc == PVOL_OK && L && !(ok(hipMemcpy(dIds, ids.data(), sizeof(uint32_t) * L, hipMemcpyHostToDevice)) &&
+    A.taskIds = B.taskIds;   // null with no communicator: slot == task
+    if (localRc == PVOL_OK && L && !((!X.comm || ok(hipMemcpy(B.taskIds, ids.data(), sizeof(uint32_t) * L, hipMemcpyHostToDevice))) &&
                                      ok(pvol_launch_shoot(&A, 0)) && ok(hipDeviceSynchronize())))
         localRc = PVOL_E_NO_DEVICE;
     A.init = 0;
     A.stateOut = B.stateB;
 
     const pvol_params &P = c->params;
-    std::vector<uint32_t> flags(T), counts(8 * (size_t)T), localFlags(Ls), localCounts(8 * (size_t)Ls);
-    // exchanged per round: a status word, then the count rows of the rank's slots, padded to Lpad rows
+    std::vector<uint32_t> flags(T), localFlags(Ls);
+    // exchanged per round: a status word, then the count rows of the rank's slots (read there from the device), padded to Lpad rows
     const size_t rowWords = 1 + 8 * (size_t)Lpad;
     std::vector<uint32_t> sendRow(rowWords), table(rowWords * R);
+    uint32_t *const localCounts = &sendRow[1];
     // this rank's own appends of a round: volume {slot, count, local offset} and surface {slot, nSurf, take, off[4], nRad}
     std::vector<uint32_t> vTask, vCount, vOff, sTask, sN, sTake, sOff, sRad;
     std::vector<float> vNshot;
-    // the plans of the five stores (volume, caustic, direct, indirect, radiance), and the round's additions to them
-    Plan plan[5];
-    for (Plan &pl : plan) pl.reset(R);
-    std::vector<uint32_t> rdSrc[5], rdN[5];
-    DevArr lp, lwi, lalpha, lsp[3], lswo[3], lsalpha[3], lrad;   // this rank's rows, in global merge order
+    Store S[5] = {{3, {3, 3, 30}}, {3, {3, 3, 30}}, {3, {3, 3, 30}}, {3, {3, 3, 30}}, {1, {8}}};   // volume, caustic, direct, indirect, radiance
+    for (Store &s : S) s.plan.reset(R);
     unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     flags.assign(T, (P.n_caustic_photons == 0 ? 1u : 0u) | (P.n_indirect_photons == 0 ? 2u : 0u) | (P.n_volume_photons == 0 ? 4u : 0u));
     uint32_t nshot = 0;
@@ -662,12 +353,12 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
         for (uint32_t i = 0; i < L; ++i) localFlags[i] = flags[ids[i]];
         if (localRc == PVOL_OK && L && !ok(hipMemcpy(B.flags, localFlags.data(), sizeof(uint32_t) * L, hipMemcpyHostToDevice))) localRc = PVOL_E_NO_DEVICE;
         bool redo = false;
-        do {   // the rank's own round, redone locally from the same states if one of its blocks outgrew a pool
+        do {   // the rank's own round: one block per live task, redone from the same states if one of its blocks outgrew a pool
             redo = false;
             if (localRc != PVOL_OK || !L) break;
             unsigned long long rs[8];
             if (!ok(hipMemset(B.stats, 0, sizeof(rs))) || !ok(pvol_launch_shoot(&A, 0)) ||
-                !ok(hipMemcpy(localCounts.data(), B.localCounts, sizeof(uint32_t) * 8 * (size_t)L, hipMemcpyDeviceToHost)) ||
+                !ok(hipMemcpy(localCounts, B.localCounts, sizeof(uint32_t) * 8 * (size_t)L, hipMemcpyDeviceToHost)) ||
                 !ok(hipMemcpy(rs, B.stats, sizeof(rs), hipMemcpyDeviceToHost))) { localRc = PVOL_E_NO_DEVICE; break; }
             uint32_t most = 0, mostS = 0, mostR = 0;
             for (uint32_t i = 0; i < L; ++i) {
@@ -701,38 +392,31 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
             }
             if (!redo) for (int i = 0; i < 8; ++i) st[i] += rs[i];
         } while (redo);
-        if (localRc == PVOL_OK && L) { const uint32_t *tmp = A.stateIn; A.stateIn = A.stateOut; A.stateOut = const_cast<uint32_t *>(tmp); }
+        if (localRc == PVOL_OK && L) { const uint32_t *tmp = A.stateIn; A.stateIn = A.stateOut; A.stateOut = const_cast<uint32_t *>(tmp); }   // the round stands
         // the count exchange: every rank learns the round's whole table and whether any rank failed
-        std::fill(sendRow.begin(), sendRow.end(), 0u);
         sendRow[0] = (uint32_t)localRc;
-        if (localRc == PVOL_OK) std::copy(localCounts.begin(), localCounts.begin() + 8 * (size_t)L, sendRow.begin() + 1);
         if (!X.host(sendRow.data(), table.data(), sizeof(uint32_t) * rowWords)) { rc = PVOL_E_NO_DEVICE; break; }
         if (const int e = agreed(table.data(), rowWords)) { rc = e; break; }
-        for (uint32_t t = 0; t < T; ++t)   // task t sits in slot t / R of rank t % R
-            memcpy(&counts[8 * (size_t)t], &table[(t % R) * rowWords + 1 + 8 * (size_t)(t / R)], 8 * sizeof(uint32_t));
-        // merge in task order (photonshooter.cpp:280-351): the rule of pvol_preprocess_blocks, on the gathered table
+        // merge in task order (photonshooter.cpp:280-351), on the whole round's table: every rank takes the same decisions
         vTask.clear(); vCount.clear(); vOff.clear(); vNshot.clear();
         sTask.clear(); sN.clear(); sTake.clear(); sOff.clear(); sRad.clear();
-        for (int k = 0; k < 5; ++k) { rdSrc[k].clear(); rdN[k].clear(); }
         const size_t volBefore = nVolume;
-        const uint64_t surfBefore[4] = {nCaustic, nDirect, nIndirect, nRadTotal};
-        const uint64_t mineBefore[5] = {plan[0].localRows[rank], plan[1].localRows[rank], plan[2].localRows[rank], plan[3].localRows[rank], plan[4].localRows[rank]};
-        uint64_t mine[5] = {mineBefore[0], mineBefore[1], mineBefore[2], mineBefore[3], mineBefore[4]};
+        const uint64_t causticBefore = nCaustic, indirectBefore = nIndirect;
         for (uint32_t t = 0; t < T; ++t) {
             uint32_t &fl = flags[t];
             if (fl & 8u) continue;
             if (abortTasks) { fl |= 8u; continue; }
             if (nshot > 500000 && (unsuccessful(P.n_caustic_photons, nCaustic, giveUpShot) || unsuccessful(P.n_indirect_photons, nIndirect, giveUpShot) ||
                                    unsuccessful(P.n_volume_photons, nVolume, giveUpShot))) {
-                nVolume = 0; nCaustic = nIndirect = 0; nRadTotal = 0;   // photonshooter.cpp:292-298
+                nVolume = 0; nCaustic = nIndirect = 0; nRadTotal = 0;   // photonshooter.cpp:292-298 erases caustic, indirect, volume, radiance
                 abortTasks = true;
                 fl |= 8u;
                 rc = PVOL_E_SHOOT_FAILED;
                 continue;
             }
             nshot += blockSize;
-            const uint32_t *lc = &counts[8 * (size_t)t];
-            const uint32_t owner = t % R, slot = t / R;
+            const uint32_t owner = t % R, slot = t / R;   // task t sits in slot t / R of rank t % R
+            const uint32_t *lc = &table[owner * rowWords + 1 + 8 * (size_t)slot];
             uint32_t take = 0;
             if (!(fl & 2u)) {
                 take |= 2u | 4u;
@@ -752,31 +436,29 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
                 const uint32_t n[4] = {(take & 1u) ? lc[1] : 0u, (take & 2u) ? lc[2] : 0u, (take & 4u) ? lc[3] : 0u, lc[5]};
                 if (owner == rank) {
                     sTask.push_back(slot); sN.push_back(lc[4]); sTake.push_back(take); sRad.push_back(lc[5]);
-                    for (int k = 0; k < 4; ++k) { sOff.push_back((uint32_t)mine[1 + k]); mine[1 + k] += n[k]; }
+                    for (int k = 0; k < 4; ++k) sOff.push_back((uint32_t)S[1 + k].plan.localRows[rank]);
                 }
-                for (int k = 0; k < 4; ++k) if (n[k]) { rdSrc[1 + k].push_back(owner); rdN[1 + k].push_back(n[k]); }
+                for (int k = 0; k < 4; ++k) S[1 + k].plan.add(owner, n[k]);
             }
             nRadTotal += keep ? lc[5] : 0;
             if (!(fl & 4u)) {
                 if (lc[0]) {
-                    if (owner == rank) { vTask.push_back(slot); vCount.push_back(lc[0]); vOff.push_back((uint32_t)mine[0]); vNshot.push_back(float(nshot)); mine[0] += lc[0]; }
-                    rdSrc[0].push_back(owner); rdN[0].push_back(lc[0]);
+                    if (owner == rank) { vTask.push_back(slot); vCount.push_back(lc[0]); vOff.push_back((uint32_t)S[0].plan.localRows[rank]); vNshot.push_back(float(nshot)); }
+                    S[0].plan.add(owner, lc[0]);
                     nVolume += lc[0];
                 }
                 if (nVolume >= P.n_volume_photons) fl |= 4u;
             }
             if ((fl & 7u) == 7u) fl |= 8u;
         }
-        if (abortTasks) continue;   // the stores are erased; the next pass of the loop finds every task finished
-        for (int k = 0; k < 5; ++k)
-            for (size_t s = 0; s < rdSrc[k].size(); ++s) plan[k].add(rdSrc[k][s], rdN[k][s]);
+        if (abortTasks) continue;   // the stores are erased (their plans are never used); the next pass finds every task finished
         if (localRc == PVOL_OK && !vTask.empty()) {   // this rank's taken volume rows, alpha / running nshot (pvol_launch_merge)
-            if (!lp.need(3 * mineBefore[0], 3 * mine[0]) || !lwi.need(3 * mineBefore[0], 3 * mine[0]) || !lalpha.need(30 * mineBefore[0], 30 * mine[0])) localRc = PVOL_E_NO_MEMORY;
+            if (!S[0].reserve(rank)) localRc = PVOL_E_NO_MEMORY;
             else {
                 MergeArgs M;
                 const size_t n = vTask.size();
                 M.localPhotons = B.localPhotons; M.cap = cap; M.srcTask = B.seg; M.count = B.seg + Ls; M.dstOff = B.seg + 2 * (size_t)Ls; M.nshot = B.segNshot;
-                M.nSeg = (uint32_t)n; M.p = lp.d; M.wi = lwi.d; M.alpha = lalpha.d;
+                M.nSeg = (uint32_t)n; M.p = S[0].f[0].d; M.wi = S[0].f[1].d; M.alpha = S[0].f[2].d;
                 if (!(ok(hipMemcpy(B.seg, vTask.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
                       ok(hipMemcpy(B.seg + Ls, vCount.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
                       ok(hipMemcpy(B.seg + 2 * (size_t)Ls, vOff.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
@@ -787,10 +469,7 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
         }
         if (localRc == PVOL_OK && keep && !sTask.empty()) {   // ... and its surface records and radiance photons (pvol_launch_merge_surface)
             bool g3 = true;
-            for (int k = 0; k < 3 && g3; ++k)
-                g3 = lsp[k].need(3 * mineBefore[1 + k], 3 * mine[1 + k]) && lswo[k].need(3 * mineBefore[1 + k], 3 * mine[1 + k]) &&
-                     lsalpha[k].need(30 * mineBefore[1 + k], 30 * mine[1 + k]);
-            g3 = g3 && lrad.need(8 * mineBefore[4], 8 * mine[4]);
+            for (int k = 1; k < 5 && g3; ++k) g3 = S[k].reserve(rank);
             if (!g3) localRc = PVOL_E_NO_MEMORY;
             else {
                 SurfMergeArgs M;
@@ -799,8 +478,8 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
                 M.localSurf = B.localSurf; M.localSurfKind = B.localSurfKind; M.capS = capS; M.localRad = B.localRad; M.capR = capR;
                 M.srcTask = d; M.nSurf = d + Ls; M.take = d + 2 * (size_t)Ls; M.nRad = d + 3 * (size_t)Ls; M.dstOff = d + 4 * (size_t)Ls;
                 M.nSeg = (uint32_t)n;
-                for (int k = 0; k < 3; ++k) { M.p[k] = lsp[k].d; M.wo[k] = lswo[k].d; M.alpha[k] = lsalpha[k].d; }
-                M.rad = lrad.d;
+                for (int k = 0; k < 3; ++k) { M.p[k] = S[1 + k].f[0].d; M.wo[k] = S[1 + k].f[1].d; M.alpha[k] = S[1 + k].f[2].d; }
+                M.rad = S[4].f[0].d;
                 if (!(ok(hipMemcpy(d, sTask.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
                       ok(hipMemcpy(d + Ls, sN.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
                       ok(hipMemcpy(d + 2 * (size_t)Ls, sTake.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) &&
@@ -810,8 +489,11 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
                     localRc = PVOL_E_NO_DEVICE;
             }
         }
-        // the 256-round stall exit of pvol_preprocess_blocks, decided on the same global counts
-        const bool progress = nCaustic != surfBefore[0] || nIndirect != surfBefore[2] || nVolume != volBefore;
+        // The reference has no exit for a store that stops growing after a good start (its `unsuccessful` test, photonshooter.cpp:37-39,
+        // passes once found >= 4): e.g. a matte scene whose "caustic" photons all come through the medium, after the volume map is
+        // full -- it would shoot forever.  Here 256 rounds in a row without a single photon for any store still wanted end the
+        // pass the way the reference's own abort does (stores erased, PVOL_E_SHOOT_FAILED), decided on the global counts.
+        const bool progress = nCaustic != causticBefore || nIndirect != indirectBefore || nVolume != volBefore;
         stallRounds = progress ? 0u : stallRounds + 1u;
         if (stallRounds >= 256u) {
             nVolume = 0; nCaustic = nIndirect = 0; nRadTotal = 0;
@@ -838,44 +520,40 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
     c->shootStats[0] = st[0]; c->shootStats[1] = st[1]; c->shootStats[2] = st[2]; c->shootStats[3] = st[3]; c->shootStats[4] = st[4];
     c->shootStats[5] = st[5]; c->shootStats[6] = nVolume; c->shootStats[7] = nCaustic; c->shootStats[8] = nDirect; c->shootStats[9] = nIndirect;
     c->shootStats[10] = st[6]; c->shootStats[11] = nshot;
-    if (rc == PVOL_OK && st[7] != 0) rc = PVOL_E_LIMIT;   // a frame stack overflowed on some rank: the summed counter says so to all
-    B.release(false);
-    hipFree(dIds);
-    // the row exchanges: every rank's rows of every store, placed in global merge order
+    if (rc == PVOL_OK && st[7] != 0) rc = PVOL_E_LIMIT;   // a frame stack overflowed on some rank: never silently drop photons
+    B.release();
+    // the stores: every rank's rows placed in global merge order; the surface stores go to the context whatever happens to the volume map
     if (rc == PVOL_OK && keep) {
         const uint64_t cnt[3] = {nCaustic, nDirect, nIndirect};
         const uint32_t paths[3] = {nCausticPaths, nDirectPaths, nIndirectPaths};
-        const uint32_t w[3] = {3, 3, 30};
         for (int k = 0; k < 3 && rc == PVOL_OK; ++k) {
-            float *srcs[3] = {lsp[k].d, lswo[k].d, lsalpha[k].d}, *dst[3];
-            rc = gather_store(X, plan[1 + k], rank, 3, w, srcs, dst);
-            if (rc == PVOL_OK && plan[1 + k].rows != cnt[k]) rc = PVOL_E_INVALID;
+            float *dst[3];
+            rc = gather_store(X, S[1 + k], rank, dst);
+            if (rc == PVOL_OK && S[1 + k].plan.rows != cnt[k]) rc = PVOL_E_INVALID;
             c->surf[k].p = dst[0]; c->surf[k].wo = dst[1]; c->surf[k].alpha = dst[2];
             c->surf[k].n = (uint32_t)cnt[k]; c->surf[k].nPaths = paths[k];
         }
-        const uint32_t w8 = 8;
-        float *srcR = lrad.d, *dstR = 0;
-        if (rc == PVOL_OK) rc = gather_store(X, plan[4], rank, 1, &w8, &srcR, &dstR);
-        if (rc == PVOL_OK && plan[4].rows != nRadTotal) rc = PVOL_E_INVALID;
+        float *dstR = 0;
+        if (rc == PVOL_OK) rc = gather_store(X, S[4], rank, &dstR);
+        if (rc == PVOL_OK && S[4].plan.rows != nRadTotal) rc = PVOL_E_INVALID;
         c->dRad = dstR; c->nRad = (uint32_t)nRadTotal;
         c->surfKept = true;
         if (rc != PVOL_OK) pvol_free_surface_stores(c);
     }
     float *raw[3] = {0, 0, 0};
     if (rc == PVOL_OK && nVolume) {
-        const uint32_t w[3] = {3, 3, 30};
-        float *srcs[3] = {lp.d, lwi.d, lalpha.d};
-        rc = gather_store(X, plan[0], rank, 3, w, srcs, raw);
-        if (rc == PVOL_OK && plan[0].rows != nVolume) rc = PVOL_E_INVALID;
+        rc = gather_store(X, S[0], rank, raw);
+        if (rc == PVOL_OK && S[0].plan.rows != nVolume) rc = PVOL_E_INVALID;
     }
-    hipFree(lp.d); hipFree(lwi.d); hipFree(lalpha.d); hipFree(lrad.d);
-    for (int k = 0; k < 3; ++k) { hipFree(lsp[k].d); hipFree(lswo[k].d); hipFree(lsalpha[k].d); }
+    for (Store &s : S)
+        for (DevArr &a : s.f) hipFree(a.d);
     c->prepSeconds[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - tShoot0).count();
     c->exchangeSeconds = X.seconds;
     if (rc != PVOL_OK || nVolume == 0) {
         for (float *a : raw) hipFree(a);
         return rc;
     }
+    // hand the merged arrays to the context and build the search structure
     std::vector<float> hostP(3 * nVolume);
     if (!ok(hipMemcpy(hostP.data(), raw[0], sizeof(float) * 3 * nVolume, hipMemcpyDeviceToHost))) { for (float *a : raw) hipFree(a); return PVOL_E_NO_DEVICE; }
     c->dRawP = raw[0]; c->dRawWi = raw[1]; c->dRawAlpha = raw[2];
@@ -884,6 +562,29 @@ extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t blo
     hipDeviceSynchronize();
     c->prepSeconds[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - tBuild0).count();
     return rc;
+}
+}  // namespace
+
+extern "C" int pvol_preprocess(pvol_ctx *c, uint32_t n_tasks) { return pvol_preprocess_blocks(c, n_tasks, 4096); }
+
+extern "C" int pvol_preprocess_blocks(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths) {
+    if (!c || n_tasks == 0 || n_tasks > 65536 || block_paths == 0 || block_paths > 4096) return PVOL_E_INVALID;
+    if (!c->haveScene) return PVOL_E_NO_SCENE;
+    Exchange X;   // no communicator: rank 0 of 1
+    return shoot(c, n_tasks, block_paths, 0, X);
+}
+
+extern "C" int pvol_preprocess_ranks(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, uint32_t n_ranks,
+                                     const pvol_shoot_comm *comm) {
+    // argument checks first: none of them touches the context or the device
+    if (!c || n_tasks == 0 || n_tasks > 65536 || block_paths == 0 || block_paths > 4096 || n_ranks == 0 || rank >= n_ranks || !comm)
+        return PVOL_E_INVALID;
+    if ((comm->nccl_comm != 0) == (comm->allgather != 0)) return PVOL_E_INVALID;   // exactly one of the two
+    if (!c->haveScene) return PVOL_E_NO_SCENE;
+    Exchange X;
+    X.comm = comm; X.nRanks = n_ranks;
+    if (comm->nccl_comm && !(X.gather = (nccl_allgather_fn)pvol_rccl_symbol("ncclAllGather"))) return PVOL_E_NO_DEVICE;   // no RCCL in reach
+    return shoot(c, n_tasks, block_paths, rank, X);
 }
 
 extern "C" int pvol_get_exchange_seconds(pvol_ctx *c, double *out) {

@@ -6,10 +6,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include <dlfcn.h>
-#include <rccl/rccl.h>   // types and enums only: the library is bound at run time (pvol_render_frame_ranks)
+#include <rccl/rccl.h>   // types and enums only: the library is bound at run time (pvol_rccl_symbol)
 
 #include "pvol_host.h"
 #include "pvol_math.h"
@@ -363,20 +364,19 @@ extern "C" int pvol_partition_tasks(uint32_t nTasks, uint32_t rank, uint32_t nRa
 }
 
 // RCCL is bound at run time: a process that already holds a copy (the application's own, or the one PyTorch ships) keeps using
-// that one, and a single-GPU user of this library never loads it.
-typedef ncclResult_t (*nccl_reduce_fn)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, int, ncclComm_t, hipStream_t);
-static nccl_reduce_fn bind_nccl_reduce() {
-    static nccl_reduce_fn fn = 0;
-    static bool tried = false;
-    if (tried) return fn;
-    tried = true;
-    if (void *sym = dlsym(RTLD_DEFAULT, "ncclReduce")) { fn = (nccl_reduce_fn)sym; return fn; }
-    const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    for (const char *nm : names)
-        if (void *h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL))
-            if (void *sym = dlsym(h, "ncclReduce")) { fn = (nccl_reduce_fn)sym; break; }
-    return fn;
+// that one, and a single-GPU user of this library never loads it.  0 when no RCCL is in reach.
+extern "C" void *pvol_rccl_symbol(const char *name) {
+    if (void *sym = dlsym(RTLD_DEFAULT, name)) return sym;
+    static void *lib = 0;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+        for (const char *nm : names)
+            if ((lib = dlopen(nm, RTLD_NOW | RTLD_GLOBAL))) break;
+    });
+    return lib ? dlsym(lib, name) : 0;
 }
+typedef ncclResult_t (*nccl_reduce_fn)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, int, ncclComm_t, hipStream_t);
 
 // One rank of an N-GPU frame: its share of the render tasks into its own full-frame film, ONE ncclReduce(sum) of the film to rank 0
 // (the Gaussian filter splats across tile borders, film/image.cpp:82-134, so tiles cannot simply be gathered), resolve on rank 0.
@@ -387,7 +387,7 @@ extern "C" int pvol_render_frame_ranks(pvol_ctx *c, const pvol_camera *camera, c
     if (!c || !smp || !film_ok(film) || !dPixels || !nRanks || rank >= nRanks) return PVOL_E_INVALID;
     if (nRanks > 1 && !ncclComm) return PVOL_E_INVALID;
     nccl_reduce_fn reduce = 0;
-    if (nRanks > 1 && !(reduce = bind_nccl_reduce())) return PVOL_E_NO_DEVICE;   // no RCCL in reach
+    if (nRanks > 1 && !(reduce = (nccl_reduce_fn)pvol_rccl_symbol("ncclReduce"))) return PVOL_E_NO_DEVICE;   // no RCCL in reach
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
     hipStream_t stream = (hipStream_t)hipStream;
     uint32_t n = 0;

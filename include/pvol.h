@@ -333,7 +333,8 @@ int pvol_preprocess_ranks(pvol_ctx *ctx, uint32_t n_tasks, uint32_t block_paths,
                           const pvol_shoot_comm *comm);
 
 /* Seconds the last pvol_preprocess_ranks spent in its all-gathers, host staging included (part of the shooting time that
- * pvol_get_preprocess_seconds reports in out[0]). */
+ * pvol_get_preprocess_seconds reports in out[0]).  0.0 after a single-rank shoot (pvol_preprocess, pvol_preprocess_blocks),
+ * which exchanges nothing. */
 int pvol_get_exchange_seconds(pvol_ctx *ctx, double *out);
 
 /* Work counters of the last pvol_preprocess (the figures SURVEY 6 reports for the reference shooter):
