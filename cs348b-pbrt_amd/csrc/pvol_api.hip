@@ -84,6 +84,8 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     { const char *tw = getenv("PVOL_TILE_WAVES"); c->tileWaves = tw ? std::max(0, atoi(tw)) : 0; }
     // li_fixup_kernel / li_fixup_group_kernel waves per CU (C3, 8 spp frame: 16.3 s at 8, 13.9 s at 16)
     { const char *fw = getenv("PVOL_FIX_WAVES"); c->fixWavesPerCU = fw ? std::max(1, atoi(fw)) : 16; }
+    // PVOL_LI_COALESCE=<max_batch>: the default of pvol_set_li_coalescing, for callers that cannot call it (an unchanged binding)
+    { const char *lc = getenv("PVOL_LI_COALESCE"); const long v = lc ? atol(lc) : 0; c->coMaxBatch = (v > 1 && v <= PVOL_LI_MAX_BATCH) ? (uint32_t)v : 0u; }
     { hipDeviceProp_t prop; if (ok(hipGetDeviceProperties(&prop, params->device))) c->nCU = prop.multiProcessorCount; }
     c->statsOn = false;
     c->timeMs = 0; c->launches = 0;
@@ -134,6 +136,7 @@ void pvol_destroy(pvol_ctx *c) {
     if (c->dSegCounter) hipFree(c->dSegCounter);
     if (c->dSegStream) hipFree(c->dSegStream);
     if (c->dSpecLink) hipFree(c->dSpecLink);
+    pvol_free_li_staging(c);
     for (auto &p : c->pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     for (auto &p : c->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     for (auto &p : c->phaseMarks) hipEventDestroy(p.second);
@@ -690,6 +693,16 @@ static bool harvest_events(pvol_ctx *c, bool wait) {
     return true;
 }
 
+// Orders `stream` behind every batch of this context still running on another stream (their end events): the device entry
+// points return with their kernels in flight, and those kernels use the context's scratch (dWords, dRecords, dState, dDefer).
+int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream) {
+    std::lock_guard<std::mutex> g(c->mu);
+    harvest_events(c, false);
+    for (const auto &p : c->pending)
+        if (!ok(hipStreamWaitEvent(stream, p.second, 0))) return PVOL_E_NO_DEVICE;
+    return PVOL_OK;
+}
+
 // Phase timing (off by default: two events per kernel group otherwise).  A mark is an event on the launch stream.
 void pvol_phase_mark(pvol_ctx *c, hipStream_t stream, int id) {
     if (!c->phaseOn) return;
@@ -759,7 +772,7 @@ static int spec_finish(pvol_ctx *c, const LiArgs &a, size_t cap, bool replay, ui
     LiArgs sa = a;
     sa.rays = c->dSegRays; sa.nRays = (uint32_t)cap; sa.streams = c->dSegStream; sa.nStreams = 1; sa.outputKind = PVOL_OUT_SPECTRAL;
     sa.out = c->dSegOut; sa.draws = 0; sa.initState = 0; sa.finalState = 0; sa.tauOut = 0; sa.defer = 0; sa.deferCount = 0; sa.deferCap = 0; sa.gated = 0;
-    sa.records = c->dSegRecords; sa.sliceM = (uint32_t)cap; sa.sliceK = 0; sa.state = 0;
+    sa.records = c->dSegRecords; sa.sliceM = (uint32_t)cap; sa.sliceK = 0; sa.state = 0; sa.status = 0;
     const uint32_t nWaves = (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 16ull);
     if (!ok(hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), stream))) return PVOL_E_NO_DEVICE;
     hipError_t e = replay ? pvol_launch_li_replay(&sa, lds_bytes_par(c), c->hs.candCap, nWaves, stream)
@@ -792,6 +805,7 @@ int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_s
     a.transmittanceOnly = transOnly;
     a.chunkCounter = c->dWords; a.needSeq = c->dWords + 1; a.gated = 0;
     a.tauOut = c->dTauNext;   // render driver with the surface integrator on: the march kernels also report every sample's *T
+    a.status = c->dStatusNext;   // coalesced per-sample batch: a PVOL_E_LIMIT fails only its own call
     // li_group_kernel bucket radius^2 = this x the guessed k-th distance^2 (measured at 64 spp: 1.3 55.5, 1.2 57.5, 1.12 58.0,
     // 1.06 56.6, 1.0 51.0 Msamples/s)
     { const char *gs = getenv("PVOL_GROUP_GUESS"); a.grpGuess = gs ? (float)atof(gs) : 1.15f; if (!(a.grpGuess >= 1.f)) a.grpGuess = 1.15f; }
@@ -1080,6 +1094,12 @@ int pvol_transmittance_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, 
 int pvol_li(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T) {
     if (!c || !ray || !mt || !mti || !Lv || !T) return PVOL_E_INVALID;
     if (*mti < 0 || *mti > 624) return PVOL_E_INVALID;
+    if (c->coMaxBatch.load(std::memory_order_relaxed) > 1) return pvol_li_coalesced(c, ray, mt, mti, Lv, T);   // pvol_li_coalesce.hip
+    return pvol_li_lone(c, ray, mt, mti, Lv, T);
+}
+
+// One call as its own batch of one stream on the null stream: pvol_li with coalescing off.
+int pvol_li_lone(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T) {
     uint32_t state[625];
     memcpy(state, mt, sizeof(uint32_t) * 624);
     state[624] = (uint32_t)*mti;

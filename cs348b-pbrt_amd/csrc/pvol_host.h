@@ -2,6 +2,9 @@
 #ifndef PVOL_HOST_H
 #define PVOL_HOST_H
 #include <hip/hip_runtime.h>
+#include <atomic>
+#include <condition_variable>
+#include <deque>
 #include <mutex>
 #include <vector>
 #include "pvol_dev.h"
@@ -126,7 +129,35 @@ struct pvol_ctx {
     // tile driver work buffers (grown on demand, pvol_tile.hip)
     void *dTile[6] = {0, 0, 0, 0, 0, 0};
     size_t tileBytes[6] = {0, 0, 0, 0, 0, 0};
+    int32_t *dStatusNext = 0;   // set by a coalesced per-sample batch around pvol_launch_batch: per ray PVOL_E_LIMIT (LiArgs::status)
+    // coalesced per-sample calls (pvol_li_coalesce.hip): concurrent pvol_li calls queue here, one of them (the leader) runs
+    // a batch of up to coMaxBatch of them while the others wait; coMu guards the queue, apiMu still guards the batch
+    std::atomic<uint32_t> coMaxBatch{0};   // <= 1: every pvol_li is its own batch (pvol_li_lone)
+    uint32_t coMaxWaitUs = 0;
+    std::mutex coMu;
+    std::condition_variable coDone, coMore;   // a batch finished / a caller joined the queue (an idle leader may wait for it)
+    std::deque<struct LiRequest *> coQueue;
+    bool coBusy = false;                   // a leader is running a batch
+    // calls served by coalesced batches, batches, largest batch, calls that queued behind a batch; then, for every batch of
+    // pvol_li_many and the coalescer: batches redone call by call (gated backup), calls that failed on their own
+    uint64_t coStats[6] = {0, 0, 0, 0, 0, 0};
+    // persistent staging of the batches (pinned host + device, grown to the largest batch) and the context's own stream
+    hipStream_t coStream = 0;
+    unsigned char *coHostIn = 0, *coHostOut = 0, *coDevIn = 0, *coDevOut = 0;
+    uint32_t coCap = 0;
 };
+
+// One per-sample call of a coalesced batch: the caller's buffers, written only when rc ends PVOL_OK.
+struct LiRequest {
+    const pvol_ray *ray;
+    uint32_t *mt;
+    int32_t *mti;
+    float *Lv, *T;
+    int rc;
+    bool done;
+};
+#define PVOL_LI_MAX_BATCH 4096u
+#define PVOL_LI_MAX_WAIT_US 1000u
 
 
 struct pvol_ctx;
@@ -142,6 +173,11 @@ void pvol_free_photons(pvol_ctx *c);
 void pvol_free_surface_stores(pvol_ctx *c);
 void pvol_free_caustic_map(pvol_ctx *c);
 int pvol_push_scene(pvol_ctx *c);
+// pvol_li without the coalescer (pvol_api.hip) and through it (pvol_li_coalesce.hip); arguments already validated
+int pvol_li_lone(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T);
+int pvol_li_coalesced(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T);
+void pvol_free_li_staging(pvol_ctx *c);
+int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream);
 // an RCCL function by name, bound at run time once per process (pvol_tile.hip); 0 when no RCCL is in reach
 void *pvol_rccl_symbol(const char *name);
 }

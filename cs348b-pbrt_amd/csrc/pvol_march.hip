@@ -429,12 +429,21 @@ __device__ __forceinline__ float analytic_tau_length(const DevScene &S, V3 o, V3
     return len(a - b);
 }
 
+// A ray the record / LDS plan cannot hold: the ray's own status where the batch keeps one (a coalesced per-sample batch, whose
+// error then never reaches the context's shared count), else the context's error count.
+__device__ __forceinline__ void report_limit(const LiArgs &A, size_t ri, int lane) {
+    if (lane != 0) return;
+    if (A.status && ri != ~(size_t)0) A.status[ri] = PVOL_E_LIMIT;
+    else atomicAdd(&A.counters->nErrors, 1ull);
+}
+
 // One call of PhotonVolumeIntegrator::Li (or Transmittance).  Returns false only in MODE_PAR when the ray
 // needs a drawn VALUE (Russian roulette): the caller must redo the batch sequentially.
 // `tauRec` (optional): *T as a TauRec (pvol_dev.h); its length is only taken where the caller wants it (A.tauOut).
+// `ri`: the ray's index in the batch, for its entry of A.status.
 template <bool STATS, int MODE, int NREG>
 __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr, Rng &rng, MarchLds &M, int lane,
-                          WaveCounters &wc, f4 *LvOut, f4 *TrOut, RayRec rec, TauRec *tauRec = nullptr) {
+                          WaveCounters &wc, f4 *LvOut, f4 *TrOut, RayRec rec, TauRec *tauRec = nullptr, size_t ri = ~(size_t)0) {
     constexpr bool RNGON = (MODE == MODE_SEQ || MODE == MODE_RESOLVE);
     constexpr bool RADIANCE = (MODE != MODE_RESOLVE);
     const int q = lane & 7;
@@ -462,7 +471,7 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
     int nSamples = hit ? (int)ceilf((t1 - t0) / S.stepSize) : 0;
     if (MODE != MODE_PAR && hit && nSamples > S.maxSteps && (nLights > 1 || MODE >= MODE_RESOLVE)) {
         // the LDS / record plan cannot hold this ray's per-step arrays: report, never guess
-        if (lane == 0) atomicAdd(&A.counters->nErrors, 1ull);
+        report_limit(A, ri, lane);
         hit = false;
         nSamples = 0;
     }
@@ -943,7 +952,7 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
         f4 Lv, Tr;
         RayRec none = {0, 0, 0};
         TauRec tr = {0.f, 1.f};
-        march_ray<STATS, MODE_SEQ, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, none, &tr);
+        march_ray<STATS, MODE_SEQ, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, none, &tr, ri);
         write_outputs(S, A, ri, Lv, Tr, lane);
         if (A.tauOut && lane == 0) A.tauOut[ri] = tr;
         if (A.draws && lane == 0) A.draws[ri] = (uint32_t)(rng.draws - d0);
@@ -1073,7 +1082,7 @@ __global__ __launch_bounds__(LANES, PVOL_WPE) void li_resolve_kernel(LiArgs A) {
         const unsigned long long d0 = rng.draws;
         RayRec rec = ray_rec(A.records + ((size_t)sidx * A.sliceM + (k - begin)) * A.recStride, S.maxSteps, grid);
         f4 Lv, Tr;
-        march_ray<false, MODE_RESOLVE, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec);
+        march_ray<false, MODE_RESOLVE, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec, nullptr, ri);
         if (lane == 0) rec.hdr[2] = (uint32_t)(rng.draws - d0);
         if (A.draws && lane == 0) A.draws[ri] = (uint32_t)(rng.draws - d0);
     }
@@ -1133,7 +1142,7 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
             f4 Lv, Tr;
             TauRec tr = {0.f, 1.f};
             if (march_ray_blocked<STATS, MODE_REPLAY, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec, &tr) == 2)
-                march_ray<STATS, MODE_REPLAY, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec, &tr);
+                march_ray<STATS, MODE_REPLAY, NREG>(S, A, pr, rng, M, lane, wc, &Lv, &Tr, rec, &tr, ri);
             write_outputs(S, A, ri, Lv, Tr, lane);
             if (A.tauOut && lane == 0) A.tauOut[ri] = tr;
         }
@@ -1150,14 +1159,14 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
 // Geometry of one ray's march steps, one step per lane: which lights are unoccluded at every step (bit ln; 0x80 = sigma_s is not
 // black there).  Shared by li_geo_kernel and the tile pre-pass of scenes with several lights (pvol_tile_dev.h).
 __device__ int geo_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr, RayRec rec, int lane, bool grid, bool blackS1,
-                       unsigned int lightBlackMask) {   // returns the ray's march-step count (0: nothing to do)
+                       unsigned int lightBlackMask, size_t ri = ~(size_t)0) {   // returns the ray's march-step count (0: nothing to do)
     RayD ray;
     ray.o = v3(pr.o[0], pr.o[1], pr.o[2]); ray.d = v3(pr.d[0], pr.d[1], pr.d[2]); ray.mint = pr.mint; ray.maxt = pr.maxt;
     float t0, t1;
     bool hit = S.volKind != PVOL_VOLUME_NONE && vol_intersect(S, ray, &t0, &t1) && (t1 - t0) != 0.f;
     int nSamples = hit ? (int)ceilf((t1 - t0) / S.stepSize) : 0;
     if (hit && nSamples > S.maxSteps) {   // the record plan cannot hold this ray: report, never guess
-        if (lane == 0) atomicAdd(&A.counters->nErrors, 1ull);
+        report_limit(A, ri, lane);
         nSamples = 0;
     }
     if (lane == 0) { rec.hdr[0] = (uint32_t)nSamples; rec.hdr[1] = 0u; }
@@ -1233,9 +1242,10 @@ __global__ __launch_bounds__(LANES) void li_geo_kernel(LiArgs A) {
         if (l0 >= sliceLen) continue;
         const uint32_t l1 = min(sliceLen, l0 + CHUNK_RAYS);
         for (uint32_t l = l0; l < l1; ++l) {
-            const pvol_ray pr = A.rays[(size_t)first + begin + l];
+            const size_t ri = (size_t)first + begin + l;
+            const pvol_ray pr = A.rays[ri];
             RayRec rec = ray_rec(A.records + ((size_t)sidx * A.sliceM + l) * A.recStride, S.maxSteps, grid);
-            geo_ray(S, A, pr, rec, lane, grid, blackS1, lightBlackMask);
+            geo_ray(S, A, pr, rec, lane, grid, blackS1, lightBlackMask, ri);
         }
     }
 }

@@ -80,6 +80,9 @@ def lib():
         L.pvol_li_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         L.pvol_li.argtypes = [C.c_void_p, C.c_void_p, _u32p, C.POINTER(C.c_int32), _f32p, _f32p]
+        L.pvol_li_many.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, _u32p, C.POINTER(C.c_int32), _f32p, _f32p, C.POINTER(C.c_int32)]
+        L.pvol_set_li_coalescing.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.pvol_get_li_coalescing_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         L.pvol_transmittance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _f32p]
         L.pvol_get_stats.argtypes = [C.c_void_p, C.POINTER(abi.Stats), C.c_int]
         L.pvol_enable_stats.argtypes = [C.c_void_p, C.c_int]
@@ -123,7 +126,8 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_download_surface_photons", "pvol_radiance_photon_count", "pvol_download_radiance_photons",
            "pvol_set_surface_integrator", "pvol_enable_phase_timing", "pvol_get_phase_ms",
            "pvol_partition_tasks", "pvol_render_frame_ranks", "pvol_preprocess_blocks",
-           "pvol_preprocess_ranks", "pvol_get_exchange_seconds"]
+           "pvol_preprocess_ranks", "pvol_get_exchange_seconds", "pvol_li_many", "pvol_set_li_coalescing",
+           "pvol_get_li_coalescing_stats"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -351,6 +355,33 @@ class PhotonVolume:
         _check(lib().pvol_li(self._h, ray.ctypes.data, mt.ctypes.data_as(_u32p), C.byref(i), Lv.ctypes.data_as(_f32p), T.ctypes.data_as(_f32p)),
                "pvol_li")
         return Lv, T, i.value
+
+    def li_many(self, rays, mt, mti):
+        """pvol_li_many: len(rays) independent per-sample calls in one batch, call i with the live state mt[i] (uint32[624]),
+        mti[i].  Returns (Lv[n,30], T[n,30], mti[n], status[n]); mt is advanced in place.  Raises only for a batch-wide
+        argument error: a call that failed on its own (PVOL_E_LIMIT) has its code in status and its state left as it was."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype == abi.RAY_DTYPE and mt.dtype == np.uint32 and mt.flags["C_CONTIGUOUS"]
+        n = len(rays)
+        assert mt.shape == (n, 624)
+        mti = np.ascontiguousarray(mti, np.int32).copy()
+        Lv = np.zeros((n, 30), np.float32)
+        T = np.zeros((n, 30), np.float32)
+        status = np.zeros(n, np.int32)
+        rc = lib().pvol_li_many(self._h, rays.ctypes.data, n, mt.ctypes.data_as(_u32p), mti.ctypes.data_as(C.POINTER(C.c_int32)),
+                                Lv.ctypes.data_as(_f32p), T.ctypes.data_as(_f32p), status.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != abi.PVOL_OK and not (status != abi.PVOL_OK).any():
+            _check(rc, "pvol_li_many")
+        return Lv, T, mti, status
+
+    def set_li_coalescing(self, max_batch, max_wait_us=0):
+        """Concurrent li_single (pvol_li) calls on this context are gathered into batches of up to max_batch (<= 1: off)."""
+        _check(lib().pvol_set_li_coalescing(self._h, int(max_batch), int(max_wait_us)), "pvol_set_li_coalescing")
+
+    def li_coalescing_stats(self, reset=False):
+        v = (C.c_uint64 * 6)()
+        _check(lib().pvol_get_li_coalescing_stats(self._h, v, int(reset)), "pvol_get_li_coalescing_stats")
+        return dict(zip(["calls", "batches", "largest_batch", "queued_behind", "batches_redone", "calls_failed"], (int(x) for x in v)))
 
     def transmittance(self, rays, streams):
         rays = np.ascontiguousarray(rays)

@@ -401,6 +401,31 @@ int pvol_check_errors(pvol_ctx *ctx);
 int pvol_li(pvol_ctx *ctx, const pvol_ray *ray, uint32_t *mt, int32_t *mti,
             float *Lv, float *T);
 
+/* n independent pvol_li calls in one device batch: ray i with its own live state mt[i*624..],
+ * mti[i] (advanced in place), Lv / T: n x 30 floats.  Every call's results are the bytes a lone
+ * pvol_li gives on the same input, whatever the other calls of the batch.  The batch runs after
+ * the context's device work still in flight (pvol_li_batch_device, pvol_render_tasks_device on
+ * any stream, and whatever runs on the default stream).  status (optional):
+ * one PVOL_* code per call, its outputs and state are written only where it is PVOL_OK.  Returns
+ * PVOL_OK or the first non-OK code in call order; PVOL_E_INVALID (nothing run) for a NULL
+ * array or an mti outside 0..624.  n == 0 does nothing. */
+int pvol_li_many(pvol_ctx *ctx, const pvol_ray *rays, uint32_t n, uint32_t *mt, int32_t *mti,
+                 float *Lv, float *T, int32_t *status);
+
+/* Coalescing of concurrent pvol_li calls on one context.  max_batch <= 1 (the default): every
+ * call is its own batch, serialised.  Otherwise calls made at the same time queue, and whenever
+ * no batch is in flight one of them sends up to max_batch queued calls as one pvol_li_many batch;
+ * an idle sender waits up to max_wait_us for more callers first.  Results are unchanged.
+ * PVOL_E_INVALID: max_batch > 4096 or max_wait_us > 1000.  At pvol_create the environment
+ * variable PVOL_LI_COALESCE=<max_batch> sets the default (wait 0). */
+int pvol_set_li_coalescing(pvol_ctx *ctx, uint32_t max_batch, uint32_t max_wait_us);
+/* out6 (since creation or the last reset): calls served through coalesced batches, coalesced
+ * batches, largest coalesced batch, calls that queued while a batch was in flight; then, over
+ * every batch of pvol_li_many and the coalescer: batches redone call by call because the
+ * hand-over backup fired (each call then runs as a lone pvol_li), calls that failed on their own
+ * (PVOL_E_LIMIT: such a call's error is its own, it never reaches pvol_check_errors). */
+int pvol_get_li_coalescing_stats(pvol_ctx *ctx, uint64_t *out6, int reset);
+
 /* Replaces PhotonVolumeIntegrator::Transmittance with sample == NULL
  * (photonvolume.cpp:15-30): step = 4*stepSize, offset = one RandomFloat per ray.
  * Rays are grouped into streams like pvol_li_batch; out: 30 floats per ray. */

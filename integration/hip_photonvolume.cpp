@@ -63,9 +63,16 @@ class HipPhotonVolumeIntegrator : public VolumeIntegrator {
 public:
     // `shooter` != NULL: take the volume map the reference's own PhotonShooter built (its Preprocess runs before ours,
     // renderers/samplerrenderer.cpp:194-196) instead of shooting on the device -- the oracle-identical map.
-    HipPhotonVolumeIntegrator(const pvol_params &p, const PhotonShooter *shooter = NULL)
+    // `coalesce` > 1: concurrent Li() calls of the renderer's task threads are gathered into device batches of up to that many
+    // (pvol_set_li_coalescing; results unchanged), a sender waiting up to `coalesceWaitUs` for more.  0, 0 keeps the context's
+    // default (one batch per call, or PVOL_LI_COALESCE from the environment).
+    HipPhotonVolumeIntegrator(const pvol_params &p, const PhotonShooter *shooter = NULL, int coalesce = 0, int coalesceWaitUs = 0)
         : params(p), ctx(NULL), mapSource(shooter), tauSampleOffset(0), scatterSampleOffset(0) {
         if (pvol_create(&params, &ctx) != PVOL_OK) Severe("photonvolume_hip: no usable HIP device");
+        if (coalesce != 0 || coalesceWaitUs != 0) {
+            if (coalesce < 0 || coalesceWaitUs < 0 || pvol_set_li_coalescing(ctx, (uint32_t)coalesce, (uint32_t)coalesceWaitUs) != PVOL_OK)
+                Severe("photonvolume_hip: \"coalesce\" must lie in 0..4096 and \"coalescewait\" in 0..1000");
+        }
     }
     ~HipPhotonVolumeIntegrator() { pvol_destroy(ctx); }
 
@@ -261,5 +268,6 @@ VolumeIntegrator *CreateHipPhotonVolumeIntegrator(const ParamSet &volparams, con
     p.final_gather = surfparams.FindOneBool("finalgather", true) ? 1 : 0;
     if (PbrtOptions.quickRender) { p.n_caustic_photons /= 10; p.n_indirect_photons /= 10; }
     const bool deviceShoot = volparams.FindOneBool("deviceshoot", true);
-    return new HipPhotonVolumeIntegrator(p, deviceShoot ? NULL : psh);
+    const int coalesce = volparams.FindOneInt("coalesce", 0), coalesceWait = volparams.FindOneInt("coalescewait", 0);
+    return new HipPhotonVolumeIntegrator(p, deviceShoot ? NULL : psh, coalesce, coalesceWait);
 }
