@@ -11,7 +11,13 @@ over the ranks, photon map replicated, one RCCL all-reduce of the film per step 
 scaling, the north_star's split); `--weak` renders one whole frame per rank instead (replicas, no collective).
 value = samples of all ranks / max-over-ranks time.
 
+A plain run does what the headline figure needs and nothing more: set up, warm up, time the steps, write --dump-outputs,
+print the line (with `end_to_end` and the `roofline` of the timed launches).  `--full` adds what takes runs of its own:
+the CPU baseline (the oracle on the host's cores, ~20 s) and the `parity` leg (the GPU re-renders the tasks the CPU
+rendered), N = 1 only.
+
     python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: spawns the N ranks itself)
+    python bench.py --full                               (+ cpu_baseline and parity)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N --dry-run                   (prints the partition; needs no GPU)
 """
@@ -352,7 +358,10 @@ def main():
     ap.add_argument("--yres", type=int, default=720)
     ap.add_argument("--spp", type=int, default=256)
     ap.add_argument("--photons", type=int, default=1000000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also time the CPU baseline (the oracle on this host's cores, ~20 s) and re-render "
+                         "its tasks on the GPU for the `parity` check (exit 3 when it fails); a plain run does neither")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity leg")
     ap.add_argument("--stats", action="store_true", help="collect gather work counters inside the timed steps (slower)")
     ap.add_argument("--cell-scale", type=float, default=0.0, help="photon-grid cell edge multiplier (0 = library default)")
     ap.add_argument("--photon-source", choices=["shoot", "synth"], default="shoot",
@@ -386,6 +395,7 @@ def main():
         ap.error("--steps must be >= 1")
     if args.dump_outputs and args.emulate_ranks:
         ap.error("--dump-outputs needs the timed steps; --emulate-ranks replaces them")
+    cpu_leg = args.full and not args.no_cpu_baseline   # the CPU baseline + parity leg (rank 0 of N = 1 only)
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.dry_run:
@@ -435,7 +445,7 @@ def main():
         # PhotonShooter::Preprocess on the device; every rank shoots the same map (same seeds): replicated, no traffic
         pv.preprocess(args.shoot_tasks)
         shoot_s, build_s = pv.preprocess_times()
-        photons = pv.download_photons() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+        photons = pv.download_photons() if (rank == 0 and world == 1 and cpu_leg) else None
         photon_note = "device shooter, %d virtual tasks" % args.shoot_tasks
     else:
         photons = synth_photons(args.photons)
@@ -572,7 +582,7 @@ def main():
         if dumped is not None:
             res["dumped_outputs"] = dumped
         cpu, ctr, first = (None, None, None)
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is a rank-0, N=1 leg
+        if cpu_leg and world == 1:   # the CPU baseline is a rank-0, N=1 leg of --full
             if args.driver == "tile":
                 surf = None
                 if args.surface:
