@@ -148,6 +148,9 @@ void pvol_destroy(pvol_ctx *c) {
     if (c->dState) hipFree(c->dState);
     if (c->dDefer) hipFree(c->dDefer);
     for (int i = 0; i < 6; ++i) if (c->dTile[i]) hipFree(c->dTile[i]);
+    if (c->groupFilmEv) hipEventDestroy(c->groupFilmEv);
+    if (c->groupStageEv) hipEventDestroy(c->groupStageEv);
+    if (c->dGroupStage) hipFree(c->dGroupStage);
     if (c->ds) hipFree(c->ds);
     if (c->dsh) hipFree(c->dsh);
     if (c->dCounters) hipFree(c->dCounters);

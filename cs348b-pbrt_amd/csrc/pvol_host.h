@@ -145,6 +145,11 @@ struct pvol_ctx {
     hipStream_t coStream = 0;
     unsigned char *coHostIn = 0, *coHostOut = 0, *coDevIn = 0, *coDevOut = 0;
     uint32_t coCap = 0;
+    // pvol_render_frame_group (pvol_group.hip): the event marking this context's film done; as the root, the other films' staging
+    // and the event after the sum that last read it
+    hipEvent_t groupFilmEv = 0, groupStageEv = 0;
+    float4 *dGroupStage = 0;
+    size_t groupStageBytes = 0;
 };
 
 // One per-sample call of a coalesced batch: the caller's buffers, written only when rc ends PVOL_OK.

@@ -111,6 +111,9 @@ def lib():
         L.pvol_partition_tasks.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p]
         L.pvol_render_frame_ranks.argtypes = [C.c_void_p, C.POINTER(abi.Camera), C.POINTER(abi.Film), C.POINTER(abi.Sampler), C.c_uint32, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pvol_preprocess_group.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32]
+        L.pvol_render_frame_group.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(abi.Camera), C.POINTER(abi.Film), C.POINTER(abi.Sampler),
+                                              C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p)]
         L.pvol_enable_phase_timing.argtypes = [C.c_void_p, C.c_int]
         L.pvol_get_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
         _lib = L
@@ -127,7 +130,7 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_set_surface_integrator", "pvol_enable_phase_timing", "pvol_get_phase_ms",
            "pvol_partition_tasks", "pvol_render_frame_ranks", "pvol_preprocess_blocks",
            "pvol_preprocess_ranks", "pvol_get_exchange_seconds", "pvol_li_many", "pvol_set_li_coalescing",
-           "pvol_get_li_coalescing_stats"]
+           "pvol_get_li_coalescing_stats", "pvol_preprocess_group", "pvol_render_frame_group"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -140,6 +143,28 @@ def partition_tasks(n_tasks, rank, n_ranks):
     ids = np.zeros(n.value, np.uint32)
     _check(lib().pvol_partition_tasks(n_tasks, rank, n_ranks, ids.ctypes.data_as(_u32p), n.value, C.byref(n)), "pvol_partition_tasks")
     return ids
+
+
+def _ptrs(values):
+    """A C array of pointers (integers, 0 / None = NULL)."""
+    return (C.c_void_p * len(values))(*[v or None for v in values])
+
+
+def preprocess_group(pvs, n_tasks, block_paths=4096):
+    """pvol_preprocess_group: preprocess(n_tasks, block_paths) sharded over the contexts `pvs` (a list of PhotonVolume, one host
+    thread each, joined by an in-process all-gather); every context ends with the single-context map, bit for bit."""
+    _check(lib().pvol_preprocess_group(_ptrs([pv._h.value for pv in pvs]), len(pvs), n_tasks, block_paths), "pvol_preprocess_group")
+
+
+def render_frame_group(pvs, cam, film, smp, d_pixels, d_rgb, hip_streams=None):
+    """pvol_render_frame_group: one frame over the contexts `pvs`.  d_pixels: one full-frame film per context (device pointers, on
+    that context's device), d_rgb on the first context's device (0: no resolve), hip_streams: one per context (None: null streams).
+    Enqueued on hip_streams[0]: synchronise it (or the first context's device) before reading d_pixels[0] / d_rgb."""
+    if len(d_pixels) != len(pvs) or (hip_streams is not None and len(hip_streams) != len(pvs)):
+        raise ValueError("render_frame_group: one film (and stream) per context")
+    streams = None if hip_streams is None else _ptrs(list(hip_streams))
+    _check(lib().pvol_render_frame_group(_ptrs([pv._h.value for pv in pvs]), len(pvs), C.byref(cam), C.byref(film), C.byref(smp),
+                                         _ptrs(list(d_pixels)), d_rgb or None, streams), "pvol_render_frame_group")
 
 
 def _check(rc, where):

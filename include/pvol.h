@@ -505,6 +505,33 @@ int pvol_partition_tasks(uint32_t n_tasks, uint32_t rank, uint32_t n_ranks, uint
 int pvol_render_frame_ranks(pvol_ctx *ctx, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *sampler,
                             uint32_t rank, uint32_t n_ranks, void *nccl_comm, float *d_pixels, float *d_rgb, void *hip_stream);
 
+/* ---- several GPUs from ONE process: the two calls above with an in-process transport instead of a rendezvous and RCCL ----
+ * ctxs: n_ctx (1 .. 64) distinct contexts made by pvol_create, each with its own params.device (several may share a device), all given
+ * the same pvol_set_scene (and the same pvol_set_surface_integrator, if one is used).  Both calls run one host thread per context and
+ * join them all before they return, so no context is ever left waiting for another.  A context takes part in one call at a time. */
+
+/* pvol_preprocess_ranks(ctxs[i], n_tasks, block_paths, i, n_ctx, &comm) on every context at once, `comm` a host all-gather between the
+ * threads (a barrier and one staging buffer, rank-major).  Every context ends with the map, the surface stores (keep_surface_photons)
+ * and the pvol_get_shoot_stats of pvol_preprocess_blocks(ctx, n_tasks, block_paths) on one context, bit for bit.  Checked on every
+ * context before any thread starts: PVOL_E_INVALID (NULL array or entry, n_ctx 0 or > 64, a context listed twice, n_tasks or
+ * block_paths out of pvol_preprocess_blocks' range), PVOL_E_NO_SCENE, PVOL_E_NO_DEVICE (hipSetDevice fails).  An all-gather that
+ * waits for a context whose thread has returned fails, which the ranks protocol turns into PVOL_E_NO_DEVICE on the others; the call
+ * returns the code of the lowest-indexed context that failed on its own, else the code the protocol made every context agree on. */
+int pvol_preprocess_group(pvol_ctx *const *ctxs, uint32_t n_ctx, uint32_t n_tasks, uint32_t block_paths);
+
+/* One frame over the contexts: context i zeroes its own full-frame film d_pixels[i] (x*y*4 floats on its device, 16-byte aligned) and
+ * renders the tasks pvol_partition_tasks(sampler->n_tasks, i, n_ctx) deals it into it (pvol_render_tasks_device) on hip_streams[i].
+ * Once every context has, context 0's stream hip_streams[0] waits for the others', copies films 1 .. n_ctx-1 (hipMemcpyPeerAsync)
+ * into a staging buffer context 0 keeps (grown on demand, freed by pvol_destroy), adds them in index order into d_pixels[0] and
+ * resolves that into d_rgb (x*y*3 floats on context 0's device; NULL: no resolve).  Returns once all of it is enqueued:
+ * synchronising hip_streams[0] covers every device, and until then films 1 .. n_ctx-1 are still being read.  hip_streams may be
+ * NULL, and a NULL entry is the null stream of that context's device.  If any context fails nothing is reduced or resolved, and
+ * the call returns the code of the lowest-indexed failing context.  PVOL_E_INVALID, checked before any device is touched: NULL
+ * ctxs, d_pixels, camera, film or sampler, a NULL or duplicate context, a NULL or misaligned d_pixels[i], n_ctx 0 or > 64, an
+ * empty film. */
+int pvol_render_frame_group(pvol_ctx *const *ctxs, uint32_t n_ctx, const pvol_camera *camera, const pvol_film *film,
+                            const pvol_sampler *sampler, float *const *d_pixels, float *d_rgb, void *const *hip_streams);
+
 /* ImageFilm::AddSample (film/image.cpp:78-137) for n samples: d_image_xy 2 floats, d_xyz `xyz_stride`
  * floats per sample (X,Y,Z first). */
 int pvol_film_add_samples_device(pvol_ctx *ctx, const pvol_film *film, const float *d_image_xy,

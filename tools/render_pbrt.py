@@ -3,7 +3,7 @@
 -> SamplerRendererTasks on the device (LD sampler, camera, surface PhotonIntegrator where it applies, PhotonVolumeIntegrator,
 image film) -> RGB.
 
-    python tools/render_pbrt.py SCENE.pbrt OUT.pfm [--xres N --yres N --spp N --photons N --shoot-tasks N --no-surface]
+    python tools/render_pbrt.py SCENE.pbrt OUT.pfm [--xres N --yres N --spp N --photons N --shoot-tasks N --no-surface --devices 0,1,...]
 
 The file's own Film / Sampler / integrator parameters are used unless overridden.  The surface integrator (direct lighting +
 caustic estimate on matte surfaces) is switched on when the scene asks for "photonmap" and the device path
@@ -22,7 +22,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_tasks=2048, surface=True, log=print, caustic_photons=None):
+def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_tasks=2048, surface=True, log=print, caustic_photons=None,
+                      devices=None):
+    """devices: None renders on one context (params.device 0); a list of HIP device ordinals (repeats allowed: [0, 0] runs the
+    two-context protocol on one GPU) makes one context per entry, shoots with preprocess_group and renders with render_frame_group,
+    whose render_s then includes the film reduce and the resolve."""
     import torch
     pkg = importlib.import_module("cs348b-pbrt_amd")
     pvol = importlib.import_module("cs348b-pbrt_amd.pvol")
@@ -37,19 +41,37 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
     if caustic_photons is not None:
         over["n_caustic_photons"] = int(caustic_photons)
     params = abi.params_from_blob(scene, **over)
-    pv = pvol.PhotonVolume(params)
+    group = devices is not None
+    if group:
+        devices = [int(d) for d in devices]
+        if not devices:
+            raise ValueError("devices: at least one device ordinal")
+    pvs = []
     try:
+        if group:
+            for d in devices:
+                pd = abi.Params.from_buffer_copy(params)
+                pd.device = d
+                pvs.append(pvol.PhotonVolume(pd))
+        else:
+            pvs.append(pvol.PhotonVolume(params))
+        pv = pvs[0]
         holder = abi.SceneHolder(scene)
-        pv.set_scene(holder)
+        for q in pvs:
+            q.set_scene(holder)
         if int(scene["lights.kind"].size):
-            pv.preprocess(shoot_tasks)
+            if group:
+                pvol.preprocess_group(pvs, shoot_tasks)
+            else:
+                pv.preprocess(shoot_tasks)
         st = pv.shoot_stats()
         log("photon map: %d volume, %d caustic photons from %d paths" % (st["stored_volume"], st["stored_caustic"], st["paths"]))
         used_surface = False
         if surface and scene["surf.name"] == "photonmap":
             try:
-                pv.set_surface_integrator(int(scene["surf.params.i"][0]), float(scene["surf.params.f"][0]), int(scene["surf.params.i"][1]),
-                                          bool(scene["surf.params.i"][2]), from_preprocess=True)
+                for q in pvs:
+                    q.set_surface_integrator(int(scene["surf.params.i"][0]), float(scene["surf.params.f"][0]), int(scene["surf.params.i"][1]),
+                                             bool(scene["surf.params.i"][2]), from_preprocess=True)
                 used_surface = True
             except pvol.PvolError as e:
                 log("surface integrator not applied (%s): the image holds the volume term only" % e)
@@ -59,33 +81,47 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
         film = abi.make_film(xres, yres, pvol.gaussian_filter_table())
         smp = abi.make_sampler(xres, yres, spp, n_tiles)
         ids = np.arange(n_tiles, dtype=np.uint32)
-        dev = torch.device("cuda:0")
-        px = torch.zeros((yres, xres, 4), dtype=torch.float32, device=dev)
-        rgb = torch.zeros((yres, xres, 3), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize()
+        devs = [torch.device("cuda:%d" % d) for d in devices] if group else [torch.device("cuda:0")]
+        pxs = [torch.zeros((yres, xres, 4), dtype=torch.float32, device=d) for d in devs]
+        px = pxs[0]
+        rgb = torch.zeros((yres, xres, 3), dtype=torch.float32, device=devs[0])
+        for d in sorted(set(devs), key=str):
+            torch.cuda.synchronize(d)
+
+        def frame():   # the group call zeroes its films, reduces them on the first context's device and resolves there
+            if group:
+                pvol.render_frame_group(pvs, cam, film, smp, [x.data_ptr() for x in pxs], rgb.data_ptr())
+                torch.cuda.synchronize(devs[0])   # covers every context's device
+            else:
+                pv.render_tasks(cam, film, smp, ids, px.data_ptr())
+                torch.cuda.synchronize()
         t0 = time.perf_counter()
         try:
-            pv.render_tasks(cam, film, smp, ids, px.data_ptr())
-            torch.cuda.synchronize()
+            frame()
         except pvol.PvolError as e:
             if not used_surface:
                 raise
             log("surface integrator not applied (%s): the image holds the volume term only" % e)
-            pv.set_surface_integrator(off=True)
+            for q in pvs:
+                q.set_surface_integrator(off=True)
             used_surface = False
             px.zero_()
             t0 = time.perf_counter()
-            pv.render_tasks(cam, film, smp, ids, px.data_ptr())
-            torch.cuda.synchronize()
+            frame()
         render_s = time.perf_counter() - t0
-        pv.film_resolve(film, px.data_ptr(), rgb.data_ptr())
-        torch.cuda.synchronize()
-        pv.check_errors()
-        return rgb.cpu().numpy(), {"xres": xres, "yres": yres, "spp": spp, "surface_integrator": used_surface, "kernel": pv.march_kernel_name(),
-                                   "photons": int(st["stored_volume"]), "caustic_photons": int(st["stored_caustic"]),
-                                   "render_s": render_s}
+        if not group:
+            pv.film_resolve(film, px.data_ptr(), rgb.data_ptr())
+            torch.cuda.synchronize()
+        for q in pvs:
+            q.check_errors()
+        info = {"xres": xres, "yres": yres, "spp": spp, "surface_integrator": used_surface, "kernel": pv.march_kernel_name(),
+                "photons": int(st["stored_volume"]), "caustic_photons": int(st["stored_caustic"]), "render_s": render_s}
+        if group:
+            info["devices"] = devices
+        return rgb.cpu().numpy(), info
     finally:
-        pv.close()
+        for q in pvs:
+            q.close()
 
 
 def write_pfm(path, rgb):
@@ -105,7 +141,10 @@ if __name__ == "__main__":
     ap.add_argument("--photons", type=int)
     ap.add_argument("--shoot-tasks", type=int, default=2048)
     ap.add_argument("--no-surface", action="store_true")
+    ap.add_argument("--devices", help="comma-separated HIP device ordinals, one context each (repeats allowed, e.g. 0,0); "
+                                      "default: one context on device 0")
     a = ap.parse_args()
-    img, info = render_scene_file(a.scene, a.xres, a.yres, a.spp, a.photons, a.shoot_tasks, not a.no_surface)
+    devices = [int(d) for d in a.devices.split(",")] if a.devices else None
+    img, info = render_scene_file(a.scene, a.xres, a.yres, a.spp, a.photons, a.shoot_tasks, not a.no_surface, devices=devices)
     write_pfm(a.out, img)
     print(info, "mean rgb", img.mean(axis=(0, 1)))
