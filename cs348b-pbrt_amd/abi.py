@@ -247,6 +247,10 @@ class Film(C.Structure):
                 ("filter_table", C.c_float * (FILTER_TABLE_SIZE * FILTER_TABLE_SIZE))]
 
 
+class FilmWindow(C.Structure):   # pvol_film_window: ImageFilm's xPixelStart / yPixelStart / xPixelCount / yPixelCount
+    _fields_ = [("x_pixel_start", C.c_int32), ("y_pixel_start", C.c_int32), ("x_pixel_count", C.c_int32), ("y_pixel_count", C.c_int32)]
+
+
 class Sampler(C.Structure):
     _fields_ = [("x_start", C.c_int32), ("x_end", C.c_int32), ("y_start", C.c_int32), ("y_end", C.c_int32),
                 ("pixel_samples", C.c_uint32), ("n_tasks", C.c_uint32),
@@ -300,6 +304,18 @@ def make_sampler(xres, yres, spp, n_tasks, xwidth=2.0, ywidth=2.0, n1d=(1, 1), n
         s.n2d[i] = v
     s.tau_index, s.scatter_index = tau_index, scatter_index
     return s
+
+
+def make_window(x_pixel_start, y_pixel_start, x_pixel_count, y_pixel_count):
+    w = FilmWindow()
+    w.x_pixel_start, w.y_pixel_start, w.x_pixel_count, w.y_pixel_count = int(x_pixel_start), int(y_pixel_start), int(x_pixel_count), int(y_pixel_count)
+    return w
+
+
+def set_sample_extent(sampler, extent):
+    """Puts a sample extent (x_start, x_end, y_start, y_end: pvol.film_sample_extent of a crop window) into a pvol_sampler."""
+    sampler.x_start, sampler.x_end, sampler.y_start, sampler.y_end = (int(v) for v in extent)
+    return sampler
 
 
 def perspective_camera(fov, xres, yres, camera_to_world):

@@ -164,14 +164,17 @@ extern "C" int pvol_preprocess_group(pvol_ctx *const *ctxs, uint32_t n, uint32_t
     return PVOL_OK;
 }
 
-extern "C" int pvol_render_frame_group(pvol_ctx *const *ctxs, uint32_t n, const pvol_camera *camera, const pvol_film *film,
-                                       const pvol_sampler *smp, float *const *dPixels, float *dRgb, void *const *hipStreams) {
+extern "C" int pvol_render_frame_group_window(pvol_ctx *const *ctxs, uint32_t n, const pvol_camera *camera, const pvol_film *film,
+                                              const pvol_film_window *window, const pvol_sampler *smp, float *const *dPixels, float *dRgb,
+                                              void *const *hipStreams) {
     if (!ctxs || !dPixels || !camera || !film || !smp || n == 0 || n > PVOL_GROUP_MAX_CTX) return PVOL_E_INVALID;
-    if (film->x_resolution <= 0 || film->y_resolution <= 0) return PVOL_E_INVALID;
+    if (film->x_resolution <= 0 || film->y_resolution <= 0 || !pvol_window_ok(film, window)) return PVOL_E_INVALID;
     for (uint32_t i = 0; i < n; ++i)
         if (!ctxs[i] || !dPixels[i] || ((uintptr_t)dPixels[i] & 15u)) return PVOL_E_INVALID;   // film_sum_kernel moves float4 pixels
     if (!distinct(ctxs, n)) return PVOL_E_INVALID;
-    const uint64_t nPix = (uint64_t)film->x_resolution * (uint64_t)film->y_resolution;
+    // every film, the staging buffer and the sum hold the window's pixels (film/image.cpp:54), not the resolution's
+    const pvol_film_window win = pvol_window_or_full(film, window);
+    const uint64_t nPix = (uint64_t)win.x_pixel_count * (uint64_t)win.y_pixel_count;
     const size_t filmBytes = sizeof(float4) * nPix;
     auto streamOf = [&](uint32_t i) { return hipStreams ? (hipStream_t)hipStreams[i] : (hipStream_t)0; };
     KeepDevice keep;
@@ -192,7 +195,7 @@ extern "C" int pvol_render_frame_group(pvol_ctx *const *ctxs, uint32_t n, const 
         // the root's last reduce (stage copies, sum, resolve) may still be reading this film
         if (root->groupStageEv && !ok(hipStreamWaitEvent(s, root->groupStageEv, 0))) return PVOL_E_NO_DEVICE;
         if (!ok(hipMemsetAsync(dPixels[i], 0, filmBytes, s))) return PVOL_E_NO_DEVICE;
-        const int r = pvol_render_tasks_device(c, camera, film, smp, ids.data(), nIds, dPixels[i], 0, s);
+        const int r = pvol_render_tasks_window_device(c, camera, film, window, smp, ids.data(), nIds, dPixels[i], 0, s);
         if (r != PVOL_OK || i == 0) return r;
         if (!c->groupFilmEv && !ok(hipEventCreateWithFlags(&c->groupFilmEv, hipEventDisableTiming))) { c->groupFilmEv = 0; return PVOL_E_NO_DEVICE; }
         return ok(hipEventRecord(c->groupFilmEv, s)) ? PVOL_OK : PVOL_E_NO_DEVICE;
@@ -224,7 +227,11 @@ extern "C" int pvol_render_frame_group(pvol_ctx *const *ctxs, uint32_t n, const 
                            n - 1, nPix);
         if (!ok(hipGetLastError())) return PVOL_E_NO_DEVICE;
     }
-    int rc0 = dRgb ? pvol_film_resolve_device(root, film, dPixels[0], dRgb, s0) : PVOL_OK;
+    int rc0 = dRgb ? pvol_film_resolve_window_device(root, film, window, dPixels[0], dRgb, s0) : PVOL_OK;
     if (n > 1 && rc0 == PVOL_OK && !ok(hipEventRecord(root->groupStageEv, s0))) rc0 = PVOL_E_NO_DEVICE;
     return rc0;
+}
+extern "C" int pvol_render_frame_group(pvol_ctx *const *ctxs, uint32_t n, const pvol_camera *camera, const pvol_film *film,
+                                       const pvol_sampler *smp, float *const *dPixels, float *dRgb, void *const *hipStreams) {
+    return pvol_render_frame_group_window(ctxs, n, camera, film, 0, smp, dPixels, dRgb, hipStreams);
 }

@@ -186,4 +186,16 @@ int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream);
 // an RCCL function by name, bound at run time once per process (pvol_tile.hip); 0 when no RCCL is in reach
 void *pvol_rccl_symbol(const char *name);
 }
+
+// ImageFilm's crop window behind the *_window entry points: a NULL window is the whole frame (crop 0 1 0 1), which is what the
+// entry points without a window pass
+static inline bool pvol_window_ok(const pvol_film *f, const pvol_film_window *w) {
+    return !w || (w->x_pixel_start >= 0 && w->y_pixel_start >= 0 && w->x_pixel_count > 0 && w->y_pixel_count > 0 &&
+                  w->x_pixel_count <= f->x_resolution - w->x_pixel_start && w->y_pixel_count <= f->y_resolution - w->y_pixel_start);
+}
+static inline pvol_film_window pvol_window_or_full(const pvol_film *f, const pvol_film_window *w) {
+    if (w) return *w;
+    pvol_film_window full = {0, 0, f->x_resolution, f->y_resolution};
+    return full;
+}
 #endif

@@ -62,6 +62,34 @@ extern "C" uint64_t pvol_render_sample_count(const pvol_sampler *s, const uint32
     return total;
 }
 
+static bool film_ok(const pvol_film *f);
+
+// ImageFilm's constructor: the film image extent of a crop window (film/image.cpp:48-51)
+extern "C" int pvol_film_window_from_crop(const pvol_film *film, const float *crop, pvol_film_window *out) {
+    if (!film_ok(film) || !crop || !out) return PVOL_E_INVALID;
+    for (int i = 0; i < 4; ++i) if (!(crop[i] >= 0.f && crop[i] <= 1.f)) return PVOL_E_INVALID;   // NaN fails too
+    if (crop[0] > crop[1] || crop[2] > crop[3]) return PVOL_E_INVALID;
+    pvol_film_window w;
+    w.x_pixel_start = (int)ceilf(film->x_resolution * crop[0]);
+    w.x_pixel_count = std::max(1, (int)ceilf(film->x_resolution * crop[1]) - w.x_pixel_start);
+    w.y_pixel_start = (int)ceilf(film->y_resolution * crop[2]);
+    w.y_pixel_count = std::max(1, (int)ceilf(film->y_resolution * crop[3]) - w.y_pixel_start);
+    if (!pvol_window_ok(film, &w)) return PVOL_E_INVALID;   // crop[0] == crop[1] == 1: the reference's one pixel past the frame
+    *out = w;
+    return PVOL_OK;
+}
+
+// ImageFilm::GetSampleExtent (film/image.cpp:157-166)
+extern "C" int pvol_film_sample_extent(const pvol_film *film, const pvol_film_window *window, int32_t out[4]) {
+    if (!film_ok(film) || !out || !pvol_window_ok(film, window)) return PVOL_E_INVALID;
+    const pvol_film_window w = pvol_window_or_full(film, window);
+    out[0] = (int)floorf(w.x_pixel_start + 0.5f - film->filter_xwidth);
+    out[1] = (int)ceilf(w.x_pixel_start + 0.5f + w.x_pixel_count + film->filter_xwidth);
+    out[2] = (int)floorf(w.y_pixel_start + 0.5f - film->filter_ywidth);
+    out[3] = (int)ceilf(w.y_pixel_start + 0.5f + w.y_pixel_count + film->filter_ywidth);
+    return PVOL_OK;
+}
+
 // ------------------------------------------------------------------------------------------ film kernels
 struct DevFilm {
     int32_t xres, yres;
@@ -86,8 +114,15 @@ __device__ __forceinline__ int wave_max_i(int v) {
 // usually share one small pixel window: weights are summed over the wave first and one lane issues the atomics
 // (the reference adds sample by sample with AtomicAdd in thread order, i.e. in no particular order either).
 // `guard`: the unexpected-radiance checks of samplerrenderer.cpp:118-133 applied to the XYZ record.
-__global__ __launch_bounds__(256) void film_add_kernel(DevFilm F, const float *xy, const float *xyz, uint32_t stride,
-                                                      unsigned long long n, int guard, float *pixels) {
+//
+// WINDOW: the film holds the pixels [wx0, wx1] x [wy0, wy1] of the frame only (ImageFilm's crop window): the footprint is clamped to
+// the window (film/image.cpp:86-89) and a pixel is addressed relative to it, `pitch` pixels per row (:121).  A sample in the filter
+// apron outside the window still reaches the pixels inside; one whose clamped footprint is empty leaves before any reduction or
+// atomic, and a wave of such samples returns at the ballot.  The full-frame form has the four bounds and the pitch as the constants
+// they were, so film_add_kernel compiles to what it was before the window existed.
+template <bool WINDOW>
+__device__ __forceinline__ void film_add_body(const DevFilm &F, const int wx0, const int wy0, const int wx1, const int wy1, const int pitch,
+                                              const float *xy, const float *xyz, uint32_t stride, unsigned long long n, int guard, float *pixels) {
     __shared__ float table[PVOL_FILTER_TABLE_SIZE * PVOL_FILTER_TABLE_SIZE];
     table[threadIdx.x] = F.table[threadIdx.x];
     __syncthreads();
@@ -103,8 +138,8 @@ __global__ __launch_bounds__(256) void film_add_kernel(DevFilm F, const float *x
         dimageY = xy[2 * i + 1] - 0.5f;
         x0 = (int)ceilf(dimageX - F.xw); x1 = (int)floorf(dimageX + F.xw);
         y0 = (int)ceilf(dimageY - F.yw); y1 = (int)floorf(dimageY + F.yw);
-        x0 = max(x0, 0); x1 = min(x1, F.xres - 1);
-        y0 = max(y0, 0); y1 = min(y1, F.yres - 1);
+        x0 = max(x0, WINDOW ? wx0 : 0); x1 = min(x1, WINDOW ? wx1 : F.xres - 1);
+        y0 = max(y0, WINDOW ? wy0 : 0); y1 = min(y1, WINDOW ? wy1 : F.yres - 1);
     }
     const bool valid = on && (x1 - x0) >= 0 && (y1 - y0) >= 0;
     if (!__ballot(valid)) return;
@@ -132,7 +167,7 @@ __global__ __launch_bounds__(256) void film_add_kernel(DevFilm F, const float *x
                 const float sx = wave_sum_f(wt * X), sy = wave_sum_f(wt * Y), sz = wave_sum_f(wt * Z), sw = wave_sum_f(wt);
                 if ((lane >> 2) == slot) {
                     const int c = lane & 3;
-                    myAddr = pixels + 4 * ((size_t)y * F.xres + x) + c;
+                    myAddr = pixels + 4 * (WINDOW ? (size_t)(y - wy0) * pitch + (x - wx0) : (size_t)y * F.xres + x) + c;
                     myVal = c == 0 ? sx : (c == 1 ? sy : (c == 2 ? sz : sw));
                 }
                 if (++slot == 16) {
@@ -150,14 +185,24 @@ __global__ __launch_bounds__(256) void film_add_kernel(DevFilm F, const float *x
                 const float fx = fabsf((x - dimageX) * F.invXW * PVOL_FILTER_TABLE_SIZE);
                 const int ix = min((int)floorf(fx), PVOL_FILTER_TABLE_SIZE - 1);
                 const float wt = table[iy * PVOL_FILTER_TABLE_SIZE + ix];
-                float *p = pixels + 4 * ((size_t)y * F.xres + x);
+                float *p = pixels + 4 * (WINDOW ? (size_t)(y - wy0) * pitch + (x - wx0) : (size_t)y * F.xres + x);
                 atomicAdd(p, wt * X); atomicAdd(p + 1, wt * Y); atomicAdd(p + 2, wt * Z); atomicAdd(p + 3, wt);
             }
         }
     }
 }
 
-// ImageFilm::WriteRGB without splats (film/image.cpp:178-214), XYZToRGB core/spectrum.h:51-55
+__global__ __launch_bounds__(256) void film_add_kernel(DevFilm F, const float *xy, const float *xyz, uint32_t stride,
+                                                      unsigned long long n, int guard, float *pixels) {
+    film_add_body<false>(F, 0, 0, 0, 0, 0, xy, xyz, stride, n, guard, pixels);
+}
+// W = xPixelStart, yPixelStart, xPixelCount, yPixelCount
+__global__ __launch_bounds__(256) void film_add_window_kernel(DevFilm F, int4 W, const float *xy, const float *xyz, uint32_t stride,
+                                                             unsigned long long n, int guard, float *pixels) {
+    film_add_body<true>(F, W.x, W.y, W.x + W.z - 1, W.y + W.w - 1, W.z, xy, xyz, stride, n, guard, pixels);
+}
+
+// ImageFilm::WriteRGB without splats (film/image.cpp:178-214), XYZToRGB core/spectrum.h:51-55: nPix = xPixelCount * yPixelCount
 __global__ void film_resolve_kernel(int nPix, const float *pixels, float *rgb) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nPix) return;
@@ -185,29 +230,45 @@ static DevFilm dev_film(const pvol_film *f) {
     return F;
 }
 
-static int film_add(pvol_ctx *c, const pvol_film *film, const float *dXY, const float *dXYZ, uint32_t stride, uint64_t n, int guard,
-                    float *dPixels, hipStream_t stream) {
+// window == NULL: the whole frame, through the full-frame kernel
+static int film_add(pvol_ctx *c, const pvol_film *film, const pvol_film_window *window, const float *dXY, const float *dXYZ, uint32_t stride,
+                    uint64_t n, int guard, float *dPixels, hipStream_t stream) {
     if (!n) return PVOL_OK;
     const DevFilm F = dev_film(film);
     const unsigned long long blocks = (n + 255ull) / 256ull;
     if (blocks > 0x7fffffffull) return PVOL_E_LIMIT;
-    hipLaunchKernelGGL(film_add_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, F, dXY, dXYZ, stride, (unsigned long long)n, guard, dPixels);
+    if (!window) {
+        hipLaunchKernelGGL(film_add_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, F, dXY, dXYZ, stride, (unsigned long long)n, guard, dPixels);
+    } else {
+        const int4 W = make_int4(window->x_pixel_start, window->y_pixel_start, window->x_pixel_count, window->y_pixel_count);
+        hipLaunchKernelGGL(film_add_window_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, F, W, dXY, dXYZ, stride, (unsigned long long)n, guard,
+                           dPixels);
+    }
     return ok(hipGetLastError()) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
+extern "C" int pvol_film_add_samples_window_device(pvol_ctx *c, const pvol_film *film, const pvol_film_window *window, const float *dXY,
+                                                   const float *dXYZ, uint32_t stride, uint64_t n, float *dPixels, void *hipStream) {
+    if (!c || !film_ok(film) || !pvol_window_ok(film, window) || (n && (!dXY || !dXYZ || !dPixels)) || stride < 3) return PVOL_E_INVALID;
+    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
+    return film_add(c, film, window, dXY, dXYZ, stride, n, 0, dPixels, (hipStream_t)hipStream);
+}
 extern "C" int pvol_film_add_samples_device(pvol_ctx *c, const pvol_film *film, const float *dXY, const float *dXYZ, uint32_t stride,
                                             uint64_t n, float *dPixels, void *hipStream) {
-    if (!c || !film_ok(film) || (n && (!dXY || !dXYZ || !dPixels)) || stride < 3) return PVOL_E_INVALID;
-    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    return film_add(c, film, dXY, dXYZ, stride, n, 0, dPixels, (hipStream_t)hipStream);
+    return pvol_film_add_samples_window_device(c, film, 0, dXY, dXYZ, stride, n, dPixels, hipStream);
 }
 
-extern "C" int pvol_film_resolve_device(pvol_ctx *c, const pvol_film *film, const float *dPixels, float *dRgb, void *hipStream) {
-    if (!c || !film_ok(film) || !dPixels || !dRgb) return PVOL_E_INVALID;
+extern "C" int pvol_film_resolve_window_device(pvol_ctx *c, const pvol_film *film, const pvol_film_window *window, const float *dPixels,
+                                               float *dRgb, void *hipStream) {
+    if (!c || !film_ok(film) || !pvol_window_ok(film, window) || !dPixels || !dRgb) return PVOL_E_INVALID;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    const int nPix = film->x_resolution * film->y_resolution;
+    const pvol_film_window w = pvol_window_or_full(film, window);
+    const int nPix = w.x_pixel_count * w.y_pixel_count;   // film/image.cpp:179
     hipLaunchKernelGGL(film_resolve_kernel, dim3((nPix + 255) / 256), dim3(256), 0, (hipStream_t)hipStream, nPix, dPixels, dRgb);
     return ok(hipGetLastError()) ? PVOL_OK : PVOL_E_NO_DEVICE;
+}
+extern "C" int pvol_film_resolve_device(pvol_ctx *c, const pvol_film *film, const float *dPixels, float *dRgb, void *hipStream) {
+    return pvol_film_resolve_window_device(c, film, 0, dPixels, dRgb, hipStream);
 }
 
 // ------------------------------------------------------------------------------------------ render
@@ -220,10 +281,12 @@ static bool grow(pvol_ctx *c, int slot, size_t bytes) {
     return true;
 }
 
-extern "C" int pvol_render_tasks_device(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *smp,
-                                        const uint32_t *taskIds, uint32_t nTaskIds, float *dPixels, const pvol_render_debug *debug,
-                                        void *hipStream) {
-    if (!c || !camera || !smp || !film_ok(film) || (nTaskIds && !taskIds) || !dPixels) return PVOL_E_INVALID;
+// The sampler carries the sample extent (the window's own, pvol_film_sample_extent, or any other): every size below -- the tasks'
+// sub-windows, the batches, the work buffers, the debug records -- comes from it, and only the splat reads the window.
+extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window,
+                                               const pvol_sampler *smp, const uint32_t *taskIds, uint32_t nTaskIds, float *dPixels,
+                                               const pvol_render_debug *debug, void *hipStream) {
+    if (!c || !camera || !smp || !film_ok(film) || !pvol_window_ok(film, window) || (nTaskIds && !taskIds) || !dPixels) return PVOL_E_INVALID;
     if (!c->haveScene) return PVOL_E_NO_SCENE;
     const uint32_t spp = smp->pixel_samples;
     if (spp == 0 || (spp & (spp - 1)) || spp > PVOL_MAX_PIXEL_SAMPLES) return PVOL_E_INVALID;   // LDSampler rounds up to a power of two itself
@@ -334,7 +397,7 @@ extern "C" int pvol_render_tasks_device(pvol_ctx *c, const pvol_camera *camera, 
                     return PVOL_E_NO_DEVICE;
             }
             pvol_phase_mark(c, stream, PVOL_PHASE_FILM);
-            rc = film_add(c, film, dXY, dOut, 4, nRays, 1, dPixels, stream);
+            rc = film_add(c, film, window, dXY, dOut, 4, nRays, 1, dPixels, stream);
             pvol_phase_mark(c, stream, PVOL_PHASE_END);
             if (rc != PVOL_OK) return rc;
         }
@@ -348,6 +411,11 @@ extern "C" int pvol_render_tasks_device(pvol_ctx *c, const pvol_camera *camera, 
         b0 = b1;
     }
     return PVOL_OK;
+}
+extern "C" int pvol_render_tasks_device(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *smp,
+                                        const uint32_t *taskIds, uint32_t nTaskIds, float *dPixels, const pvol_render_debug *debug,
+                                        void *hipStream) {
+    return pvol_render_tasks_window_device(c, camera, film, 0, smp, taskIds, nTaskIds, dPixels, debug, hipStream);
 }
 
 // ------------------------------------------------------------------------------------------ multi-GPU frame (north_star)
@@ -378,13 +446,14 @@ extern "C" void *pvol_rccl_symbol(const char *name) {
 }
 typedef ncclResult_t (*nccl_reduce_fn)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, int, ncclComm_t, hipStream_t);
 
-// One rank of an N-GPU frame: its share of the render tasks into its own full-frame film, ONE ncclReduce(sum) of the film to rank 0
+// One rank of an N-GPU frame: its share of the render tasks into its own film (the window's pixels), ONE ncclReduce(sum) of the film to rank 0
 // (the Gaussian filter splats across tile borders, film/image.cpp:82-134, so tiles cannot simply be gathered), resolve on rank 0.
 // Every rank holds the whole photon map beforehand: pvol_preprocess with the same seeds on each rank, or pvol_preprocess_ranks,
 // which shares the shoot and leaves the same map on all of them.
-extern "C" int pvol_render_frame_ranks(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *smp,
-                                       uint32_t rank, uint32_t nRanks, void *ncclComm, float *dPixels, float *dRgb, void *hipStream) {
-    if (!c || !smp || !film_ok(film) || !dPixels || !nRanks || rank >= nRanks) return PVOL_E_INVALID;
+extern "C" int pvol_render_frame_ranks_window(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window,
+                                              const pvol_sampler *smp, uint32_t rank, uint32_t nRanks, void *ncclComm, float *dPixels,
+                                              float *dRgb, void *hipStream) {
+    if (!c || !smp || !film_ok(film) || !pvol_window_ok(film, window) || !dPixels || !nRanks || rank >= nRanks) return PVOL_E_INVALID;
     if (nRanks > 1 && !ncclComm) return PVOL_E_INVALID;
     nccl_reduce_fn reduce = 0;
     if (nRanks > 1 && !(reduce = (nccl_reduce_fn)pvol_rccl_symbol("ncclReduce"))) return PVOL_E_NO_DEVICE;   // no RCCL in reach
@@ -394,11 +463,16 @@ extern "C" int pvol_render_frame_ranks(pvol_ctx *c, const pvol_camera *camera, c
     pvol_partition_tasks(smp->n_tasks, rank, nRanks, 0, 0, &n);
     std::vector<uint32_t> ids(n);
     pvol_partition_tasks(smp->n_tasks, rank, nRanks, ids.data(), n, &n);
-    const size_t nFloats = (size_t)film->x_resolution * film->y_resolution * 4;
+    const pvol_film_window w = pvol_window_or_full(film, window);
+    const size_t nFloats = (size_t)w.x_pixel_count * w.y_pixel_count * 4;
     if (!ok(hipMemsetAsync(dPixels, 0, nFloats * sizeof(float), stream))) return PVOL_E_NO_DEVICE;
-    int rc = pvol_render_tasks_device(c, camera, film, smp, ids.data(), n, dPixels, 0, hipStream);
+    int rc = pvol_render_tasks_window_device(c, camera, film, window, smp, ids.data(), n, dPixels, 0, hipStream);
     if (rc != PVOL_OK) return rc;
     if (nRanks > 1 && reduce(dPixels, dPixels, nFloats, ncclFloat, ncclSum, 0, (ncclComm_t)ncclComm, stream) != ncclSuccess) return PVOL_E_NO_DEVICE;
-    if (rank == 0 && dRgb) rc = pvol_film_resolve_device(c, film, dPixels, dRgb, hipStream);
+    if (rank == 0 && dRgb) rc = pvol_film_resolve_window_device(c, film, window, dPixels, dRgb, hipStream);
     return rc;
+}
+extern "C" int pvol_render_frame_ranks(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *smp,
+                                       uint32_t rank, uint32_t nRanks, void *ncclComm, float *dPixels, float *dRgb, void *hipStream) {
+    return pvol_render_frame_ranks_window(c, camera, film, 0, smp, rank, nRanks, ncclComm, dPixels, dRgb, hipStream);
 }

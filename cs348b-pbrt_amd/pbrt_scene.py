@@ -3,7 +3,7 @@ parser + API layer do (core/pbrtlex.ll, core/pbrtparse.yy, core/api.cpp:521-1300
 package's C ABI takes -- the same dictionary `blob.load("scene_*.bin")` gives, so `abi.SceneHolder(d)`, `abi.params_from_blob(d)`
 and everything downstream work unchanged.
 
-Covered: Film "image" (resolution), Sampler "lowdiscrepancy" (pixelsamples), PixelFilter, SurfaceIntegrator "photonmap" and
+Covered: Film "image" (resolution, cropwindow), Sampler "lowdiscrepancy" (pixelsamples), PixelFilter, SurfaceIntegrator "photonmap" and
 VolumeIntegrator "photonvolume" parameters (incl. what CreatePhotonShooter reads from both, core/photonshooter.cpp:529-548),
 Camera "perspective", the transform directives (Identity, Translate, Scale, Rotate, LookAt, Transform, ConcatTransform,
 TransformBegin/End, AttributeBegin/End, ReverseOrientation), WorldBegin/End, LightSource "point" / "spot" / "distant", Material
@@ -380,6 +380,38 @@ def _read_params(toks, k):
     return ps, k
 
 
+# ------------------------------------------------------------------------------------------------ the film's crop window
+def crop_window(values):
+    """CreateImageFilm's reading of `"float cropwindow" [x0 x1 y0 y1]` (film/image.cpp:254-262): each pair ordered and clamped to
+    [0, 1].  The reference ignores a list that is not four numbers; here that raises, like everything else the front end cannot honour."""
+    v = [float(x) for x in values]
+    if len(v) != 4 or not all(math.isfinite(x) for x in v):
+        raise ValueError("cropwindow takes four finite numbers (x0 x1 y0 y1), got %r" % (list(values),))
+    clamp = lambda x: F(min(max(F(x), F(0)), F(1)))   # noqa: E731
+    return np.array([clamp(min(v[0], v[1])), clamp(max(v[0], v[1])), clamp(min(v[2], v[3])), clamp(max(v[2], v[3]))], F)
+
+
+def film_window(xres, yres, crop):
+    """ImageFilm's film image extent (film/image.cpp:48-51) as [xPixelStart, yPixelStart, xPixelCount, yPixelCount] -- the field
+    order of pvol_film_window.  A crop that starts at 1 puts the reference's one pixel past the frame: refused."""
+    c = np.asarray(crop, F)
+    x0 = int(math.ceil(F(F(xres) * c[0])))
+    nx = max(1, int(math.ceil(F(F(xres) * c[1]))) - x0)
+    y0 = int(math.ceil(F(F(yres) * c[2])))
+    ny = max(1, int(math.ceil(F(F(yres) * c[3]))) - y0)
+    if x0 + nx > xres or y0 + ny > yres:
+        raise ValueError("cropwindow %s leaves the %d x %d frame" % (list(map(float, c)), xres, yres))
+    return np.array([x0, y0, nx, ny], np.int32)
+
+
+def sample_extent(window, xwidth=2.0, ywidth=2.0):
+    """ImageFilm::GetSampleExtent (film/image.cpp:157-166) of a film_window() as [xstart, xend, ystart, yend]: what the sampler covers."""
+    x0, y0, nx, ny = (int(v) for v in window)
+    xw, yw, h = F(xwidth), F(ywidth), F(0.5)
+    return np.array([math.floor(F(F(x0) + h) - xw), math.ceil(F(F(F(x0) + h) + F(nx)) + xw),
+                     math.floor(F(F(y0) + h) - yw), math.ceil(F(F(F(y0) + h) + F(ny)) + yw)], np.int32)
+
+
 # ------------------------------------------------------------------------------------------------ the API layer
 class _Builder:
     def __init__(self):
@@ -388,6 +420,7 @@ class _Builder:
         self.reverse = False
         self.material = ("matte", _Params())
         self.film = [640, 480]
+        self.crop = np.array([0, 1, 0, 1], F)   # CreateImageFilm's default (film/image.cpp:254)
         self.spp = 4
         self.surf = ("photonmap", _Params())
         self.vol = ("photonvolume", _Params())
@@ -553,6 +586,14 @@ def _run(path, b, depth=0):
             if name != "image":
                 raise Unsupported('Film "%s"' % name)
             b.film = [ps.i("xresolution", 640), ps.i("yresolution", 480)]
+            b.crop = np.array([0, 1, 0, 1], F)
+            if "cropwindow" in ps:
+                if ps["cropwindow"][0] != "float":
+                    raise ValueError('%s:%d: cropwindow is a "float" parameter, not "%s"' % (path, line, ps["cropwindow"][0]))
+                try:
+                    b.crop = crop_window(ps["cropwindow"][1])
+                except (TypeError, ValueError) as e:
+                    raise ValueError("%s:%d: %s" % (path, line, e))
         elif word == "Sampler":
             name, ps = named()
             if name != "lowdiscrepancy":
@@ -671,4 +712,8 @@ def load(path):
     d["camera.c2w"] = _mat16(b.camera["c2w"].m)
     d["camera.fov"] = np.array([b.camera["fov"]], F)
     d["film"] = np.array([b.film[0], b.film[1], b.spp], np.int32)
+    # the crop window at the file's own resolution (recompute with film_window / sample_extent when the resolution is overridden)
+    d["film.cropwindow"] = b.crop
+    d["film.window"] = film_window(b.film[0], b.film[1], b.crop)
+    d["film.sample_extent"] = sample_extent(d["film.window"])
     return d

@@ -114,6 +114,17 @@ def lib():
         L.pvol_preprocess_group.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32]
         L.pvol_render_frame_group.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(abi.Camera), C.POINTER(abi.Film), C.POINTER(abi.Sampler),
                                               C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p)]
+        _cam, _film, _win, _smp = C.POINTER(abi.Camera), C.POINTER(abi.Film), C.POINTER(abi.FilmWindow), C.POINTER(abi.Sampler)
+        L.pvol_film_window_from_crop.argtypes = [_film, _f32p, _win]
+        L.pvol_film_sample_extent.argtypes = [_film, _win, C.POINTER(C.c_int32)]
+        L.pvol_render_tasks_window_device.argtypes = [C.c_void_p, _cam, _film, _win, _smp, _u32p, C.c_uint32, C.c_void_p, C.POINTER(abi.RenderDebug),
+                                                      C.c_void_p]
+        L.pvol_film_add_samples_window_device.argtypes = [C.c_void_p, _film, _win, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.pvol_film_resolve_window_device.argtypes = [C.c_void_p, _film, _win, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pvol_render_frame_ranks_window.argtypes = [C.c_void_p, _cam, _film, _win, _smp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        L.pvol_render_frame_group_window.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, _cam, _film, _win, _smp, C.POINTER(C.c_void_p), C.c_void_p,
+                                                     C.POINTER(C.c_void_p)]
         L.pvol_enable_phase_timing.argtypes = [C.c_void_p, C.c_int]
         L.pvol_get_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
         _lib = L
@@ -130,7 +141,10 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_set_surface_integrator", "pvol_enable_phase_timing", "pvol_get_phase_ms",
            "pvol_partition_tasks", "pvol_render_frame_ranks", "pvol_preprocess_blocks",
            "pvol_preprocess_ranks", "pvol_get_exchange_seconds", "pvol_li_many", "pvol_set_li_coalescing",
-           "pvol_get_li_coalescing_stats", "pvol_preprocess_group", "pvol_render_frame_group"]
+           "pvol_get_li_coalescing_stats", "pvol_preprocess_group", "pvol_render_frame_group",
+           "pvol_film_window_from_crop", "pvol_film_sample_extent", "pvol_render_tasks_window_device",
+           "pvol_film_add_samples_window_device", "pvol_film_resolve_window_device", "pvol_render_frame_ranks_window",
+           "pvol_render_frame_group_window"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -156,13 +170,18 @@ def preprocess_group(pvs, n_tasks, block_paths=4096):
     _check(lib().pvol_preprocess_group(_ptrs([pv._h.value for pv in pvs]), len(pvs), n_tasks, block_paths), "pvol_preprocess_group")
 
 
-def render_frame_group(pvs, cam, film, smp, d_pixels, d_rgb, hip_streams=None):
+def render_frame_group(pvs, cam, film, smp, d_pixels, d_rgb, hip_streams=None, window=None):
     """pvol_render_frame_group: one frame over the contexts `pvs`.  d_pixels: one full-frame film per context (device pointers, on
     that context's device), d_rgb on the first context's device (0: no resolve), hip_streams: one per context (None: null streams).
-    Enqueued on hip_streams[0]: synchronise it (or the first context's device) before reading d_pixels[0] / d_rgb."""
+    Enqueued on hip_streams[0]: synchronise it (or the first context's device) before reading d_pixels[0] / d_rgb.
+    window (an abi.FilmWindow): pvol_render_frame_group_window, every film, the sum and d_rgb hold the window's pixels."""
     if len(d_pixels) != len(pvs) or (hip_streams is not None and len(hip_streams) != len(pvs)):
         raise ValueError("render_frame_group: one film (and stream) per context")
     streams = None if hip_streams is None else _ptrs(list(hip_streams))
+    if window is not None:
+        _check(lib().pvol_render_frame_group_window(_ptrs([pv._h.value for pv in pvs]), len(pvs), C.byref(cam), C.byref(film), C.byref(window),
+                                                    C.byref(smp), _ptrs(list(d_pixels)), d_rgb or None, streams), "pvol_render_frame_group_window")
+        return
     _check(lib().pvol_render_frame_group(_ptrs([pv._h.value for pv in pvs]), len(pvs), C.byref(cam), C.byref(film), C.byref(smp),
                                          _ptrs(list(d_pixels)), d_rgb or None, streams), "pvol_render_frame_group")
 
@@ -286,8 +305,13 @@ class PhotonVolume:
         """Raises PvolError(PVOL_E_LIMIT) if a batch enqueued through a device entry point hit a kernel limit."""
         _check(lib().pvol_check_errors(self._h), "pvol_check_errors")
 
-    def render_frame_ranks(self, cam, film, smp, rank, n_ranks, nccl_comm, d_pixels, d_rgb=0, hip_stream=0):
-        """One rank of an N-GPU frame behind the C ABI: partition, render, ncclReduce of the film, resolve on rank 0."""
+    def render_frame_ranks(self, cam, film, smp, rank, n_ranks, nccl_comm, d_pixels, d_rgb=0, hip_stream=0, window=None):
+        """One rank of an N-GPU frame behind the C ABI: partition, render, ncclReduce of the film, resolve on rank 0.
+        window (an abi.FilmWindow): pvol_render_frame_ranks_window, the films hold the window's pixels."""
+        if window is not None:
+            _check(lib().pvol_render_frame_ranks_window(self._h, C.byref(cam), C.byref(film), C.byref(window), C.byref(smp), rank, n_ranks, nccl_comm,
+                                                        d_pixels, d_rgb, hip_stream), "pvol_render_frame_ranks_window")
+            return
         _check(lib().pvol_render_frame_ranks(self._h, C.byref(cam), C.byref(film), C.byref(smp), rank, n_ranks, nccl_comm, d_pixels, d_rgb, hip_stream),
                "pvol_render_frame_ranks")
 
@@ -336,8 +360,15 @@ class PhotonVolume:
                "pvol_li_batch_device")
 
     # ---- tile driver (device pointers are integers, e.g. torch.Tensor.data_ptr())
-    def render_tasks(self, camera, film, sampler, task_ids, d_pixels, debug=None, hip_stream=0):
+    def render_tasks(self, camera, film, sampler, task_ids, d_pixels, debug=None, hip_stream=0, window=None):
+        """window (an abi.FilmWindow): pvol_render_tasks_window_device, d_pixels holds the window's pixels and `sampler` its sample
+        extent (film_sample_extent)."""
         ids = np.ascontiguousarray(task_ids, np.uint32)
+        if window is not None:
+            _check(lib().pvol_render_tasks_window_device(self._h, C.byref(camera), C.byref(film), C.byref(window), C.byref(sampler),
+                                                         ids.ctypes.data_as(_u32p), len(ids), d_pixels, C.byref(debug) if debug is not None else None,
+                                                         hip_stream), "pvol_render_tasks_window_device")
+            return
         _check(lib().pvol_render_tasks_device(self._h, C.byref(camera), C.byref(film), C.byref(sampler), ids.ctypes.data_as(_u32p), len(ids),
                                               d_pixels, C.byref(debug) if debug is not None else None, hip_stream), "pvol_render_tasks_device")
 
@@ -364,11 +395,19 @@ class PhotonVolume:
         _check(lib().pvol_set_surface_integrator(self._h, C.byref(sp), p.ctypes.data_as(_f32p), w.ctypes.data_as(_f32p), a.ctypes.data_as(_f32p), n),
                "pvol_set_surface_integrator")
 
-    def film_add_samples(self, film, d_image_xy, d_xyz, stride, n, d_pixels, hip_stream=0):
+    def film_add_samples(self, film, d_image_xy, d_xyz, stride, n, d_pixels, hip_stream=0, window=None):
+        if window is not None:
+            _check(lib().pvol_film_add_samples_window_device(self._h, C.byref(film), C.byref(window), d_image_xy, d_xyz, stride, n, d_pixels, hip_stream),
+                   "pvol_film_add_samples_window_device")
+            return
         _check(lib().pvol_film_add_samples_device(self._h, C.byref(film), d_image_xy, d_xyz, stride, n, d_pixels, hip_stream),
                "pvol_film_add_samples_device")
 
-    def film_resolve(self, film, d_pixels, d_rgb, hip_stream=0):
+    def film_resolve(self, film, d_pixels, d_rgb, hip_stream=0, window=None):
+        if window is not None:
+            _check(lib().pvol_film_resolve_window_device(self._h, C.byref(film), C.byref(window), d_pixels, d_rgb, hip_stream),
+                   "pvol_film_resolve_window_device")
+            return
         _check(lib().pvol_film_resolve_device(self._h, C.byref(film), d_pixels, d_rgb, hip_stream), "pvol_film_resolve_device")
 
     def li_single(self, ray, mt, mti):
@@ -444,6 +483,25 @@ def sub_window(sampler, task):
     w = (C.c_int32 * 4)()
     lib().pvol_compute_sub_window(C.byref(sampler), task, w)
     return list(w)
+
+
+def film_window_from_crop(film, crop):
+    """pvol_film_window_from_crop: ImageFilm's pixel window of `crop` = (x0, x1, y0, y1) in [0, 1] (film/image.cpp:48-51).
+    Pure host code: needs no GPU."""
+    c = np.ascontiguousarray(crop, np.float32).reshape(-1)
+    if c.size != 4:
+        raise ValueError("cropwindow takes four numbers (x0 x1 y0 y1), got %d" % c.size)
+    w = abi.FilmWindow()
+    _check(lib().pvol_film_window_from_crop(C.byref(film), c.ctypes.data_as(_f32p), C.byref(w)), "pvol_film_window_from_crop")
+    return w
+
+
+def film_sample_extent(film, window=None):
+    """pvol_film_sample_extent: ImageFilm::GetSampleExtent of the window (None: the whole frame) as [x_start, x_end, y_start, y_end].
+    Pure host code: needs no GPU."""
+    e = (C.c_int32 * 4)()
+    _check(lib().pvol_film_sample_extent(C.byref(film), C.byref(window) if window is not None else None, e), "pvol_film_sample_extent")
+    return list(e)
 
 
 def render_sample_count(sampler, task_ids):

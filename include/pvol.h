@@ -216,11 +216,20 @@ typedef struct pvol_camera {     /* PerspectiveCamera (cameras/perspective.cpp:4
     float focal_distance;
 } pvol_camera;
 
-typedef struct pvol_film {       /* ImageFilm with the full-frame crop window (film/image.cpp:37-75) */
+typedef struct pvol_film {       /* ImageFilm (film/image.cpp:37-75); its crop window travels apart, as a pvol_film_window */
     int32_t x_resolution, y_resolution;
     float filter_xwidth, filter_ywidth;              /* Filter::xWidth, yWidth                     */
     float filter_table[PVOL_FILTER_TABLE_SIZE * PVOL_FILTER_TABLE_SIZE];  /* ImageFilm::filterTable */
 } pvol_film;
+
+/* ImageFilm's film image extent (film/image.cpp:48-51): the pixels [x_pixel_start, x_pixel_start + x_pixel_count) x
+ * [y_pixel_start, y_pixel_start + y_pixel_count) of the frame are the ones the film stores (:54), splats into (:86-89, :121) and
+ * writes (:179-219).  Taken by the *_window entry points; a NULL window there is the whole frame (crop 0 1 0 1), which is what
+ * the entry points without a window render.  Valid: starts >= 0, counts > 0, inside the resolution. */
+typedef struct pvol_film_window {
+    int32_t x_pixel_start, y_pixel_start;
+    int32_t x_pixel_count, y_pixel_count;
+} pvol_film_window;
 
 typedef struct pvol_sampler {    /* LDSampler (samplers/lowdiscrepancy.cpp:40-80) + the Sample layout  */
     int32_t x_start, x_end, y_start, y_end;          /* Film::GetSampleExtent (film/image.cpp:157-166) */
@@ -541,6 +550,49 @@ int pvol_film_add_samples_device(pvol_ctx *ctx, const pvol_film *film, const flo
 /* ImageFilm::WriteRGB (film/image.cpp:178-214) without splats: d_rgb gets 3 floats per pixel. */
 int pvol_film_resolve_device(pvol_ctx *ctx, const pvol_film *film, const float *d_pixels, float *d_rgb,
                              void *hip_stream);
+
+/* ---- crop window: Film "image" `"float cropwindow" [x0 x1 y0 y1]` (CreateImageFilm, film/image.cpp:254-264) ----
+ * A crop render is not a cut-out of the full render: the window moves Film::GetSampleExtent, so Sampler::ComputeSubWindow deals
+ * different tiles and every task's MT19937 stream covers different pixels.  The window goes to the film (below), its sample extent
+ * into pvol_sampler.x_start .. y_end; the camera and the film's resolution stay those of the whole frame. */
+
+/* ImageFilm's constructor (film/image.cpp:48-51): x_pixel_start = Ceil2Int(xRes * crop[0]), x_pixel_count =
+ * max(1, Ceil2Int(xRes * crop[1]) - x_pixel_start), the same in y with crop[2], crop[3].  Host code, no GPU needed.
+ * PVOL_E_INVALID: a NULL argument, a crop value outside [0, 1] (or NaN), crop[0] > crop[1] or crop[2] > crop[3] (CreateImageFilm
+ * clamps and orders them first, :258-261), or a window that leaves the resolution (a crop that starts at 1). */
+int pvol_film_window_from_crop(const pvol_film *film, const float *crop4, pvol_film_window *out);
+
+/* ImageFilm::GetSampleExtent (film/image.cpp:157-166) of the window (NULL: the whole frame): out = x_start, x_end, y_start, y_end
+ * for pvol_sampler.  Host code.  PVOL_E_INVALID: a NULL film or out, an invalid window. */
+int pvol_film_sample_extent(const pvol_film *film, const pvol_film_window *window, int32_t out[4]);
+
+/* pvol_render_tasks_device into a film that holds the window's pixels only: d_pixels has x_pixel_count * y_pixel_count * 4 floats,
+ * row-major over the window.  A sample's footprint is clamped to the window and addressed relative to it (film/image.cpp:86-89,
+ * :121): samples in the filter apron outside the window add to the pixels inside, a sample whose clamped footprint is empty adds
+ * nothing but is rendered and draws like any other.  `sampler` carries the sample extent (pvol_film_sample_extent): the tasks'
+ * sub-windows, the debug records and pvol_render_sample_count follow it, and a task whose sub-window is empty (more tasks than
+ * the extent has columns; GetSubSampler returns NULL, samplers/lowdiscrepancy.cpp:61-66) renders nothing and draws nothing
+ * (end_draw 0).  PVOL_E_INVALID for an invalid window, otherwise as pvol_render_tasks_device. */
+int pvol_render_tasks_window_device(pvol_ctx *ctx, const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window,
+                                    const pvol_sampler *sampler, const uint32_t *task_ids, uint32_t n_task_ids,
+                                    float *d_pixels, const pvol_render_debug *debug, void *hip_stream);
+
+/* pvol_film_add_samples_device / pvol_film_resolve_device over the window's pixels (ImageFilm::AddSample, WriteRGB with
+ * nPix = xPixelCount * yPixelCount, film/image.cpp:179): d_pixels 4, d_rgb 3 floats per pixel of the window. */
+int pvol_film_add_samples_window_device(pvol_ctx *ctx, const pvol_film *film, const pvol_film_window *window, const float *d_image_xy,
+                                        const float *d_xyz, uint32_t xyz_stride, uint64_t n, float *d_pixels, void *hip_stream);
+int pvol_film_resolve_window_device(pvol_ctx *ctx, const pvol_film *film, const pvol_film_window *window, const float *d_pixels,
+                                    float *d_rgb, void *hip_stream);
+
+/* pvol_render_frame_ranks / pvol_render_frame_group with window-sized films: what is zeroed, reduced (ncclReduce; the staging buffer
+ * and the sum of the group), and resolved is x_pixel_count * y_pixel_count pixels.  The tasks are dealt as before
+ * (pvol_partition_tasks): which stream renders which pixel does not depend on the number of GPUs. */
+int pvol_render_frame_ranks_window(pvol_ctx *ctx, const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window,
+                                   const pvol_sampler *sampler, uint32_t rank, uint32_t n_ranks, void *nccl_comm, float *d_pixels,
+                                   float *d_rgb, void *hip_stream);
+int pvol_render_frame_group_window(pvol_ctx *const *ctxs, uint32_t n_ctx, const pvol_camera *camera, const pvol_film *film,
+                                   const pvol_film_window *window, const pvol_sampler *sampler, float *const *d_pixels, float *d_rgb,
+                                   void *const *hip_streams);
 
 #ifdef __cplusplus
 }

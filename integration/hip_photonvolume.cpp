@@ -173,15 +173,17 @@ public:
     // One rank of a multi-GPU render (north_star: pixel tiles partitioned over the GPUs of one node, one RCCL reduce of the film):
     // what a renderer calls on rank `rank` of `nRanks` INSTEAD of SamplerRenderer::Render's task loop, after every rank ran
     // Preprocess (same seeds: identical photon maps, nothing to exchange) or SetScene + PreprocessRanks (the shoot shared).  `ncclComm` is the caller's ncclComm_t (ncclCommInitRank);
-    // dPixels / dRgb are buffers on this rank's device; rank 0 ends up with the resolved frame.
+    // dPixels / dRgb are buffers on this rank's device, sized by the film's crop window like RenderTasks'; rank 0 ends up with the
+    // resolved image of the window.
     int RenderFrameRanks(const PerspectiveCamera *camera, const ImageFilm *film, const LDSampler *sampler, const Sample *origSample,
                          int nTasks, int rank, int nRanks, void *ncclComm, float *dPixels, float *dRgb, void *hipStream) const {
         pvol_camera cam;
         pvol_film f;
+        pvol_film_window win;
         pvol_sampler smp;
-        int rc = fillTileArgs(camera, film, sampler, origSample, nTasks, &cam, &f, &smp);
+        int rc = fillTileArgs(camera, film, sampler, origSample, nTasks, &cam, &f, &win, &smp);
         if (rc != PVOL_OK) return rc;
-        return pvol_render_frame_ranks(ctx, &cam, &f, &smp, (uint32_t)rank, (uint32_t)nRanks, ncclComm, dPixels, dRgb, hipStream);
+        return pvol_render_frame_ranks_window(ctx, &cam, &f, &win, &smp, (uint32_t)rank, (uint32_t)nRanks, ncclComm, dPixels, dRgb, hipStream);
     }
 
     pvol_ctx *context() const { return ctx; }
@@ -190,29 +192,33 @@ public:
 
     // Tile driver (include/pvol.h): what a renderer calls INSTEAD of enqueueing SamplerRendererTasks
     // (renderers/samplerrenderer.cpp:206-221) when the camera is a pinhole PerspectiveCamera, the film an ImageFilm, the
-    // sampler an LDSampler and the surface integrator contributes nothing.  d_pixels / d_rgb are device buffers
-    // (x*y*4 and x*y*3 floats, d_pixels zeroed); the resolved RGB then goes through ::WriteImage as before.
+    // sampler an LDSampler and the surface integrator contributes nothing.  The film's crop window is honoured: the window is
+    // film->GetPixelExtent, the sample extent film->GetSampleExtent (film/image.cpp:157-175), and d_pixels / d_rgb are device
+    // buffers of xPixelCount*yPixelCount*4 and *3 floats (d_pixels zeroed) -- x*y for a film without a cropwindow; the resolved
+    // RGB then goes through ::WriteImage with the window's size and offset as ImageFilm::WriteImage passes them (:218-219).
     int RenderTasks(const PerspectiveCamera *camera, const ImageFilm *film, const LDSampler *sampler, const Sample *origSample,
                     int nTasks, float *d_pixels, float *d_rgb, void *hipStream, const std::vector<uint32_t> *taskList = NULL) const {
         pvol_camera cam;
         pvol_film f;
+        pvol_film_window win;
         pvol_sampler smp;
         {
-            int rc0 = fillTileArgs(camera, film, sampler, origSample, nTasks, &cam, &f, &smp);
+            int rc0 = fillTileArgs(camera, film, sampler, origSample, nTasks, &cam, &f, &win, &smp);
             if (rc0 != PVOL_OK) return rc0;
         }
         std::vector<uint32_t> tasks;   // all of them, or the caller's share (one rank of a multi-GPU render)
         if (taskList) tasks = *taskList;
         else for (int t = 0; t < nTasks; ++t) tasks.push_back(t);
-        int rc = pvol_render_tasks_device(ctx, &cam, &f, &smp, tasks.empty() ? NULL : &tasks[0], (uint32_t)tasks.size(), d_pixels, NULL, hipStream);
-        if (rc == PVOL_OK) rc = pvol_film_resolve_device(ctx, &f, d_pixels, d_rgb, hipStream);
+        int rc = pvol_render_tasks_window_device(ctx, &cam, &f, &win, &smp, tasks.empty() ? NULL : &tasks[0], (uint32_t)tasks.size(), d_pixels, NULL,
+                                                 hipStream);
+        if (rc == PVOL_OK) rc = pvol_film_resolve_window_device(ctx, &f, &win, d_pixels, d_rgb, hipStream);
         return rc;
     }
 
 private:
     // PerspectiveCamera / ImageFilm / LDSampler / Sample -> the PODs of include/pvol.h
     int fillTileArgs(const PerspectiveCamera *camera, const ImageFilm *film, const LDSampler *sampler, const Sample *origSample, int nTasks,
-                     pvol_camera *pcam, pvol_film *pf, pvol_sampler *psmp) const {
+                     pvol_camera *pcam, pvol_film *pf, pvol_film_window *pwin, pvol_sampler *psmp) const {
         pvol_camera &cam = *pcam;
         pvol_film &f = *pf;
         pvol_sampler &smp = *psmp;
@@ -225,6 +231,12 @@ private:
         f.x_resolution = film->xResolution; f.y_resolution = film->yResolution;
         f.filter_xwidth = film->filter->xWidth; f.filter_ywidth = film->filter->yWidth;
         memcpy(f.filter_table, film->filterTable, sizeof(f.filter_table));
+        {   // the crop window: ImageFilm::GetPixelExtent (film/image.cpp:169-175)
+            int x0, x1, y0, y1;
+            film->GetPixelExtent(&x0, &x1, &y0, &y1);
+            pwin->x_pixel_start = x0; pwin->y_pixel_start = y0;
+            pwin->x_pixel_count = x1 - x0; pwin->y_pixel_count = y1 - y0;
+        }
         memset(&smp, 0, sizeof(smp));
         film->GetSampleExtent(&smp.x_start, &smp.x_end, &smp.y_start, &smp.y_end);
         smp.pixel_samples = sampler->samplesPerPixel;

@@ -3,9 +3,13 @@
 -> SamplerRendererTasks on the device (LD sampler, camera, surface PhotonIntegrator where it applies, PhotonVolumeIntegrator,
 image film) -> RGB.
 
-    python tools/render_pbrt.py SCENE.pbrt OUT.pfm [--xres N --yres N --spp N --photons N --shoot-tasks N --no-surface --devices 0,1,...]
+    python tools/render_pbrt.py SCENE.pbrt OUT.pfm [--xres N --yres N --spp N --photons N --shoot-tasks N --no-surface --devices 0,1,...
+                                                    --cropwindow X0 X1 Y0 Y1]
 
-The file's own Film / Sampler / integrator parameters are used unless overridden.  The surface integrator (direct lighting +
+The file's own Film / Sampler / integrator parameters are used unless overridden.  A crop window (the file's `"float cropwindow"`
+or --cropwindow, fractions of the frame as in the reference's ImageFilm) renders only that part: the image and the PFM have the
+window's size, info["window"] says where it lies; the sampler then covers the window's own sample extent, so the tiles and their
+random streams are those of the reference's crop render, not a cut-out of the full frame's.  The surface integrator (direct lighting +
 caustic estimate on matte surfaces) is switched on when the scene asks for "photonmap" and the device path
 covers it (matte and glass surfaces -- the specular recursion included --, a homogeneous or rainbow medium at any nused and
 phase function, or no medium; no indirect map); otherwise (a VolumeGrid, an indirect map) Ls = 0 and the image holds the
@@ -23,8 +27,11 @@ sys.path.insert(0, ROOT)
 
 
 def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_tasks=2048, surface=True, log=print, caustic_photons=None,
-                      devices=None):
-    """devices: None renders on one context (params.device 0); a list of HIP device ordinals (repeats allowed: [0, 0] runs the
+                      devices=None, cropwindow=None, phases=False):
+    """cropwindow: (x0, x1, y0, y1) overrides the file's; None keeps it (the whole frame when the file names none).
+    phases: info["phase_ms"] gets the first context's device milliseconds per phase of the frame (tile pre-pass, march + gather,
+    surface, film) from HIP events, which serialise the phases a little: not for the frame's own timing.
+    devices: None renders on one context (params.device 0); a list of HIP device ordinals (repeats allowed: [0, 0] runs the
     two-context protocol on one GPU) makes one context per entry, shoots with preprocess_group and renders with render_frame_group,
     whose render_s then includes the film reduce and the resolve."""
     import torch
@@ -80,21 +87,33 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
         cam = abi.perspective_camera(float(scene["camera.fov"][0]), xres, yres, scene["camera.c2w"])
         film = abi.make_film(xres, yres, pvol.gaussian_filter_table())
         smp = abi.make_sampler(xres, yres, spp, n_tiles)
+        # ImageFilm's window of the crop at the resolution rendered, and the sample extent that goes with it (film/image.cpp:48-51,
+        # :157-166); the whole frame keeps the entry points without a window
+        crop = ps.crop_window(cropwindow) if cropwindow is not None else scene["film.cropwindow"]
+        win = pvol.film_window_from_crop(film, crop)
+        if (win.x_pixel_start, win.y_pixel_start, win.x_pixel_count, win.y_pixel_count) == (0, 0, xres, yres):
+            win = None
+        else:
+            abi.set_sample_extent(smp, pvol.film_sample_extent(film, win))
+        wx, wy = (win.x_pixel_count, win.y_pixel_count) if win is not None else (xres, yres)
         ids = np.arange(n_tiles, dtype=np.uint32)
         devs = [torch.device("cuda:%d" % d) for d in devices] if group else [torch.device("cuda:0")]
-        pxs = [torch.zeros((yres, xres, 4), dtype=torch.float32, device=d) for d in devs]
+        pxs = [torch.zeros((wy, wx, 4), dtype=torch.float32, device=d) for d in devs]
         px = pxs[0]
-        rgb = torch.zeros((yres, xres, 3), dtype=torch.float32, device=devs[0])
+        rgb = torch.zeros((wy, wx, 3), dtype=torch.float32, device=devs[0])
         for d in sorted(set(devs), key=str):
             torch.cuda.synchronize(d)
 
         def frame():   # the group call zeroes its films, reduces them on the first context's device and resolves there
             if group:
-                pvol.render_frame_group(pvs, cam, film, smp, [x.data_ptr() for x in pxs], rgb.data_ptr())
+                pvol.render_frame_group(pvs, cam, film, smp, [x.data_ptr() for x in pxs], rgb.data_ptr(), window=win)
                 torch.cuda.synchronize(devs[0])   # covers every context's device
             else:
-                pv.render_tasks(cam, film, smp, ids, px.data_ptr())
+                pv.render_tasks(cam, film, smp, ids, px.data_ptr(), window=win)
                 torch.cuda.synchronize()
+        if phases:
+            pv.enable_phase_timing(True)
+            pv.phase_ms(reset=True)
         t0 = time.perf_counter()
         try:
             frame()
@@ -110,7 +129,7 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
             frame()
         render_s = time.perf_counter() - t0
         if not group:
-            pv.film_resolve(film, px.data_ptr(), rgb.data_ptr())
+            pv.film_resolve(film, px.data_ptr(), rgb.data_ptr(), window=win)
             torch.cuda.synchronize()
         for q in pvs:
             q.check_errors()
@@ -118,6 +137,10 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
                 "photons": int(st["stored_volume"]), "caustic_photons": int(st["stored_caustic"]), "render_s": render_s}
         if group:
             info["devices"] = devices
+        if phases:
+            info["phase_ms"] = pv.phase_ms()
+        if win is not None:   # xPixelStart, yPixelStart, xPixelCount, yPixelCount
+            info["window"] = [win.x_pixel_start, win.y_pixel_start, wx, wy]
         return rgb.cpu().numpy(), info
     finally:
         for q in pvs:
@@ -143,8 +166,11 @@ if __name__ == "__main__":
     ap.add_argument("--no-surface", action="store_true")
     ap.add_argument("--devices", help="comma-separated HIP device ordinals, one context each (repeats allowed, e.g. 0,0); "
                                       "default: one context on device 0")
+    ap.add_argument("--cropwindow", type=float, nargs=4, metavar=("X0", "X1", "Y0", "Y1"),
+                    help="render this part of the frame only (fractions of the frame, as Film \"float cropwindow\"); overrides the file's")
+    ap.add_argument("--phases", action="store_true", help="also report device milliseconds per phase of the frame")
     a = ap.parse_args()
     devices = [int(d) for d in a.devices.split(",")] if a.devices else None
-    img, info = render_scene_file(a.scene, a.xres, a.yres, a.spp, a.photons, a.shoot_tasks, not a.no_surface, devices=devices)
+    img, info = render_scene_file(a.scene, a.xres, a.yres, a.spp, a.photons, a.shoot_tasks, not a.no_surface, devices=devices, cropwindow=a.cropwindow, phases=a.phases)
     write_pfm(a.out, img)
     print(info, "mean rgb", img.mean(axis=(0, 1)))
