@@ -128,14 +128,7 @@ void pvol_destroy(pvol_ctx *c) {
     pvol_free_photons(c);
     pvol_free_surface_stores(c);
     pvol_free_caustic_map(c);
-    if (c->dTau) hipFree(c->dTau);
-    if (c->dSegRays) hipFree(c->dSegRays);
-    if (c->dSegInfo) hipFree(c->dSegInfo);
-    if (c->dSegOut) hipFree(c->dSegOut);
-    if (c->dSegRecords) hipFree(c->dSegRecords);
-    if (c->dSegCounter) hipFree(c->dSegCounter);
-    if (c->dSegStream) hipFree(c->dSegStream);
-    if (c->dSpecLink) hipFree(c->dSpecLink);
+    for (DevBuf &b : c->buf) if (b.p) hipFree(b.p);
     pvol_free_li_staging(c);
     for (auto &p : c->pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     for (auto &p : c->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -144,13 +137,8 @@ void pvol_destroy(pvol_ctx *c) {
     if (c->dDensity) hipFree(c->dDensity);
     if (c->dBvhNodes) hipFree(c->dBvhNodes);
     if (c->dBvhTris) hipFree(c->dBvhTris);
-    if (c->dRecords) hipFree(c->dRecords);
-    if (c->dState) hipFree(c->dState);
-    if (c->dDefer) hipFree(c->dDefer);
-    for (int i = 0; i < 6; ++i) if (c->dTile[i]) hipFree(c->dTile[i]);
     if (c->groupFilmEv) hipEventDestroy(c->groupFilmEv);
     if (c->groupStageEv) hipEventDestroy(c->groupStageEv);
-    if (c->dGroupStage) hipFree(c->dGroupStage);
     if (c->ds) hipFree(c->ds);
     if (c->dsh) hipFree(c->dsh);
     if (c->dCounters) hipFree(c->dCounters);
@@ -645,18 +633,126 @@ int pvol_download_photons(pvol_ctx *c, float *p, float *wi, float *alpha, uint32
     return good ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
-// LDS plans of the two kernels (pvol_march.hip)
-static size_t lds_bytes_seq(const pvol_ctx *c) { return 624 * 4 + (size_t)c->hs.candCap * 8 + (size_t)c->hs.maxSteps * 4 + 256 * 4 + 1024 * 4; }
-static size_t lds_bytes_par(const pvol_ctx *c) { return (size_t)c->hs.candCap * 8 + 256 * 4 + 1024 * 4; }
+// ---- the plan of a batch (pvol_host.h): no HIP call, no context, no environment up to pvol_plan_batch
+// bytes of one record slot: header, one byte per march step, and for a VolumeGrid the drawn offsets of every step
+size_t pvol_rec_stride(int maxSteps, bool grid) {
+    const size_t stride = 16 + (size_t)((maxSteps + 15) & ~15) + (grid ? 8 * (size_t)maxSteps : 0);
+    return (stride + 15) & ~(size_t)15;
+}
 
-// Drawn VALUES cannot reach Li()'s result with at most one light and an analytic tau():
-// such scenes take the ray-parallel kernel, backed by the sequential one if a ray reaches the roulette.
-static bool par_eligible(const pvol_ctx *c) { return c->hs.nLights <= 1 && c->hs.volKind != PVOL_VOLUME_GRID; }
+BatchPlan plan_path(const PlanIn &in) {
+    BatchPlan p = {};
+    const bool tile = in.hasTile, grid = in.volKind == PVOL_VOLUME_GRID, homog = in.volKind == PVOL_VOLUME_HOMOGENEOUS;
+    // Drawn VALUES cannot reach Li()'s result with at most one light and an analytic tau(): such scenes take the
+    // ray-parallel kernel, backed by the sequential one if a ray reaches the roulette.
+    const bool parOk = in.nLights <= 1 && !grid && !in.hasInit;
+    // the tile pre-pass can COUNT Li()'s draws (instead of drawing them) under the same conditions, provided no march step can
+    // reach the roulette
+    const bool tileCount = tile && parOk && !in.roulette;
+    // a VolumeGrid with at most one light: the draw COUNT is still geometry only (4 + 6n + n + u; the drawn offsets change values,
+    // not counts), so the tile pre-pass counts and the values come from the RNG-only resolve pass of each slice
+    const bool tileGridCount = tile && in.nLights <= 1 && grid && !in.hasInit && !in.roulette && !in.forceSeq && !in.noLite;
+    const bool par = parOk && !in.forceSeq && (!tile || tileCount);
+    // scenes where drawn values matter: sequential RESOLVE pre-pass + ray-parallel REPLAY, slice by slice
+    const bool sliced = !par && !in.forceSeq && !in.transOnly && (in.volKind != PVOL_VOLUME_NONE || tile);
+    p.kernel = "li_seq_kernel";
+    p.path = par ? PVOL_PATH_PAR : sliced ? PVOL_PATH_SLICED : PVOL_PATH_SEQ;
+    p.tile = !tile ? PVOL_TILE_NONE : !sliced ? PVOL_TILE_COUNT : tileGridCount ? PVOL_TILE_GRID_COUNT : PVOL_TILE_FUSED;
+    if (p.tile == PVOL_TILE_COUNT && !tileCount) p.rc = PVOL_E_UNSUPPORTED;
+    // *T of a VolumeGrid is a product of stepped taus with drawn offsets: not a TauRec (the surface term is refused there)
+    if (in.hasTauOut && grid) p.rc = PVOL_E_UNSUPPORTED;
+    // li_group_kernel (one ray per lane, gathers of 64 rays share a photon bucket): an isotropic medium with a photon map
+    const bool bucket = !in.noGroup && in.g == 0.f && in.nPhotons > 0 && in.nUsed >= 10;
+    if (par) {   // homogeneous and k <= 64; li_par_kernel (one wave per ray) otherwise
+        p.groupForm = bucket && homog && in.nUsed <= 64 && in.candCap <= 4 * 64;
+        p.kernel = p.groupForm ? "li_group_kernel" : "li_par_kernel";
+    } else if (sliced) {
+        // with a tile pre-pass in FUSED mode (several lights) the flag selects the pre-pass's own geometry + RNG-only form
+        p.liteResolve = !in.noLite && !in.roulette;
+        p.resolve = p.tile == PVOL_TILE_NONE || p.tile == PVOL_TILE_GRID_COUNT;
+        // the replay form where no march step can reach the roulette; li_replay_kernel (one wave per ray) otherwise, and as the gated backup
+        if (bucket && !in.statsOn && !in.roulette && (homog || grid)) p.groupForm = grid ? 2 : 1;
+        p.fixGroup = p.groupForm && in.nUsed > 100 && !in.knobs.fixExact;   // GRP_PLAN_KMAX: see pvol_fixgrp_dev.h
+        p.kernel = p.groupForm ? "li_group_kernel" : "li_replay_kernel";
+        // the FUSED pre-pass walks the segments of the specular recursion (geo_ray + lite_ray)
+        if (in.specOn && !(p.tile == PVOL_TILE_FUSED && p.liteResolve)) p.rc = PVOL_E_UNSUPPORTED;
+    }
+    return p;
+}
 
-static int launch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_stream *dStreams, uint32_t nStreams, int outputKind,
-                  float *dOut, uint32_t *dDraws, const uint32_t *dInit, uint32_t *dFinal, int transOnly, uint32_t maxRaysPerStream,
-                  hipStream_t stream) {
-    return pvol_launch_batch(c, dRays, nRays, dStreams, nStreams, outputKind, dOut, dDraws, dInit, dFinal, transOnly, maxRaysPerStream, 0, stream);
+// Waves per render task of the COUNT-mode tile pre-pass.  A task is a serial chain (one MT19937 stream); with many tasks per CU
+// the chip is kept busy by running them side by side (one wave each), with few -- one rank's share of a multi-GPU frame -- the
+// draw count of every pixel is spread over several waves instead (tile_mw_kernel).  PVOL_TILE_WAVES overrides.
+static int tile_waves_per_task(const PlanIn &in) {
+    if (in.tileWaves > 0) return in.tileWaves;
+    // measured on the C2 frame (tools/cmp_mt.sh, profiles/r03_tile_waves.txt): 16 tasks per CU 231 ms with one wave against 345 with two, 8 per CU
+    // 210 with one, 210 with two, 270 with eight; 4 per CU 198 with one, 132 with two, 144 with eight; 2 per CU 194 against 86 with eight
+    const double perCU = (double)in.nStreams / (double)std::max(1, in.nCU);
+    // (second pass, with the multi-wave kernels held to two waves per SIMD -- 256 VGPRs, so that the workgroups of ALL a CU's tasks are resident:
+    // 4 per CU 77 ms with two waves (134 before), 99 with four; 2 per CU 56.5 ms with four waves, 80.8 with eight at 128 VGPRs, 85.9 at 256)
+    // 8 per CU: 131.5 ms with two waves, 146.9 with one; 16 per CU: 174.7 with one, 190.7 with two
+    return perCU >= 12.0 ? 1 : (perCU >= 3.0 ? 2 : 4);
+}
+
+void plan_size(const PlanIn &in, BatchPlan &p) {
+    typedef unsigned long long ull;
+    const bool slicedPath = p.path == PVOL_PATH_SLICED;
+    // LDS plans of the kernels (pvol_march.hip)
+    p.ldsPar = (size_t)in.candCap * 8 + 256 * 4 + 1024 * 4; p.ldsResolve = 624 * 4 + (size_t)in.maxSteps * 4;
+    p.ldsSeq = p.ldsResolve + p.ldsPar; p.ldsGroup = pvol_group_lds_bytes(in.candCap);
+    if (p.tile == PVOL_TILE_FUSED) { p.ldsTile = pvol_tile_lds_bytes(in.maxSteps, in.spp, true, in.nTris, false); p.tileWavesPerTask = 1; }
+    else if (p.tile != PVOL_TILE_NONE) { p.ldsTile = pvol_tile_lds_bytes(0, in.spp, false, in.nTris, in.distant != 0); p.tileWavesPerTask = tile_waves_per_task(in); }
+    if (slicedPath) {
+        const size_t stride = pvol_rec_stride(in.maxSteps, in.volKind == PVOL_VOLUME_GRID);
+        size_t m = ((size_t)4 << 30) / (stride * (size_t)in.nStreams);   // the record budget
+        // nused beyond the bucket plan hands every dense lookup of a slice to the exact pass: keep that list within 8 GB
+        if (in.nUsed > 100) m = std::min<size_t>(m, std::max<size_t>(64, (((size_t)8 << 30) / sizeof(DeferRec) / 64) / (size_t)in.nStreams));
+        if (in.specOn) m = std::min<size_t>(m, std::max<size_t>(64, ((size_t)8 << 20) / (size_t)in.nStreams));   // keeps a slice's segment pool within its 16 M slots
+        m = std::max<size_t>(64, std::min<size_t>(m, ((size_t)in.maxRays + 63) & ~(size_t)63));
+        m &= ~(size_t)63;
+        if (in.knobs.sliceRays >= 64) m = (size_t)in.knobs.sliceRays & ~(size_t)63;   // testing: force many slices
+        if (in.hasTile) {   // a slice holds whole pixels (both powers of two)
+            const size_t unit = std::max<size_t>(64, in.spp);
+            m = std::max(unit, m / unit * unit);
+        }
+        p.recStride = (uint32_t)stride; p.sliceM = (uint32_t)m;
+        p.nSlices = in.maxRays ? (in.maxRays + p.sliceM - 1) / p.sliceM : 1;
+        p.recBytes = stride * (size_t)in.nStreams * p.sliceM; p.stateBytes = sizeof(uint32_t) * 625 * (size_t)in.nStreams;
+    }
+    // rays one launch marches: the batch, or one slice of every stream
+    const ull chunks = slicedPath ? (ull)((p.sliceM + 63) / 64) * in.nStreams : ((ull)in.nRays + 63ull) / 64ull;
+    const ull gchunks = slicedPath ? (ull)((p.sliceM + 511) / 512) * in.nStreams : ((ull)in.nRays + 511ull) / 512ull;   // GRP_CH rays per chunk
+    const size_t inFlight = slicedPath ? (size_t)p.sliceM * in.nStreams : (size_t)in.nRays;
+    if (p.path != PVOL_PATH_SEQ) p.nWaves = (uint32_t)std::min<ull>(chunks, (ull)in.nCU * 16ull);
+    p.fixWaves = (uint32_t)(in.nCU * in.fixWavesPerCU);
+    if (p.groupForm) {
+        p.gWaves = (uint32_t)std::min<ull>(gchunks, (ull)in.nCU * (ull)in.groupWavesPerCU);
+        // room for the lookups the bucket plan hands over (a fraction of a percent of ~40 per ray on C2); a list that overflows raises needSeq and
+        // the batch is redone, never truncated.  nused beyond the bucket plan sends every dense lookup to the exact pass (C3: ~14 per ray)
+        if (!slicedPath) p.deferWant = inFlight / 2 + 65536;
+        else p.deferWant = std::min<size_t>((in.nUsed > 100 ? inFlight * 64 : inFlight) + 65536, ((size_t)8 << 30) / sizeof(DeferRec));
+    }
+    if (in.specOn) {   // segments of one batch / slice: twice its camera samples, 64 k .. 16 M (the link holds 25 bits)
+        const size_t cap = in.knobs.specPool > 0 ? (size_t)in.knobs.specPool : std::max<size_t>(65536, 2 * inFlight);
+        p.specCap = std::min<size_t>(cap, (size_t)1 << 24);
+    }
+}
+
+void pvol_plan_batch(const PlanIn *in, BatchPlan *out) {
+    *out = plan_path(*in);
+    if (out->rc == PVOL_OK) plan_size(*in, *out);
+}
+
+LaunchKnobs pvol_read_knobs() {
+    auto num = [](const char *name) { const char *v = getenv(name); return v ? (int64_t)atoll(v) : (int64_t)0; };
+    auto real = [](const char *name) { const char *v = getenv(name); return v ? (float)atof(v) : 0.f; };
+    LaunchKnobs k;
+    k.sliceRays = num("PVOL_SLICE_RAYS"); k.specPool = num("PVOL_SPEC_POOL"); k.tileBatchRays = num("PVOL_TILE_BATCH_RAYS");
+    // li_group_kernel bucket radius^2 = this x the guessed k-th distance^2 (measured at 64 spp: 1.3 55.5, 1.2 57.5, 1.12 58.0,
+    // 1.06 56.6, 1.0 51.0 Msamples/s)
+    k.groupGuess = real("PVOL_GROUP_GUESS"); if (!(k.groupGuess >= 1.f)) k.groupGuess = 1.15f;
+    k.fxgWiden = real("PVOL_FXG_WIDEN"); k.fxgAim = real("PVOL_FXG_AIM"); k.fixExact = getenv("PVOL_FIX_EXACT") != 0;
+    return k;
 }
 
 // Whether a single march step can reach the Russian roulette (Tr.y() < 1e-3, photonvolume.cpp:156-161): Tr is
@@ -668,6 +764,29 @@ static bool roulette_possible(const pvol_ctx *c) {
     // stepSize/2, DensityRegion::tau) can overshoot the segment by one sample: 1.5 x stepSize bounds it
     const float dens = c->hs.volKind == PVOL_VOLUME_GRID ? 1.5f * c->maxDensity : 1.f;
     return !(c->hs.stepSize * m * dens < 6.8f);
+}
+
+static PlanIn plan_input(const pvol_ctx *c, const BatchArgs &b) {
+    const DevScene &h = c->hs;
+    PlanIn in = {};
+    in.nLights = h.nLights; in.volKind = h.volKind; in.g = h.g; in.nPhotons = h.nPhotons; in.nUsed = h.nUsed; in.candCap = h.candCap;
+    in.maxSteps = h.maxSteps; in.nTris = h.nTris; in.roulette = roulette_possible(c); in.distant = h.nLights > 0 && h.lights[0].kind == PVOL_LIGHT_DISTANT;
+    in.forceSeq = c->forceSeq; in.noGroup = c->noGroup; in.noLite = c->noLite; in.statsOn = c->statsOn;
+    in.nCU = c->nCU; in.groupWavesPerCU = c->groupWavesPerCU; in.fixWavesPerCU = c->fixWavesPerCU; in.tileWaves = c->tileWaves;
+    in.nRays = b.nRays; in.nStreams = b.nStreams; in.maxRays = b.maxRaysPerStream; in.hasInit = b.initState != 0; in.transOnly = b.transOnly != 0; in.hasTile = b.tile != 0;
+    in.spp = b.tile ? b.tile->spp : 0; in.specOn = b.tile && b.tile->specOn; in.hasTauOut = b.tauOut != 0;
+    in.knobs = pvol_read_knobs();
+    return in;
+}
+
+bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream) {
+    if (want <= b.bytes) return true;
+    hipStreamSynchronize(stream);   // an earlier batch may still read the old buffer
+    if (b.p) hipFree(b.p);
+    b.p = 0; b.bytes = 0;
+    if (!ok(hipMalloc(&b.p, want))) { b.p = 0; return false; }
+    b.bytes = want;
+    return true;
 }
 
 // Timing events: every batch records a pair on its launch stream.  Finished pairs are folded into the running sum and
@@ -697,7 +816,7 @@ static bool harvest_events(pvol_ctx *c, bool wait) {
 }
 
 // Orders `stream` behind every batch of this context still running on another stream (their end events): the device entry
-// points return with their kernels in flight, and those kernels use the context's scratch (dWords, dRecords, dState, dDefer).
+// points return with their kernels in flight, and those kernels use the context's scratch (dWords and `buf`).
 int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream) {
     std::lock_guard<std::mutex> g(c->mu);
     harvest_events(c, false);
@@ -717,101 +836,107 @@ void pvol_phase_mark(pvol_ctx *c, hipStream_t stream, int id) {
     c->phaseMarks.push_back(std::make_pair(id, e));
 }
 
-// Waves per render task of the COUNT-mode tile pre-pass.  A task is a serial chain (one MT19937 stream); with many tasks per CU
-// the chip is kept busy by running them side by side (one wave each), with few -- one rank's share of a multi-GPU frame -- the
-// draw count of every pixel is spread over several waves instead (tile_mw_kernel).  PVOL_TILE_WAVES overrides.
-static int tile_waves_per_task(const pvol_ctx *c, uint32_t nTasks) {
-    if (c->tileWaves > 0) return c->tileWaves;
-    // measured on the C2 frame (tools/cmp_mt.sh, profiles/r03_tile_waves.txt): 16 tasks per CU 231 ms with one wave against 345 with two,
-    // 8 per CU 210 with one, 210 with two, 270 with eight; 4 per CU 198 with one, 132 with two, 144 with eight; 2 per CU 194 against 86
-    // with eight
-    const double perCU = (double)nTasks / (double)std::max(1, c->nCU);
-    // (second pass, with the multi-wave kernels held to two waves per SIMD -- 256 VGPRs, so that the workgroups of ALL a CU's tasks are resident:
-    // 4 per CU 77 ms with two waves (134 before), 99 with four; 2 per CU 56.5 ms with four waves, 80.8 with eight at 128 VGPRs, 85.9 at 256)
-    // 8 per CU: 131.5 ms with two waves, 146.9 with one; 16 per CU: 174.7 with one, 190.7 with two
-    return perCU >= 12.0 ? 1 : (perCU >= 3.0 ? 2 : 4);
-}
-
-// ---- specular recursion (pvol_spec_dev.h): the pool of segment rays of one batch (COUNT mode) or one slice (FUSED mode)
-static int spec_pool_prepare(pvol_ctx *c, size_t cap, size_t recStride, hipStream_t stream) {
-    if (cap > c->segCap) {
-        hipStreamSynchronize(stream);
-        if (c->dSegRays) hipFree(c->dSegRays);
-        if (c->dSegInfo) hipFree(c->dSegInfo);
-        if (c->dSegOut) hipFree(c->dSegOut);
-        c->dSegRays = 0; c->dSegInfo = 0; c->dSegOut = 0; c->segCap = 0;
-        if (!ok(hipMalloc(&c->dSegRays, sizeof(pvol_ray) * cap)) || !ok(hipMalloc(&c->dSegInfo, sizeof(SegInfo) * cap)) ||
-            !ok(hipMalloc(&c->dSegOut, sizeof(float) * 60 * cap))) return PVOL_E_NO_MEMORY;
-        c->segCap = cap;
-    }
-    if (recStride * cap > c->segRecBytes) {
-        hipStreamSynchronize(stream);
-        if (c->dSegRecords) hipFree(c->dSegRecords);
-        c->dSegRecords = 0; c->segRecBytes = 0;
-        if (!ok(hipMalloc(&c->dSegRecords, recStride * cap))) return PVOL_E_NO_MEMORY;
-        c->segRecBytes = recStride * cap;
-    }
-    if (!c->dSegCounter && !ok(hipMalloc(&c->dSegCounter, 16))) return PVOL_E_NO_MEMORY;
-    if (!c->dSegStream && !ok(hipMalloc(&c->dSegStream, sizeof(pvol_stream)))) return PVOL_E_NO_MEMORY;
-    memset(&c->hSegStream, 0, sizeof(pvol_stream));
-    c->hSegStream.n_rays = (uint32_t)cap;
-    if (!ok(hipMemsetAsync(c->dSegCounter, 0, 16, stream)) || !ok(hipMemcpyAsync(c->dSegStream, &c->hSegStream, sizeof(pvol_stream), hipMemcpyHostToDevice, stream)) ||
-        !ok(pvol_launch_spec_fill(c->dSegRays, (uint32_t)cap, stream)) || !ok(hipMemsetAsync(c->dSegOut, 0, sizeof(float) * 60 * cap, stream)))
+// ---- specular recursion (pvol_spec_dev.h): the pool of segment rays of one batch (COUNT mode) or one slice (FUSED mode).
+// Emptied in front of every tile pre-pass that fills it, and handed to that pre-pass through its TileArgs.
+static int spec_pool_reset(pvol_ctx *c, TileArgs *t, size_t cap, hipStream_t stream) {
+    memset(&c->hSegStream, 0, sizeof(pvol_stream)); c->hSegStream.n_rays = (uint32_t)cap;
+    pvol_ray *segRays = pvol_buf<pvol_ray>(c, PVOL_BUF_SEG_RAYS);
+    uint32_t *segCounter = pvol_buf<uint32_t>(c, PVOL_BUF_SEG_COUNTER);
+    if (!ok(hipMemsetAsync(segCounter, 0, 16, stream)) || !ok(hipMemcpyAsync(c->buf[PVOL_BUF_SEG_STREAM].p, &c->hSegStream, sizeof(pvol_stream), hipMemcpyHostToDevice, stream)) ||
+        !ok(pvol_launch_spec_fill(segRays, (uint32_t)cap, stream)) || !ok(hipMemsetAsync(c->buf[PVOL_BUF_SEG_OUT].p, 0, sizeof(float) * 60 * cap, stream)))
         return PVOL_E_NO_DEVICE;
+    t->specOn = 1; t->segRays = segRays; t->segInfo = pvol_buf<SegInfo>(c, PVOL_BUF_SEG_INFO); t->segCounter = segCounter; t->segCap = (uint32_t)cap;
+    t->segRecords = pvol_buf<unsigned char>(c, PVOL_BUF_SEG_RECORDS);
     return PVOL_OK;
-}
-static size_t spec_pool_cap(size_t raysInFlight) {   // segments of one batch / slice: twice its camera samples, 64 k .. 16 M (the link holds 25 bits)
-    size_t cap = std::max<size_t>(65536, 2 * raysInFlight);
-    if (const char *ev = getenv("PVOL_SPEC_POOL")) { long long v = atoll(ev); if (v > 0) cap = (size_t)v; }
-    return std::min<size_t>(cap, (size_t)1 << 24);
-}
-static void spec_fill_tile(const pvol_ctx *c, TileArgs *t, size_t cap) {
-    t->specOn = 1; t->segRays = c->dSegRays; t->segInfo = c->dSegInfo; t->segCounter = c->dSegCounter; t->segCap = (uint32_t)cap;
-    t->segRecords = c->dSegRecords;
 }
 // The segments' own volume Li() (spectral), the surface term at their matte hits, and the fold into the camera samples.
 // `replay`: the pool's records were written by the FUSED tile pre-pass (li_replay_kernel); else no drawn value matters (li_par_kernel).
-static int spec_finish(pvol_ctx *c, const LiArgs &a, size_t cap, bool replay, uint32_t nPrimary, float *primaryOut, float *surfOut, hipStream_t stream) {
+static int spec_finish(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, const LiArgs &a, bool replay) {
+    const size_t cap = p.specCap;
+    pvol_ray *segRays = pvol_buf<pvol_ray>(c, PVOL_BUF_SEG_RAYS);
+    float *segOut = pvol_buf<float>(c, PVOL_BUF_SEG_OUT);
     LiArgs sa = a;
-    sa.rays = c->dSegRays; sa.nRays = (uint32_t)cap; sa.streams = c->dSegStream; sa.nStreams = 1; sa.outputKind = PVOL_OUT_SPECTRAL;
-    sa.out = c->dSegOut; sa.draws = 0; sa.initState = 0; sa.finalState = 0; sa.tauOut = 0; sa.defer = 0; sa.deferCount = 0; sa.deferCap = 0; sa.gated = 0;
-    sa.records = c->dSegRecords; sa.sliceM = (uint32_t)cap; sa.sliceK = 0; sa.state = 0; sa.status = 0;
+    sa.rays = segRays; sa.nRays = (uint32_t)cap; sa.streams = pvol_buf<pvol_stream>(c, PVOL_BUF_SEG_STREAM); sa.nStreams = 1; sa.outputKind = PVOL_OUT_SPECTRAL;
+    sa.out = segOut; sa.draws = 0; sa.initState = 0; sa.finalState = 0; sa.tauOut = 0; sa.defer = 0; sa.deferCount = 0; sa.deferCap = 0; sa.gated = 0;
+    sa.records = pvol_buf<unsigned char>(c, PVOL_BUF_SEG_RECORDS); sa.sliceM = (uint32_t)cap; sa.sliceK = 0; sa.state = 0; sa.status = 0;
     const uint32_t nWaves = (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 16ull);
-    if (!ok(hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), stream))) return PVOL_E_NO_DEVICE;
-    hipError_t e = replay ? pvol_launch_li_replay(&sa, lds_bytes_par(c), c->hs.candCap, nWaves, stream)
-                          : pvol_launch_li_par(&sa, lds_bytes_par(c), c->hs.candCap, false, nWaves, stream);
+    if (!ok(hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), b.stream))) return PVOL_E_NO_DEVICE;
+    hipError_t e = replay ? pvol_launch_li_replay(&sa, p.ldsPar, c->hs.candCap, nWaves, b.stream)
+                          : pvol_launch_li_par(&sa, p.ldsPar, c->hs.candCap, false, nWaves, b.stream);
     if (!ok(e)) return PVOL_E_NO_DEVICE;
-    SurfArgs su;
-    memset(&su, 0, sizeof(su));
-    su.scene = c->ds; su.rays = c->dSegRays; su.nRays = (uint32_t)cap; su.out = c->dSegOut; su.tau = 0; su.surfOut = 0; su.counters = c->dCounters; su.link = 0; su.spectral = 1;
-    if (!ok(pvol_launch_surface(&su, (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 24ull), stream))) return PVOL_E_NO_DEVICE;
-    SpecComposeArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.scene = c->ds; ca.link = c->dSpecLink; ca.info = c->dSegInfo; ca.segOut = c->dSegOut; ca.tau = a.tauOut; ca.out = primaryOut; ca.surfOut = surfOut;
-    ca.first = 0; ca.nRays = nPrimary;
-    return ok(pvol_launch_spec_compose(&ca, stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    SurfArgs su = {};
+    su.scene = c->ds; su.rays = segRays; su.nRays = (uint32_t)cap; su.out = segOut; su.tau = 0; su.surfOut = 0; su.counters = c->dCounters; su.link = 0; su.spectral = 1;
+    if (!ok(pvol_launch_surface(&su, (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 24ull), b.stream))) return PVOL_E_NO_DEVICE;
+    SpecComposeArgs ca = {};
+    ca.scene = c->ds; ca.link = pvol_buf<uint32_t>(c, PVOL_BUF_SPEC_LINK); ca.info = pvol_buf<SegInfo>(c, PVOL_BUF_SEG_INFO); ca.segOut = segOut; ca.tau = a.tauOut;
+    ca.out = b.out; ca.surfOut = b.specSurfOut; ca.first = 0; ca.nRays = b.nRays;
+    return ok(pvol_launch_spec_compose(&ca, b.stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
-// `tile` != 0: the rays do not exist yet -- the tile kernel (pvol_tile_dev.h) generates them stream by stream
-// (LD sampler + camera) in front of the march, and takes the place of the RESOLVE pre-pass where one is needed.
-int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_stream *dStreams, uint32_t nStreams, int outputKind,
-                      float *dOut, uint32_t *dDraws, const uint32_t *dInit, uint32_t *dFinal, int transOnly, uint32_t maxRaysPerStream,
-                      const TileArgs *tile, hipStream_t stream) {
-    TileArgs tloc;   // the tile driver's arguments, completed here where the batch is cut into slices (segment pool of the specular recursion)
-    if (tile) { tloc = *tile; tile = &tloc; }
-    const bool spec = tile && tloc.specOn;
-    size_t specCap = 0;
-    LiArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene = c->ds; a.rays = dRays; a.streams = dStreams; a.nStreams = nStreams; a.nRays = nRays; a.outputKind = outputKind;
-    a.out = dOut; a.draws = dDraws; a.initState = dInit; a.finalState = dFinal; a.counters = c->dCounters;
-    a.transmittanceOnly = transOnly;
-    a.chunkCounter = c->dWords; a.needSeq = c->dWords + 1; a.gated = 0;
-    a.tauOut = c->dTauNext;   // render driver with the surface integrator on: the march kernels also report every sample's *T
-    a.status = c->dStatusNext;   // coalesced per-sample batch: a PVOL_E_LIMIT fails only its own call
-    // li_group_kernel bucket radius^2 = this x the guessed k-th distance^2 (measured at 64 spp: 1.3 55.5, 1.2 57.5, 1.12 58.0,
-    // 1.06 56.6, 1.0 51.0 Msamples/s)
-    { const char *gs = getenv("PVOL_GROUP_GUESS"); a.grpGuess = gs ? (float)atof(gs) : 1.15f; if (!(a.grpGuess >= 1.f)) a.grpGuess = 1.15f; }
+// ---- the three paths of a batch: each fills what is left of LiArgs and launches, in stream order
+// sampler + camera pre-pass that COUNTs Li()'s draws for the whole batch, once (`t`: the batch as one slice)
+static int run_tile_count(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, const LiArgs &t, const TileArgs *tile) {
+    pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
+    return ok(pvol_launch_tile(&t, tile, false, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+}
+static int run_par(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a) {
+    hipError_t e = p.groupForm ? pvol_launch_li_group(&a, p.ldsGroup, c->hs.candCap, c->statsOn, p.gWaves, p.fixWaves, 0, b.stream)
+                               : pvol_launch_li_par(&a, p.ldsPar, c->hs.candCap, c->statsOn, p.nWaves, b.stream);
+    if (ok(e)) {   // runs only if a ray raised needSeq (gate read on the device: no host sync here)
+        a.gated = 1;
+        e = pvol_launch_li_seq(&a, p.ldsSeq, c->hs.candCap, c->statsOn, b.stream);
+        a.gated = 0;
+    }
+    if (!ok(e)) return PVOL_E_NO_DEVICE;
+    return p.specCap ? spec_finish(c, b, p, a, false) : PVOL_OK;
+}
+
+static int run_sliced(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a, TileArgs *tile) {
+    a.records = pvol_buf<unsigned char>(c, PVOL_BUF_RECORDS); a.recStride = p.recStride; a.sliceM = p.sliceM; a.state = pvol_buf<uint32_t>(c, PVOL_BUF_STATE);
+    a.liteResolve = p.liteResolve; a.fixGroup = p.fixGroup;
+    if (p.tile == PVOL_TILE_GRID_COUNT) {
+        LiArgs t = a;
+        t.sliceK = 0; t.sliceM = 0xffffffc0u; t.state = 0;
+        if (run_tile_count(c, b, p, t, tile) != PVOL_OK) return PVOL_E_NO_DEVICE;
+    }
+    for (uint32_t k = 0; k < p.nSlices; ++k) {
+        a.sliceK = k;
+        hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), b.stream);
+        if (p.specCap && spec_pool_reset(c, tile, p.specCap, b.stream) != PVOL_OK) return PVOL_E_NO_DEVICE;
+        if (p.tile == PVOL_TILE_FUSED) {
+            pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
+            if (!ok(pvol_launch_tile(&a, tile, true, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask))) return PVOL_E_NO_DEVICE;
+        }
+        pvol_phase_mark(c, b.stream, PVOL_PHASE_MARCH);   // incl. the RNG-only resolve pass of a slice where there is one
+        if (!ok(pvol_launch_li_slice(&a, p.ldsResolve, p.ldsPar, c->hs.candCap, c->statsOn, p.nWaves, b.stream, p.resolve != 0, p.groupForm, p.ldsGroup,
+                                     p.gWaves, p.fixWaves))) return PVOL_E_NO_DEVICE;
+        // this slice's segments: their Li() from the records the pre-pass left, then the fold into the slice's camera samples
+        if (p.specCap && spec_finish(c, b, p, a, true) != PVOL_OK) return PVOL_E_NO_DEVICE;
+    }
+    return PVOL_OK;
+}
+
+static int run_seq(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a) {
+    return ok(pvol_launch_li_seq(&a, p.ldsSeq, c->hs.candCap, c->statsOn, b.stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+}
+
+// Scratch of the plan's sizes, all of it before the first enqueue of the batch.
+static int reserve_scratch(pvol_ctx *c, const BatchPlan &p, hipStream_t stream) {
+    const size_t cap = p.specCap;
+    if (!pvol_reserve(c->buf[PVOL_BUF_RECORDS], p.recBytes, stream) || !pvol_reserve(c->buf[PVOL_BUF_STATE], p.stateBytes, stream) ||
+        !pvol_reserve(c->buf[PVOL_BUF_DEFER], p.deferWant * sizeof(DeferRec), stream) ||
+        !pvol_reserve(c->buf[PVOL_BUF_SEG_RAYS], sizeof(pvol_ray) * cap, stream) || !pvol_reserve(c->buf[PVOL_BUF_SEG_INFO], sizeof(SegInfo) * cap, stream) ||
+        !pvol_reserve(c->buf[PVOL_BUF_SEG_OUT], sizeof(float) * 60 * cap, stream) || !pvol_reserve(c->buf[PVOL_BUF_SEG_RECORDS], p.recStride * cap, stream) ||
+        !pvol_reserve(c->buf[PVOL_BUF_SEG_COUNTER], cap ? 16 : 0, stream) || !pvol_reserve(c->buf[PVOL_BUF_SEG_STREAM], cap ? sizeof(pvol_stream) : 0, stream))
+        return PVOL_E_NO_MEMORY;
+    return PVOL_OK;
+}
+
+int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
+    PlanIn in = plan_input(c, b);
+    BatchPlan p = plan_path(in);
+    if (p.rc != PVOL_OK) return p.rc;
+    const hipStream_t stream = b.stream;
     std::pair<hipEvent_t, hipEvent_t> ev;
     {
         std::lock_guard<std::mutex> g(c->mu);
@@ -819,182 +944,50 @@ int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_s
         if (!c->pool.empty()) { ev = c->pool.back(); c->pool.pop_back(); }
         else if (!ok(hipEventCreate(&ev.first)) || !ok(hipEventCreate(&ev.second))) return PVOL_E_NO_DEVICE;
     }
-    // the pair goes back to the pool on every early return below (an UNSUPPORTED batch must not leak events)
+    // the pair goes back to the pool on every early return below (a failed batch must not leak events)
     struct EventReturn {
         pvol_ctx *c; std::pair<hipEvent_t, hipEvent_t> ev; bool keep = false;
         ~EventReturn() { if (!keep) { std::lock_guard<std::mutex> g(c->mu); c->pool.push_back(ev); } }
     } evGuard{c, ev};
-    hipError_t e;
-    // the tile pre-pass can COUNT Li()'s draws (instead of drawing them) under the same conditions as li_par_kernel,
-    // provided no march step can reach the roulette
-    const bool tileCount = tile && par_eligible(c) && !dInit && !roulette_possible(c);
-    // a VolumeGrid with at most one light: the draw COUNT is still geometry only (4 + 6n + n + u; the drawn offsets change values,
-    // not counts), so the tile pre-pass counts and the values come from the RNG-only resolve pass of each slice
-    const bool tileGridCount = tile && c->hs.nLights <= 1 && c->hs.volKind == PVOL_VOLUME_GRID && !dInit && !roulette_possible(c) && !c->forceSeq && !c->noLite;
-    const bool par = par_eligible(c) && !dInit && !c->forceSeq && (!tile || tileCount);
-    // scenes where drawn values matter: sequential RESOLVE pre-pass + ray-parallel REPLAY, slice by slice
-    const bool sliced = !par && !c->forceSeq && !transOnly && (c->hs.volKind != PVOL_VOLUME_NONE || tile);
-    if (tile && !par && !sliced && !tileCount) return PVOL_E_UNSUPPORTED;
-    // *T of a VolumeGrid is a product of stepped taus with drawn offsets: not a TauRec (the surface term is refused there)
-    if (a.tauOut && c->hs.volKind == PVOL_VOLUME_GRID) return PVOL_E_UNSUPPORTED;
-    uint32_t sliceM = 0, nSlices = 0;
-    if (sliced) {
-        uint32_t maxRays = maxRaysPerStream;
-        if (maxRays == 0) {   // device entry point: the stream table lives on the device
-            std::vector<pvol_stream> hs(nStreams);   // read on the caller's stream: ordered behind whatever produced the table
-            if (!ok(hipMemcpyAsync(hs.data(), dStreams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyDeviceToHost, stream)) ||
-                !ok(hipStreamSynchronize(stream))) return PVOL_E_NO_DEVICE;
-            for (uint32_t i = 0; i < nStreams; ++i) maxRays = std::max(maxRays, hs[i].n_rays);
-        }
-        const bool grid = c->hs.volKind == PVOL_VOLUME_GRID;
-        size_t stride = 16 + (size_t)((c->hs.maxSteps + 15) & ~15) + (grid ? 8 * (size_t)c->hs.maxSteps : 0);
-        stride = (stride + 15) & ~(size_t)15;
-        const size_t budget = (size_t)4 << 30;
-        size_t m = budget / (stride * (size_t)nStreams);
-        // nused beyond the bucket plan hands every dense lookup of a slice to the exact pass: keep that list within 8 GB
-        if (c->hs.nUsed > 100) m = std::min<size_t>(m, std::max<size_t>(64, (((size_t)8 << 30) / sizeof(DeferRec) / 64) / (size_t)nStreams));
-        if (spec) m = std::min<size_t>(m, std::max<size_t>(64, ((size_t)8 << 20) / (size_t)nStreams));   // keeps a slice's segment pool within its 16 M slots
-        m = std::max<size_t>(64, std::min<size_t>(m, ((size_t)maxRays + 63) & ~(size_t)63));
-        m &= ~(size_t)63;
-        if (const char *ev = getenv("PVOL_SLICE_RAYS")) { long v = atol(ev); if (v >= 64) m = (size_t)v & ~(size_t)63; }   // testing: force many slices
-        if (tile) {   // a slice holds whole pixels (both powers of two)
-            const size_t unit = std::max<size_t>(64, tile->spp);
-            m = std::max(unit, m / unit * unit);
-        }
-        sliceM = (uint32_t)m;
-        nSlices = maxRays ? (maxRays + sliceM - 1) / sliceM : 1;
-        size_t recBytes = stride * (size_t)nStreams * sliceM, stBytes = sizeof(uint32_t) * 625 * (size_t)nStreams;
-        if (recBytes > c->recBytes) { if (c->dRecords) hipFree(c->dRecords); c->dRecords = 0; c->recBytes = 0;
-                                      if (!ok(hipMalloc(&c->dRecords, recBytes))) return PVOL_E_NO_MEMORY; c->recBytes = recBytes; }
-        if (stBytes > c->stateBytes) { if (c->dState) hipFree(c->dState); c->dState = 0; c->stateBytes = 0;
-                                       if (!ok(hipMalloc(&c->dState, stBytes))) return PVOL_E_NO_MEMORY; c->stateBytes = stBytes; }
-        a.records = c->dRecords; a.recStride = (uint32_t)stride; a.sliceM = sliceM; a.state = c->dState;
-        // with a tile pre-pass in FUSED mode (several lights) the flag selects the pre-pass's own geometry + RNG-only form
-        a.liteResolve = (!c->noLite && !roulette_possible(c)) ? 1 : 0;
+    if (p.path == PVOL_PATH_SLICED && in.maxRays == 0) {   // device entry point: the stream table lives on the device
+        std::vector<pvol_stream> hs(b.nStreams);   // read on the caller's stream: ordered behind whatever produced the table
+        if (!ok(hipMemcpyAsync(hs.data(), b.streams, sizeof(pvol_stream) * (size_t)b.nStreams, hipMemcpyDeviceToHost, stream)) ||
+            !ok(hipStreamSynchronize(stream))) return PVOL_E_NO_DEVICE;
+        for (uint32_t i = 0; i < b.nStreams; ++i) in.maxRays = std::max(in.maxRays, hs[i].n_rays);
     }
-    if (par) hipMemsetAsync(c->dWords, 0, 3 * sizeof(uint32_t), stream);
-    if (tile && (par || (!sliced && tileCount))) {   // sampler + camera pre-pass, outside the timed region of the march kernel
+    plan_size(in, p);
+    int rc = reserve_scratch(c, p, stream);
+    if (rc != PVOL_OK) return rc;
+    c->lastKernel = p.kernel;
+    TileArgs tile;   // the tile driver's arguments, completed here with the segment pool of the specular recursion
+    if (b.tile) tile = *b.tile;
+    LiArgs a = {};
+    a.scene = c->ds; a.rays = b.rays; a.streams = b.streams; a.nStreams = b.nStreams; a.nRays = b.nRays; a.outputKind = b.outputKind;
+    a.out = b.out; a.draws = b.draws; a.initState = b.initState; a.finalState = b.finalState; a.counters = c->dCounters;
+    a.transmittanceOnly = b.transOnly; a.chunkCounter = c->dWords; a.needSeq = c->dWords + 1; a.gated = 0;
+    a.tauOut = b.tauOut; a.status = b.status; a.grpGuess = in.knobs.groupGuess;
+    if (p.groupForm) {
+        a.defer = pvol_buf<DeferRec>(c, PVOL_BUF_DEFER); a.deferCount = c->dWords + 2;
+        a.deferCap = (uint32_t)std::min<size_t>(c->buf[PVOL_BUF_DEFER].bytes / sizeof(DeferRec), 0xffffffffu);
+        if (p.path == PVOL_PATH_SLICED) { a.fxgWiden = in.knobs.fxgWiden; a.fxgAim = in.knobs.fxgAim; }
+    }
+    if (p.path == PVOL_PATH_PAR) hipMemsetAsync(c->dWords, 0, 3 * sizeof(uint32_t), stream);
+    if (p.tile == PVOL_TILE_COUNT) {   // outside the timed region of the march kernel; the march keeps the pre-pass's slice fields
         a.sliceK = 0; a.sliceM = 0xffffffc0u; a.state = 0;
-        if (spec) {
-            specCap = spec_pool_cap(nRays);
-            int rc = spec_pool_prepare(c, specCap, 0, stream);
-            if (rc != PVOL_OK) return rc;
-            spec_fill_tile(c, &tloc, specCap);
-        }
-        pvol_phase_mark(c, stream, PVOL_PHASE_TILE);
-        if (!ok(pvol_launch_tile(&a, tile, false, pvol_tile_lds_bytes(0, tile->spp, false, c->hs.nTris, c->hs.nLights > 0 && c->hs.lights[0].kind == PVOL_LIGHT_DISTANT), c->hs.candCap, stream,
-                                 tile_waves_per_task(c, nStreams)))) return PVOL_E_NO_DEVICE;
+        if (p.specCap) rc = spec_pool_reset(c, &tile, p.specCap, stream);
+        if (rc == PVOL_OK) rc = run_tile_count(c, b, p, a, &tile);
+        if (rc != PVOL_OK) return rc;
     }
     hipEventRecord(ev.first, stream);
     pvol_phase_mark(c, stream, PVOL_PHASE_MARCH);
-    if (par) {
-        unsigned long long chunks = ((unsigned long long)nRays + 63ull) / 64ull;
-        uint32_t nWaves = (uint32_t)std::min<unsigned long long>(chunks, (unsigned long long)c->nCU * 16ull);
-        // homogeneous isotropic medium with a photon map and k <= 64: one ray per lane, gathers of 64 rays share a bucket
-        const bool group = !c->noGroup && c->hs.volKind == PVOL_VOLUME_HOMOGENEOUS && c->hs.g == 0.f && c->hs.nPhotons > 0 &&
-                           c->hs.nUsed >= 10 && c->hs.nUsed <= 64 && c->hs.candCap <= 4 * 64;
-        if (group) {
-            unsigned long long gchunks = ((unsigned long long)nRays + 511ull) / 512ull;   // GRP_CH rays per chunk
-            uint32_t gWaves = (uint32_t)std::min<unsigned long long>(gchunks, (unsigned long long)c->nCU * (unsigned long long)c->groupWavesPerCU);
-            // room for the lookups the bucket plan hands over (a fraction of a percent of ~40 per ray on C2); a list that
-            // overflows raises needSeq and the batch is redone sequentially, never truncated
-            const size_t wantDefer = (size_t)nRays / 2 + 65536;
-            if (wantDefer > c->deferCap) {
-                hipStreamSynchronize(stream);   // an earlier batch may still read the old list
-                if (c->dDefer) hipFree(c->dDefer);
-                c->dDefer = 0; c->deferCap = 0;
-                if (!ok(hipMalloc(&c->dDefer, wantDefer * sizeof(DeferRec)))) return PVOL_E_NO_MEMORY;
-                c->deferCap = wantDefer;
-            }
-            a.defer = c->dDefer; a.deferCount = c->dWords + 2; a.deferCap = (uint32_t)std::min<size_t>(c->deferCap, 0xffffffffu);
-            e = pvol_launch_li_group(&a, pvol_group_lds_bytes(c->hs.candCap), c->hs.candCap, c->statsOn, gWaves, (uint32_t)(c->nCU * c->fixWavesPerCU), 0, stream);
-            c->lastKernel = "li_group_kernel";
-        } else {
-            c->lastKernel = "li_par_kernel";
-            e = pvol_launch_li_par(&a, lds_bytes_par(c), c->hs.candCap, c->statsOn, nWaves, stream);
-        }
-        if (ok(e)) {   // runs only if a ray raised needSeq (gate read on the device: no host sync here)
-            a.gated = 1;
-            e = pvol_launch_li_seq(&a, lds_bytes_seq(c), c->hs.candCap, c->statsOn, stream);
-            a.gated = 0;
-        }
-        if (ok(e) && spec) {
-            int rc = spec_finish(c, a, specCap, false, nRays, dOut, c->specSurfOut, stream);
-            if (rc != PVOL_OK) return rc;
-        }
-    } else if (sliced) {
-        c->lastKernel = "li_replay_kernel";
-        e = hipSuccess;
-        unsigned long long chunks = (unsigned long long)((sliceM + 63) / 64) * nStreams;
-        uint32_t nWaves = (uint32_t)std::min<unsigned long long>(chunks, (unsigned long long)c->nCU * 16ull);
-        // li_group_kernel's replay form (one ray per lane, shared photon bucket) where no march step can reach the roulette, the
-        // medium is isotropic and a photon map exists; li_replay_kernel (one wave per ray) otherwise, and as the gated backup
-        const bool gridVol = c->hs.volKind == PVOL_VOLUME_GRID;
-        int groupForm = 0;
-        if (!c->noGroup && !c->statsOn && !roulette_possible(c) && c->hs.g == 0.f && c->hs.nPhotons > 0 && c->hs.nUsed >= 10 &&
-            (c->hs.volKind == PVOL_VOLUME_HOMOGENEOUS || gridVol))
-            groupForm = gridVol ? 2 : 1;
-        uint32_t gWaves = 0;
-        if (groupForm) {
-            const unsigned long long gchunks = (unsigned long long)((sliceM + 511) / 512) * nStreams;
-            gWaves = (uint32_t)std::min<unsigned long long>(gchunks, (unsigned long long)c->nCU * (unsigned long long)c->groupWavesPerCU);
-            // hand-over list: nused beyond the bucket plan sends every dense lookup to the exact pass (C3: ~14 per ray)
-            const size_t perSlice = (size_t)sliceM * nStreams;
-            size_t wantDefer = (c->hs.nUsed > 100 ? perSlice * 64 : perSlice) + 65536;
-            wantDefer = std::min<size_t>(wantDefer, ((size_t)8 << 30) / sizeof(DeferRec));
-            if (wantDefer > c->deferCap) {
-                hipStreamSynchronize(stream);
-                if (c->dDefer) hipFree(c->dDefer);
-                c->dDefer = 0; c->deferCap = 0;
-                if (!ok(hipMalloc(&c->dDefer, wantDefer * sizeof(DeferRec)))) return PVOL_E_NO_MEMORY;
-                c->deferCap = wantDefer;
-            }
-            a.defer = c->dDefer; a.deferCount = c->dWords + 2; a.deferCap = (uint32_t)std::min<size_t>(c->deferCap, 0xffffffffu);
-            a.fixGroup = (c->hs.nUsed > 100 && !getenv("PVOL_FIX_EXACT")) ? 1 : 0;   // GRP_PLAN_KMAX: see pvol_fixgrp_dev.h
-            { const char *ew = getenv("PVOL_FXG_WIDEN"), *ea = getenv("PVOL_FXG_AIM"); a.fxgWiden = ew ? (float)atof(ew) : 0.f; a.fxgAim = ea ? (float)atof(ea) : 0.f; }   // measurement knobs
-            c->lastKernel = "li_group_kernel";
-        }
-        if (spec && !(tile && !tileGridCount && a.liteResolve)) return PVOL_E_UNSUPPORTED;   // the FUSED pre-pass walks the segments (geo_ray + lite_ray)
-        if (spec) specCap = spec_pool_cap((size_t)sliceM * nStreams);
-        if (tileGridCount) {   // sampler + camera + draw COUNT for the whole batch, once
-            LiArgs t = a;
-            t.sliceK = 0; t.sliceM = 0xffffffc0u; t.state = 0;
-            pvol_phase_mark(c, stream, PVOL_PHASE_TILE);
-            e = pvol_launch_tile(&t, tile, false, pvol_tile_lds_bytes(0, tile->spp, false, c->hs.nTris, c->hs.nLights > 0 && c->hs.lights[0].kind == PVOL_LIGHT_DISTANT), c->hs.candCap, stream,
-                                 tile_waves_per_task(c, nStreams));
-        }
-        for (uint32_t k = 0; k < nSlices && ok(e); ++k) {
-            a.sliceK = k;
-            hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), stream);
-            if (spec) {
-                int rc = spec_pool_prepare(c, specCap, a.recStride, stream);
-                if (rc != PVOL_OK) return rc;
-                spec_fill_tile(c, &tloc, specCap);
-            }
-            if (tile && !tileGridCount) {
-                pvol_phase_mark(c, stream, PVOL_PHASE_TILE);
-                e = pvol_launch_tile(&a, tile, true, pvol_tile_lds_bytes(c->hs.maxSteps, tile->spp, true, c->hs.nTris, false), c->hs.candCap, stream, 1);
-            }
-            pvol_phase_mark(c, stream, PVOL_PHASE_MARCH);   // incl. the RNG-only resolve pass of a slice where there is one
-            if (ok(e)) e = pvol_launch_li_slice(&a, 624 * 4 + (size_t)c->hs.maxSteps * 4, lds_bytes_par(c), c->hs.candCap, c->statsOn, nWaves, stream,
-                                                tile == 0 || tileGridCount, groupForm, pvol_group_lds_bytes(c->hs.candCap), gWaves, (uint32_t)(c->nCU * c->fixWavesPerCU));
-            if (ok(e) && spec) {   // this slice's segments: their Li() from the records the pre-pass left, then the fold into the slice's camera samples
-                int rc = spec_finish(c, a, specCap, true, nRays, dOut, c->specSurfOut, stream);
-                if (rc != PVOL_OK) return rc;
-            }
-        }
-    } else {
-        c->lastKernel = "li_seq_kernel";
-        e = pvol_launch_li_seq(&a, lds_bytes_seq(c), c->hs.candCap, c->statsOn, stream);
-    }
+    rc = p.path == PVOL_PATH_PAR ? run_par(c, b, p, a) : p.path == PVOL_PATH_SLICED ? run_sliced(c, b, p, a, &tile) : run_seq(c, b, p, a);
+    if (rc != PVOL_OK) return rc;
     hipEventRecord(ev.second, stream);
     pvol_phase_mark(c, stream, PVOL_PHASE_END);
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        c->pending.push_back(ev);
-        evGuard.keep = true;
-    }
-    return ok(e) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->pending.push_back(ev);
+    evGuard.keep = true;
+    return PVOL_OK;
 }
 
 static int check_errors(pvol_ctx *c) {
@@ -1016,7 +1009,10 @@ int pvol_li_batch_device(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvo
     if (!nStreams) return PVOL_OK;
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    return launch(c, dRays, nRays, dStreams, nStreams, outputKind, dOut, dDraws, 0, 0, 0, 0, (hipStream_t)hipStream);
+    BatchArgs b = {};   // maxRaysPerStream 0: the stream table lives on the device
+    b.rays = dRays; b.nRays = nRays; b.streams = dStreams; b.nStreams = nStreams; b.outputKind = outputKind; b.out = dOut; b.draws = dDraws;
+    b.stream = (hipStream_t)hipStream;
+    return pvol_launch_batch(c, b);
 }
 
 int pvol_check_errors(pvol_ctx *c) {
@@ -1059,7 +1055,12 @@ static int host_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, pvol_st
         if (good && mtState) good = ok(hipMemcpy(dState, mtState, sizeof(uint32_t) * 625 * (size_t)nStreams, hipMemcpyHostToDevice));
         if (!good) rc = PVOL_E_NO_DEVICE;
     }
-    if (rc == PVOL_OK) rc = launch(c, dRays, nRays, dStreams, nStreams, transOnly ? PVOL_OUT_SPECTRAL : outputKind, dOut, dDraws, dState, dState, transOnly, maxRays, 0);
+    if (rc == PVOL_OK) {
+        BatchArgs b = {};
+        b.rays = dRays; b.nRays = nRays; b.streams = dStreams; b.nStreams = nStreams; b.outputKind = transOnly ? PVOL_OUT_SPECTRAL : outputKind;
+        b.out = dOut; b.draws = dDraws; b.initState = dState; b.finalState = dState; b.transOnly = transOnly; b.maxRaysPerStream = maxRays;
+        rc = pvol_launch_batch(c, b);
+    }
     if (rc == PVOL_OK && !ok(hipStreamSynchronize(0))) rc = PVOL_E_NO_DEVICE;
     if (rc == PVOL_OK) rc = check_errors(c);
     if (rc == PVOL_OK) {

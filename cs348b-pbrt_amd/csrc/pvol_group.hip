@@ -207,23 +207,20 @@ extern "C" int pvol_render_frame_group_window(pvol_ctx *const *ctxs, uint32_t n,
     if (!ok(hipSetDevice(root->params.device))) return PVOL_E_NO_DEVICE;
     const hipStream_t s0 = streamOf(0);
     if (n > 1) {
+        DevBuf &stage = root->buf[PVOL_BUF_GROUP_STAGE];
         const size_t need = filmBytes * (n - 1);
-        if (need > root->groupStageBytes) {
-            if (root->groupStageEv && !ok(hipEventSynchronize(root->groupStageEv))) return PVOL_E_NO_DEVICE;   // the last sum read it
-            hipFree(root->dGroupStage);
-            root->dGroupStage = 0; root->groupStageBytes = 0;
-            if (!ok(hipMalloc(&root->dGroupStage, need))) { root->dGroupStage = 0; return PVOL_E_NO_MEMORY; }
-            root->groupStageBytes = need;
-        }
+        if (need > stage.bytes && root->groupStageEv && !ok(hipEventSynchronize(root->groupStageEv))) return PVOL_E_NO_DEVICE;   // the last sum read it
+        if (!pvol_reserve(stage, need, s0)) return PVOL_E_NO_MEMORY;
+        float4 *const dStage = (float4 *)stage.p;
         if (!root->groupStageEv && !ok(hipEventCreateWithFlags(&root->groupStageEv, hipEventDisableTiming))) { root->groupStageEv = 0; return PVOL_E_NO_DEVICE; }
         const int dev0 = root->params.device;
         for (uint32_t i = 1; i < n; ++i) {
             if (!ok(hipStreamWaitEvent(s0, ctxs[i]->groupFilmEv, 0)) ||
-                !ok(hipMemcpyPeerAsync(root->dGroupStage + (size_t)(i - 1) * nPix, dev0, dPixels[i], ctxs[i]->params.device, filmBytes, s0)))
+                !ok(hipMemcpyPeerAsync(dStage + (size_t)(i - 1) * nPix, dev0, dPixels[i], ctxs[i]->params.device, filmBytes, s0)))
                 return PVOL_E_NO_DEVICE;
         }
         const uint64_t blocks = std::min<uint64_t>((nPix + 255) / 256, (uint64_t)root->nCU * 8);
-        hipLaunchKernelGGL(film_sum_kernel, dim3((uint32_t)blocks), dim3(256), 0, s0, (float4 *)dPixels[0], (const float4 *)root->dGroupStage,
+        hipLaunchKernelGGL(film_sum_kernel, dim3((uint32_t)blocks), dim3(256), 0, s0, (float4 *)dPixels[0], dStage,
                            n - 1, nPix);
         if (!ok(hipGetLastError())) return PVOL_E_NO_DEVICE;
     }

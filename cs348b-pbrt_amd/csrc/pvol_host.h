@@ -45,6 +45,21 @@ extern "C" hipError_t pvol_grid_occupancy(const uint32_t *cellStart, uint32_t nc
 #define PVOL_N_PHASES 6
 enum { PVOL_PHASE_END = -1, PVOL_PHASE_TILE = 0, PVOL_PHASE_RNG = 1, PVOL_PHASE_MARCH = 2, PVOL_PHASE_SURFACE = 3, PVOL_PHASE_FILM = 4, PVOL_PHASE_OTHER = 5 };
 
+// The context's on-demand device buffers.  pvol_reserve is the one place they are allocated: nothing to do when `want` fits, else it
+// waits for `stream` (an earlier batch may still read the old buffer), frees, and allocates exactly `want` bytes.
+struct DevBuf { void *p = 0; size_t bytes = 0; };
+enum {
+    PVOL_BUF_RECORDS, PVOL_BUF_STATE,   // resolve/replay: per-step records of a slice, MT state of every stream
+    PVOL_BUF_DEFER,                     // li_group_kernel's deferred lookups (DeferRec)
+    PVOL_BUF_TAU, PVOL_BUF_SPEC_LINK,   // per sample of a render batch: the T the surface term is attenuated by (TauRec); its segments (one word)
+    PVOL_BUF_SEG_RAYS, PVOL_BUF_SEG_INFO, PVOL_BUF_SEG_OUT, PVOL_BUF_SEG_RECORDS,   // segment pool of the specular recursion: rays, SegInfo, 60 floats, records,
+    PVOL_BUF_SEG_COUNTER, PVOL_BUF_SEG_STREAM,   // ... its fill counter (16 bytes) and the pool seen as one pvol_stream
+    PVOL_BUF_TILE_RAYS, PVOL_BUF_TILE_XY, PVOL_BUF_TILE_OUT, PVOL_BUF_TILE_STREAMS, PVOL_BUF_TILE_WINDOWS,   // tile driver (pvol_tile.hip)
+    PVOL_BUF_LI_IN, PVOL_BUF_LI_OUT,    // device staging of the coalesced per-sample batches (pvol_li_coalesce.hip)
+    PVOL_BUF_GROUP_STAGE, PVOL_N_BUFS   // pvol_render_frame_group: the other contexts' films next to the root's
+};
+extern "C" bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream);
+
 struct pvol_ctx {
     pvol_params params;
     bool haveScene;
@@ -63,8 +78,6 @@ struct pvol_ctx {
     uint32_t *dSubStart = 0;   // second level of a clumpy map (pvol_grid.hip), else 0
     DevCounters *dCounters;
     uint32_t *dWords;   // [0] chunk counter of the ray-parallel kernels, [1] needSeq flag, [2] length of the deferred-lookup list, [3] chunk counter of a gated backup kernel
-    DeferRec *dDefer = 0;   // li_group_kernel's deferred lookups (grown on demand)
-    size_t deferCap = 0;
     int nCU;
     float maxDensity = 1.f;   // largest density factor of the medium (1 for analytic volumes, max of the grid values)
     bool noLite = false;      // PVOL_NO_LITE=1: keep the geometry inside the sequential resolve pass (testing)
@@ -87,15 +100,10 @@ struct pvol_ctx {
     std::vector<std::pair<int, hipEvent_t> > phaseMarks;
     std::vector<hipEvent_t> phasePool;
     double phaseMs[PVOL_N_PHASES] = {0, 0, 0, 0, 0, 0};
-    // One batch at a time per context: the launches of a batch share dWords / dRecords / dState / dCounters and the
-    // deferred-lookup list.  Host entry points hold it from upload to copy-back (VolumeIntegrator::Li is called from every
+    // One batch at a time per context: the launches of a batch share dWords / dCounters and the scratch in `buf`.  Host entry points hold it from upload to copy-back (VolumeIntegrator::Li is called from every
     // SamplerRendererTask thread at once, samplerrenderer.cpp:247); device entry points hold it while they enqueue.
     std::recursive_mutex apiMu;
-    // resolve/replay scratch (grown on demand)
-    unsigned char *dRecords = 0;
-    size_t recBytes = 0;
-    uint32_t *dState = 0;
-    size_t stateBytes = 0;
+    DevBuf buf[PVOL_N_BUFS];   // scratch grown on demand (pvol_reserve), freed in one loop by pvol_destroy
     // photon shooter
     DevShootScene hsh;
     DevShootScene *dsh;
@@ -108,28 +116,11 @@ struct pvol_ctx {
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     float4 *dCPos4 = 0, *dCAlpha4 = 0, *dCWi4 = 0;
     uint32_t *dCCellStart = 0;
-    TauRec *dTau = 0;      // per sample of a render batch: the T the surface term is attenuated by
-    size_t tauBytes = 0;
-    TauRec *dTauNext = 0;   // set by the render driver around pvol_launch_batch when the surface integrator is on
     // specular recursion of the surface integrator (pvol_spec_dev.h): segments of the camera samples that meet glass
     bool specOn = false;            // the scene holds a specular material and the surface integrator is on
-    pvol_ray *dSegRays = 0;
-    SegInfo *dSegInfo = 0;
-    float *dSegOut = 0;             // 60 floats per segment
-    unsigned char *dSegRecords = 0; // per-step records of the segments (scenes where drawn values matter)
-    uint32_t *dSegCounter = 0;
-    pvol_stream *dSegStream = 0;    // the pool seen as one stream of a ray batch
-    pvol_stream hSegStream;
-    size_t segCap = 0, segRecBytes = 0;
-    uint32_t *dSpecLink = 0;        // per primary ray of a render batch
-    size_t specLinkBytes = 0;
-    float *specSurfOut = 0;         // set by the render driver around pvol_launch_batch: where the composition reports the surface term
+    pvol_stream hSegStream;         // the segment pool seen as one stream of a ray batch (host copy of PVOL_BUF_SEG_STREAM)
     double exchangeSeconds = 0.0;   // last pvol_preprocess: time in its all-gathers (part of prepSeconds[0]; 0 after pvol_preprocess_blocks)
     double prepSeconds[2] = {0.0, 0.0};   // last pvol_preprocess: shooting (all rounds + merges), search-structure build
-    // tile driver work buffers (grown on demand, pvol_tile.hip)
-    void *dTile[6] = {0, 0, 0, 0, 0, 0};
-    size_t tileBytes[6] = {0, 0, 0, 0, 0, 0};
-    int32_t *dStatusNext = 0;   // set by a coalesced per-sample batch around pvol_launch_batch: per ray PVOL_E_LIMIT (LiArgs::status)
     // coalesced per-sample calls (pvol_li_coalesce.hip): concurrent pvol_li calls queue here, one of them (the leader) runs
     // a batch of up to coMaxBatch of them while the others wait; coMu guards the queue, apiMu still guards the batch
     std::atomic<uint32_t> coMaxBatch{0};   // <= 1: every pvol_li is its own batch (pvol_li_lone)
@@ -141,15 +132,13 @@ struct pvol_ctx {
     // calls served by coalesced batches, batches, largest batch, calls that queued behind a batch; then, for every batch of
     // pvol_li_many and the coalescer: batches redone call by call (gated backup), calls that failed on their own
     uint64_t coStats[6] = {0, 0, 0, 0, 0, 0};
-    // persistent staging of the batches (pinned host + device, grown to the largest batch) and the context's own stream
+    // persistent staging of the batches (pinned host here, device in `buf`, grown to the largest batch) and the context's own stream
     hipStream_t coStream = 0;
-    unsigned char *coHostIn = 0, *coHostOut = 0, *coDevIn = 0, *coDevOut = 0;
+    unsigned char *coHostIn = 0, *coHostOut = 0;
     uint32_t coCap = 0;
-    // pvol_render_frame_group (pvol_group.hip): the event marking this context's film done; as the root, the other films' staging
-    // and the event after the sum that last read it
+    // pvol_render_frame_group (pvol_group.hip): the event marking this context's film done; as the root, the event after the sum
+    // that last read the other films' staging (PVOL_BUF_GROUP_STAGE)
     hipEvent_t groupFilmEv = 0, groupStageEv = 0;
-    float4 *dGroupStage = 0;
-    size_t groupStageBytes = 0;
 };
 
 // One per-sample call of a coalesced batch: the caller's buffers, written only when rc ends PVOL_OK.
@@ -164,11 +153,50 @@ struct LiRequest {
 #define PVOL_LI_MAX_BATCH 4096u
 #define PVOL_LI_MAX_WAIT_US 1000u
 
+// Every input of one batch (pvol_launch_batch).  `tile` != 0: the rays do not exist yet -- the tile kernel (pvol_tile_dev.h) generates
+// them stream by stream in front of the march.  maxRaysPerStream 0: unknown, read back from the device table where a slice is sized.
+struct BatchArgs {
+    const pvol_ray *rays; uint32_t nRays; pvol_stream *streams; uint32_t nStreams;
+    int outputKind; float *out; uint32_t *draws; const uint32_t *initState; uint32_t *finalState;
+    int transOnly; uint32_t maxRaysPerStream; const TileArgs *tile; hipStream_t stream;
+    TauRec *tauOut;       // render driver with the surface integrator on: the march kernels also report every sample's *T
+    int32_t *status;      // coalesced per-sample batch: per ray PVOL_E_LIMIT (LiArgs::status), a limit fails only its own call
+    float *specSurfOut;   // specular recursion: where the composition reports the surface term (debug), or 0
+};
+extern "C" int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b);
+template <class T> static inline T *pvol_buf(const pvol_ctx *c, int which) { return (T *)c->buf[which].p; }
 
-struct pvol_ctx;
-extern "C" int pvol_launch_batch(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_stream *dStreams, uint32_t nStreams, int outputKind,
-                      float *dOut, uint32_t *dDraws, const uint32_t *dInit, uint32_t *dFinal, int transOnly, uint32_t maxRaysPerStream,
-                      const TileArgs *tile, hipStream_t stream);
+// ---- the plan of a batch: which kernels it takes and every size they need, a pure function of PlanIn.  LaunchKnobs: the
+// environment knobs read once per launch (pvol_read_knobs); 0 = unset, the default applies.
+struct LaunchKnobs {
+    int64_t sliceRays, specPool, tileBatchRays;   // PVOL_SLICE_RAYS (>= 64: forced slice length), PVOL_SPEC_POOL, PVOL_TILE_BATCH_RAYS
+    float groupGuess;                             // PVOL_GROUP_GUESS, already defaulted: li_group_kernel's bucket radius^2 factor
+    float fxgWiden, fxgAim;                       // PVOL_FXG_WIDEN, PVOL_FXG_AIM (measurement knobs of li_fixup_group_kernel)
+    int32_t fixExact;                             // PVOL_FIX_EXACT set
+};
+extern "C" LaunchKnobs pvol_read_knobs();
+struct PlanIn {
+    int32_t nLights, volKind; float g; uint32_t nPhotons; int32_t nUsed, candCap, maxSteps, nTris;   // medium and map
+    int32_t roulette, distant;   // a march step can reach the Russian roulette (roulette_possible); the first light is a distant one
+    int32_t forceSeq, noGroup, noLite, statsOn, nCU, groupWavesPerCU, fixWavesPerCU, tileWaves;   // context flags, device shape
+    uint32_t nRays, nStreams, maxRays; int32_t hasInit, transOnly, hasTile; uint32_t spp; int32_t specOn, hasTauOut;   // the batch
+    LaunchKnobs knobs;
+};
+enum { PVOL_PATH_PAR, PVOL_PATH_SLICED, PVOL_PATH_SEQ };
+enum { PVOL_TILE_NONE, PVOL_TILE_COUNT, PVOL_TILE_GRID_COUNT, PVOL_TILE_FUSED };
+struct BatchPlan {
+    int32_t rc, path, tile;
+    int32_t groupForm;        // li_group_kernel's form: 0 none, 1 homogeneous (PAR: no records), 2 VolumeGrid
+    int32_t fixGroup, liteResolve;
+    int32_t resolve;          // SLICED: the slice runs its own resolve pass (no FUSED pre-pass wrote the records)
+    uint32_t recStride, sliceM, nSlices, nWaves, gWaves, fixWaves; int32_t tileWavesPerTask;
+    uint64_t recBytes, stateBytes, deferWant, specCap, ldsSeq, ldsPar, ldsResolve, ldsGroup, ldsTile;
+    const char *kernel;       // what pvol_march_kernel_name reports
+};
+static_assert(sizeof(PlanIn) == 152 && sizeof(BatchPlan) == 136, "tests/test_launch_plan.py mirrors both");
+extern "C" size_t pvol_rec_stride(int maxSteps, bool grid);   // bytes of one record slot
+extern "C" BatchPlan plan_path(const PlanIn &in);             // everything that needs no maxRays
+extern "C" void plan_size(const PlanIn &in, BatchPlan &p);    // the rest, once in.maxRays is known
 
 extern "C" {
 void pvol_phase_mark(pvol_ctx *c, hipStream_t stream, int id);
@@ -185,6 +213,8 @@ void pvol_free_li_staging(pvol_ctx *c);
 int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream);
 // an RCCL function by name, bound at run time once per process (pvol_tile.hip); 0 when no RCCL is in reach
 void *pvol_rccl_symbol(const char *name);
+// plan_size(plan_path(in)) for the tests; like pvol_rccl_symbol not part of include/pvol.h
+void pvol_plan_batch(const PlanIn *in, BatchPlan *out);
 }
 
 // ImageFilm's crop window behind the *_window entry points: a NULL window is the whole frame (crop 0 1 0 1), which is what the

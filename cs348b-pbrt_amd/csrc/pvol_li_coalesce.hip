@@ -24,13 +24,13 @@ static bool ok(hipError_t e) { return e == hipSuccess; }
 static size_t in_bytes(size_t n) { return n * (sizeof(pvol_ray) + sizeof(pvol_stream) + 625 * 4); }
 static size_t out_bytes(size_t n) { return n * (60 * 4 + 625 * 4 + 4) + 16; }
 
-void pvol_free_li_staging(pvol_ctx *c) {
+static void free_host_staging(pvol_ctx *c) {
     if (c->coHostIn) hipHostFree(c->coHostIn);
     if (c->coHostOut) hipHostFree(c->coHostOut);
-    if (c->coDevIn) hipFree(c->coDevIn);
-    if (c->coDevOut) hipFree(c->coDevOut);
-    c->coHostIn = c->coHostOut = c->coDevIn = c->coDevOut = 0;
-    c->coCap = 0;
+    c->coHostIn = c->coHostOut = 0; c->coCap = 0;
+}
+void pvol_free_li_staging(pvol_ctx *c) {   // the device halves (PVOL_BUF_LI_IN / _OUT) go with the context's other buffers
+    free_host_staging(c);
     if (c->coStream) hipStreamDestroy(c->coStream);
     c->coStream = 0;
 }
@@ -40,18 +40,12 @@ static int reserve_staging(pvol_ctx *c, uint32_t n) {
     if (!c->coStream && !ok(hipStreamCreate(&c->coStream))) { c->coStream = 0; return PVOL_E_NO_DEVICE; }   // blocking: behind the null stream
     if (n <= c->coCap) return PVOL_OK;
     const uint32_t cap = std::min(PVOL_LI_MAX_BATCH, std::max(n, 2 * c->coCap));
-    hipStream_t s = c->coStream;
-    c->coStream = 0;   // kept across the regrowth
-    pvol_free_li_staging(c);
-    c->coStream = s;
+    free_host_staging(c);
     if (!ok(hipHostMalloc((void **)&c->coHostIn, in_bytes(cap), hipHostMallocDefault)) ||
-        !ok(hipHostMalloc((void **)&c->coHostOut, out_bytes(cap), hipHostMallocDefault)) || !ok(hipMalloc(&c->coDevIn, in_bytes(cap))) ||
-        !ok(hipMalloc(&c->coDevOut, out_bytes(cap)))) {
+        !ok(hipHostMalloc((void **)&c->coHostOut, out_bytes(cap), hipHostMallocDefault)) ||
+        !pvol_reserve(c->buf[PVOL_BUF_LI_IN], in_bytes(cap), c->coStream) || !pvol_reserve(c->buf[PVOL_BUF_LI_OUT], out_bytes(cap), c->coStream)) {
         (void)hipGetLastError();
-        s = c->coStream;
-        c->coStream = 0;
-        pvol_free_li_staging(c);
-        c->coStream = s;
+        free_host_staging(c);
         return PVOL_E_NO_MEMORY;
     }
     c->coCap = cap;
@@ -82,21 +76,22 @@ static void run_piece(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
         hStates[(size_t)i * 625 + 624] = (uint32_t)*req[i]->mti;
     }
     hipStream_t s = c->coStream;
-    float *dOut = reinterpret_cast<float *>(c->coDevOut);
-    int32_t *dStatus = reinterpret_cast<int32_t *>(c->coDevOut + oStatus);
-    bool good = pvol_order_after_pending(c, s) == PVOL_OK && ok(hipMemcpyAsync(c->coDevIn, c->coHostIn, in_bytes(n), hipMemcpyHostToDevice, s)) &&
+    unsigned char *devIn = pvol_buf<unsigned char>(c, PVOL_BUF_LI_IN), *devOut = pvol_buf<unsigned char>(c, PVOL_BUF_LI_OUT);
+    float *dOut = reinterpret_cast<float *>(devOut);
+    int32_t *dStatus = reinterpret_cast<int32_t *>(devOut + oStatus);
+    bool good = pvol_order_after_pending(c, s) == PVOL_OK && ok(hipMemcpyAsync(devIn, c->coHostIn, in_bytes(n), hipMemcpyHostToDevice, s)) &&
                 ok(hipMemsetAsync(dOut, 0, oStatesOut, s)) && ok(hipMemsetAsync(dStatus, 0, (size_t)n * 4, s));
     rc = good ? PVOL_OK : PVOL_E_NO_DEVICE;
     if (rc == PVOL_OK) {
-        c->dStatusNext = dStatus;
-        rc = pvol_launch_batch(c, reinterpret_cast<const pvol_ray *>(c->coDevIn), n, reinterpret_cast<pvol_stream *>(c->coDevIn + oStreams), n,
-                               PVOL_OUT_SPECTRAL, dOut, 0, reinterpret_cast<const uint32_t *>(c->coDevIn + oStatesIn),
-                               reinterpret_cast<uint32_t *>(c->coDevOut + oStatesOut), 0, 1, 0, s);
-        c->dStatusNext = 0;
+        BatchArgs b = {};
+        b.rays = reinterpret_cast<const pvol_ray *>(devIn); b.nRays = n; b.streams = reinterpret_cast<pvol_stream *>(devIn + oStreams); b.nStreams = n;
+        b.outputKind = PVOL_OUT_SPECTRAL; b.out = dOut; b.initState = reinterpret_cast<const uint32_t *>(devIn + oStatesIn);
+        b.finalState = reinterpret_cast<uint32_t *>(devOut + oStatesOut); b.maxRaysPerStream = 1; b.stream = s; b.status = dStatus;
+        rc = pvol_launch_batch(c, b);
     }
     // a PVOL_E_LIMIT of this batch is in its rays' status only (report_limit): the context's shared count is left alone
     if (rc == PVOL_OK)
-        good = ok(hipMemcpyAsync(c->coHostOut, c->coDevOut, oGate, hipMemcpyDeviceToHost, s)) &&
+        good = ok(hipMemcpyAsync(c->coHostOut, devOut, oGate, hipMemcpyDeviceToHost, s)) &&
                ok(hipMemcpyAsync(c->coHostOut + oGate, c->dWords + 1, 4, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s));
     if (rc == PVOL_OK && !good) rc = PVOL_E_NO_DEVICE;
     if (rc != PVOL_OK) { (void)hipGetLastError(); hipStreamSynchronize(s); return failAll(rc); }
@@ -125,17 +120,18 @@ static void run_piece(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
     if (failed) count(c, 5, failed);
 }
 
-// Runs n <= PVOL_LI_MAX_BATCH validated calls; every request's rc is set, its buffers written where it is PVOL_OK.  Every call
-// holds a record slice of 64 slots (the sliced path's floor): a batch whose slices would outgrow the 4 GB record budget of
-// pvol_launch_batch (a VolumeGrid with a long step plan) is launched in pieces.
+// Every call holds a record slice of 64 slots (the sliced path's floor): a batch whose slices would outgrow the 4 GB record budget of
+// the plan (a VolumeGrid with a long step plan) is launched in pieces of this many calls.
+extern "C" uint32_t pvol_li_piece(int maxSteps, int grid, uint32_t n) {
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, ((size_t)4 << 30) / (pvol_rec_stride(maxSteps, grid != 0) * 64)));
+}
+
+// Runs n <= PVOL_LI_MAX_BATCH validated calls; every request's rc is set, its buffers written where it is PVOL_OK.
 static void run_batch(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
     if (!c->haveScene) { for (uint32_t i = 0; i < n; ++i) req[i]->rc = PVOL_E_NO_SCENE; return; }
     if (!ok(hipSetDevice(c->params.device))) { for (uint32_t i = 0; i < n; ++i) req[i]->rc = PVOL_E_NO_DEVICE; return; }
-    const size_t maxSteps = (size_t)std::max(0, c->hs.maxSteps);
-    size_t stride = 16 + ((maxSteps + 15) & ~(size_t)15) + (c->hs.volKind == PVOL_VOLUME_GRID ? 8 * maxSteps : 0);
-    stride = (stride + 15) & ~(size_t)15;
-    const uint32_t piece = (uint32_t)std::max<size_t>(1, std::min<size_t>(n, ((size_t)4 << 30) / (stride * 64)));
+    const uint32_t piece = pvol_li_piece(c->hs.maxSteps, c->hs.volKind == PVOL_VOLUME_GRID, n);
     for (uint32_t b = 0; b < n; b += piece) run_piece(c, req + b, std::min(piece, n - b));
 }
 

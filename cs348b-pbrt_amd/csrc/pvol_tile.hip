@@ -272,15 +272,6 @@ extern "C" int pvol_film_resolve_device(pvol_ctx *c, const pvol_film *film, cons
 }
 
 // ------------------------------------------------------------------------------------------ render
-static bool grow(pvol_ctx *c, int slot, size_t bytes) {
-    if (bytes <= c->tileBytes[slot]) return true;
-    if (c->dTile[slot]) hipFree(c->dTile[slot]);
-    c->dTile[slot] = 0; c->tileBytes[slot] = 0;
-    if (!ok(hipMalloc(&c->dTile[slot], bytes))) return false;
-    c->tileBytes[slot] = bytes;
-    return true;
-}
-
 // The sampler carries the sample extent (the window's own, pvol_film_sample_extent, or any other): every size below -- the tasks'
 // sub-windows, the batches, the work buffers, the debug records -- comes from it, and only the splat reads the window.
 extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window,
@@ -314,9 +305,8 @@ extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *c
 #endif
 
     // batches of tasks bounded by the work-buffer budget (rays 48 B + xy 8 B + XYZ 16 B per sample)
-    size_t batchRays = (size_t)256 << 20;
-    if (const char *ev = getenv("PVOL_TILE_BATCH_RAYS")) { long long v = atoll(ev); if (v > 0) batchRays = (size_t)v; }
-    batchRays = std::min<size_t>(batchRays, 0xfffff000u);
+    const int64_t knob = pvol_read_knobs().tileBatchRays;
+    const size_t batchRays = std::min<size_t>(knob > 0 ? (size_t)knob : (size_t)256 << 20, 0xfffff000u);
     std::vector<int32_t> win(4 * (size_t)nTaskIds);
     std::vector<uint64_t> count(nTaskIds);
     for (uint32_t i = 0; i < nTaskIds; ++i) {
@@ -340,56 +330,42 @@ extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *c
             hs[i].n_rays = (uint32_t)count[b0 + i];
             first += count[b0 + i];
         }
-        if (!grow(c, 0, std::max<size_t>(sizeof(pvol_ray) * nRays, 64)) || !grow(c, 1, std::max<size_t>(8 * nRays, 64)) ||
-            !grow(c, 2, std::max<size_t>(16 * nRays, 64)) || !grow(c, 3, sizeof(pvol_stream) * nStreams) || !grow(c, 4, 16 * (size_t)nStreams))
-            return PVOL_E_NO_MEMORY;
-        pvol_ray *dRays = (pvol_ray *)c->dTile[0];
-        float *dXY = (float *)c->dTile[1], *dOut = (float *)c->dTile[2];
-        pvol_stream *dStreams = (pvol_stream *)c->dTile[3];
-        int4 *dWin = (int4 *)c->dTile[4];
+        const bool surfOn = c->hs.surf.enabled != 0 && nRays;
+        const bool specOn = surfOn && c->specOn;
+        // work buffers; with the surface integrator every sample's T, with specular surfaces in view a link word per sample (its segments)
+        const size_t want[] = {std::max<size_t>(sizeof(pvol_ray) * nRays, 64), std::max<size_t>(8 * nRays, 64), std::max<size_t>(16 * nRays, 64),
+                               sizeof(pvol_stream) * nStreams, 16 * (size_t)nStreams};
+        for (int i = 0; i < 5; ++i) if (!pvol_reserve(c->buf[PVOL_BUF_TILE_RAYS + i], want[i], stream)) return PVOL_E_NO_MEMORY;
+        if (!pvol_reserve(c->buf[PVOL_BUF_TAU], surfOn ? sizeof(TauRec) * nRays : 0, stream) ||
+            !pvol_reserve(c->buf[PVOL_BUF_SPEC_LINK], specOn ? 4 * nRays : 0, stream)) return PVOL_E_NO_MEMORY;
+        pvol_ray *dRays = pvol_buf<pvol_ray>(c, PVOL_BUF_TILE_RAYS);
+        float *dXY = pvol_buf<float>(c, PVOL_BUF_TILE_XY), *dOut = pvol_buf<float>(c, PVOL_BUF_TILE_OUT);
+        pvol_stream *dStreams = pvol_buf<pvol_stream>(c, PVOL_BUF_TILE_STREAMS);
+        int4 *dWin = pvol_buf<int4>(c, PVOL_BUF_TILE_WINDOWS);
+        TauRec *dTau = pvol_buf<TauRec>(c, PVOL_BUF_TAU);
+        uint32_t *dSpecLink = pvol_buf<uint32_t>(c, PVOL_BUF_SPEC_LINK);
         // the previous batch's kernels still read the buffers: these copies are ordered behind them on `stream`
         if (!ok(hipMemcpyAsync(dStreams, hs.data(), sizeof(pvol_stream) * nStreams, hipMemcpyHostToDevice, stream)) ||
             !ok(hipMemcpyAsync(dWin, &win[4 * (size_t)b0], 16 * (size_t)nStreams, hipMemcpyHostToDevice, stream)))
             return PVOL_E_NO_DEVICE;
         if (!ok(hipStreamSynchronize(stream))) return PVOL_E_NO_DEVICE;   // hs / win are host temporaries
         T.windows = dWin; T.rays = dRays; T.xy = dXY;
-        const bool surfOn = c->hs.surf.enabled != 0;
-        const bool specOn = surfOn && c->specOn;
-        T.specOn = 0; T.specLink = 0;
-        if (specOn && nRays) {   // one link word per camera sample: which segments of the specular recursion belong to it
-            const size_t want = 4 * nRays;
-            if (want > c->specLinkBytes) {
-                hipStreamSynchronize(stream);
-                if (c->dSpecLink) hipFree(c->dSpecLink);
-                c->dSpecLink = 0; c->specLinkBytes = 0;
-                if (!ok(hipMalloc(&c->dSpecLink, want))) return PVOL_E_NO_MEMORY;
-                c->specLinkBytes = want;
-            }
-            T.specOn = 1; T.specLink = c->dSpecLink;
-            if (!ok(hipMemsetAsync(c->dSpecLink, 0, want, stream))) return PVOL_E_NO_DEVICE;
-            c->specSurfOut = debug && debug->d_surf_xyz ? debug->d_surf_xyz + 3 * doneRays : 0;
-        }
-        if (surfOn && nRays) {
-            const size_t want = sizeof(TauRec) * nRays;
-            if (want > c->tauBytes) {
-                hipStreamSynchronize(stream);
-                if (c->dTau) hipFree(c->dTau);
-                c->dTau = 0; c->tauBytes = 0;
-                if (!ok(hipMalloc(&c->dTau, want))) return PVOL_E_NO_MEMORY;
-                c->tauBytes = want;
-            }
-        }
+        T.specOn = specOn; T.specLink = specOn ? dSpecLink : 0;
+        if (specOn && !ok(hipMemsetAsync(dSpecLink, 0, 4 * nRays, stream))) return PVOL_E_NO_DEVICE;
         if (nRays) {
-            c->dTauNext = surfOn ? c->dTau : 0;
-            int rc = pvol_launch_batch(c, dRays, (uint32_t)nRays, dStreams, nStreams, PVOL_OUT_XYZ, dOut, 0, 0, 0, 0, maxRays, &T, stream);
-            c->dTauNext = 0;
+            float *const surfOut = debug && debug->d_surf_xyz ? debug->d_surf_xyz + 3 * doneRays : 0;
+            BatchArgs b = {};
+            b.rays = dRays; b.nRays = (uint32_t)nRays; b.streams = dStreams; b.nStreams = nStreams; b.outputKind = PVOL_OUT_XYZ; b.out = dOut;
+            b.maxRaysPerStream = maxRays; b.tile = &T; b.stream = stream;
+            b.tauOut = surfOn ? dTau : 0; b.specSurfOut = specOn ? surfOut : 0;
+            int rc = pvol_launch_batch(c, b);
             if (rc != PVOL_OK) return rc;
             if (surfOn) {   // Ls of PhotonIntegrator::Li, composed as T * Ls + Lvi (samplerrenderer.cpp:95-97)
                 SurfArgs sa;
                 memset(&sa, 0, sizeof(sa));
-                sa.link = specOn ? c->dSpecLink : 0;
-                sa.scene = c->ds; sa.rays = dRays; sa.nRays = (uint32_t)nRays; sa.out = dOut; sa.tau = c->dTau;
-                sa.surfOut = debug ? debug->d_surf_xyz ? debug->d_surf_xyz + 3 * doneRays : 0 : 0;
+                sa.link = specOn ? dSpecLink : 0;
+                sa.scene = c->ds; sa.rays = dRays; sa.nRays = (uint32_t)nRays; sa.out = dOut; sa.tau = dTau;
+                sa.surfOut = surfOut;
                 sa.counters = c->dCounters;
                 const unsigned long long groups = (nRays + 63) / 64;
                 pvol_phase_mark(c, stream, PVOL_PHASE_SURFACE);
