@@ -877,7 +877,7 @@ static int spec_finish(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, cons
 // sampler + camera pre-pass that COUNTs Li()'s draws for the whole batch, once (`t`: the batch as one slice)
 static int run_tile_count(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, const LiArgs &t, const TileArgs *tile) {
     pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
-    return ok(pvol_launch_tile(&t, tile, false, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return ok(pvol_launch_tile(&t, tile, false, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, &c->lastTileKernel)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 static int run_par(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a) {
     hipError_t e = p.groupForm ? pvol_launch_li_group(&a, p.ldsGroup, c->hs.candCap, c->statsOn, p.gWaves, p.fixWaves, 0, b.stream)
@@ -905,7 +905,7 @@ static int run_sliced(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArg
         if (p.specCap && spec_pool_reset(c, tile, p.specCap, b.stream) != PVOL_OK) return PVOL_E_NO_DEVICE;
         if (p.tile == PVOL_TILE_FUSED) {
             pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
-            if (!ok(pvol_launch_tile(&a, tile, true, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask))) return PVOL_E_NO_DEVICE;
+            if (!ok(pvol_launch_tile(&a, tile, true, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, &c->lastTileKernel))) return PVOL_E_NO_DEVICE;
         }
         pvol_phase_mark(c, b.stream, PVOL_PHASE_MARCH);   // incl. the RNG-only resolve pass of a slice where there is one
         if (!ok(pvol_launch_li_slice(&a, p.ldsResolve, p.ldsPar, c->hs.candCap, c->statsOn, p.nWaves, b.stream, p.resolve != 0, p.groupForm, p.ldsGroup,
@@ -1143,6 +1143,7 @@ int pvol_get_stats(pvol_ctx *c, pvol_stats *out, int reset) {
 }
 
 const char *pvol_march_kernel_name(pvol_ctx *c) { return c ? c->lastKernel : ""; }
+const char *pvol_tile_kernel_name(pvol_ctx *c) { return c ? c->lastTileKernel : ""; }
 
 int pvol_enable_phase_timing(pvol_ctx *c, int on) {
     if (!c) return PVOL_E_INVALID;

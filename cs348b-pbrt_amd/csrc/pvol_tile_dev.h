@@ -644,26 +644,30 @@ extern "C" size_t pvol_tile_lds_bytes(int maxSteps, uint32_t spp, bool fused, in
            (shadowRows ? (size_t)nTris * 16 * 4 : 0) + 64;
 }
 
+// *form: the name of what was launched (pvol_tile_kernel_name), written next to each launch so that it cannot say anything else
 template <bool SPEC>
-static hipError_t launch_tile_t(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask) {
+static hipError_t launch_tile_t(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask,
+                                const char **form) {
     dim3 grid(args->nStreams), block(LANES);
     if (!fused && wavesPerTask > 1 && args->state == 0 && args->sliceK == 0) {
         const uint32_t partOff = (uint32_t)((ldsBytes + 15) & ~(size_t)15);
         const size_t bytes = partOff + 16 * 8;
-        if (wavesPerTask >= 16) hipLaunchKernelGGL((tile_mw_kernel<16, SPEC>), grid, dim3(LANES * 16), bytes, stream, *args, *tile, partOff);
-        else if (wavesPerTask >= 8) hipLaunchKernelGGL((tile_mw_kernel<8, SPEC>), grid, dim3(LANES * 8), bytes, stream, *args, *tile, partOff);
-        else if (wavesPerTask >= 4) hipLaunchKernelGGL((tile_mw_kernel<4, SPEC>), grid, dim3(LANES * 4), bytes, stream, *args, *tile, partOff);
-        else hipLaunchKernelGGL((tile_mw_kernel<2, SPEC>), grid, dim3(LANES * 2), bytes, stream, *args, *tile, partOff);
+        if (wavesPerTask >= 16) { *form = "tile_mw_kernel<16>"; hipLaunchKernelGGL((tile_mw_kernel<16, SPEC>), grid, dim3(LANES * 16), bytes, stream, *args, *tile, partOff); }
+        else if (wavesPerTask >= 8) { *form = "tile_mw_kernel<8>"; hipLaunchKernelGGL((tile_mw_kernel<8, SPEC>), grid, dim3(LANES * 8), bytes, stream, *args, *tile, partOff); }
+        else if (wavesPerTask >= 4) { *form = "tile_mw_kernel<4>"; hipLaunchKernelGGL((tile_mw_kernel<4, SPEC>), grid, dim3(LANES * 4), bytes, stream, *args, *tile, partOff); }
+        else { *form = "tile_mw_kernel<2>"; hipLaunchKernelGGL((tile_mw_kernel<2, SPEC>), grid, dim3(LANES * 2), bytes, stream, *args, *tile, partOff); }
         return hipGetLastError();
     }
+    *form = fused ? "tile_kernel<fused>" : "tile_kernel<count>";
     if (!fused) hipLaunchKernelGGL((tile_kernel<false, 4, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
     else if (candCap <= 4 * LANES) hipLaunchKernelGGL((tile_kernel<true, 4, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
     else hipLaunchKernelGGL((tile_kernel<true, 12, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
     return hipGetLastError();
 }
-// wavesPerTask (COUNT mode, whole batch in one launch): 1 = the one-wave kernel; 4 / 8 / 16 = tile_mw_kernel, chosen by the host when
+// wavesPerTask (COUNT mode, whole batch in one launch): 1 = the one-wave kernel; 2 / 4 / 8 / 16 = tile_mw_kernel, chosen by the host when
 // few tasks share a CU (pvol_api.hip)
-extern "C" hipError_t pvol_launch_tile(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask) {
-    return tile->specOn ? launch_tile_t<true>(args, tile, fused, ldsBytes, candCap, stream, wavesPerTask)
-                        : launch_tile_t<false>(args, tile, fused, ldsBytes, candCap, stream, wavesPerTask);
+extern "C" hipError_t pvol_launch_tile(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask,
+                                       const char **form) {
+    return tile->specOn ? launch_tile_t<true>(args, tile, fused, ldsBytes, candCap, stream, wavesPerTask, form)
+                        : launch_tile_t<false>(args, tile, fused, ldsBytes, candCap, stream, wavesPerTask, form);
 }

@@ -98,6 +98,8 @@ def lib():
         L.pvol_download_radiance_photons.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_march_kernel_name.restype = C.c_char_p
+        L.pvol_tile_kernel_name.argtypes = [C.c_void_p]
+        L.pvol_tile_kernel_name.restype = C.c_char_p
         L.pvol_gaussian_filter_table.argtypes = [C.c_float, C.c_float, C.c_float, _f32p]
         L.pvol_gaussian_filter_table.restype = None
         L.pvol_compute_sub_window.argtypes = [C.POINTER(abi.Sampler), C.c_uint32, C.POINTER(C.c_int32)]
@@ -144,7 +146,7 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_get_li_coalescing_stats", "pvol_preprocess_group", "pvol_render_frame_group",
            "pvol_film_window_from_crop", "pvol_film_sample_extent", "pvol_render_tasks_window_device",
            "pvol_film_add_samples_window_device", "pvol_film_resolve_window_device", "pvol_render_frame_ranks_window",
-           "pvol_render_frame_group_window"]
+           "pvol_render_frame_group_window", "pvol_tile_kernel_name"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -465,6 +467,10 @@ class PhotonVolume:
 
     def march_kernel_name(self):
         return lib().pvol_march_kernel_name(self._h).decode()
+
+    def tile_kernel_name(self):
+        """The form of the tile pre-pass the last render batch launched ("" if none ran)."""
+        return lib().pvol_tile_kernel_name(self._h).decode()
 
     def kernel_time_ms(self, reset=False):
         avg = C.c_double()

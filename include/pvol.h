@@ -453,6 +453,10 @@ int pvol_kernel_time_ms(pvol_ctx *ctx, double *avg_ms, uint64_t *launches, int r
 /* Name of the march+gather kernel the last batch was dispatched to ("li_group_kernel", "li_par_kernel",
  * "li_replay_kernel", "li_seq_kernel"; "" before the first batch): the kernel the time above belongs to. */
 const char *pvol_march_kernel_name(pvol_ctx *ctx);
+/* Form of the tile pre-pass the context's last pvol_render_tasks_device batch that ran one actually launched: "tile_kernel<count>",
+ * "tile_kernel<fused>", "tile_mw_kernel<2>", "<4>", "<8>" or "<16>" (the multi-wave COUNT form; a requested wave count is rounded down
+ * to one of these, and sliced launches take the one-wave kernel whatever was asked); "" before the first. */
+const char *pvol_tile_kernel_name(pvol_ctx *ctx);
 
 /* Per-phase device time of pvol_render_tasks_device, HIP events on the launch stream (off by default).  out[6], milliseconds
  * summed since the last reset: [0] tile pre-pass (LDSampler + camera + Scene::Intersect clip + draw count: tile_kernel),

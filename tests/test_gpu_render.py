@@ -325,7 +325,7 @@ def test_specular_recursion_matches_reference_capture(torch_cuda, name):
         pv.close()
 
 
-@pytest.mark.parametrize("waves", ["1", "4"])
+@pytest.mark.parametrize("waves", ["1", "2", "4", "8", "16"])
 def test_specular_recursion_one_light_matches_oracle(torch_cuda, orc, waves):
     """The COUNT form of the pre-pass (one light: no drawn value reaches a result, the tree's draws are counted, one camera sample
     per lane) on pinkfloyd without its point light, glass with a reflective lobe as well (a real tree, not a chain), against

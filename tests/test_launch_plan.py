@@ -164,6 +164,11 @@ def test_plan_sizes(lib):
     assert p.sliceM % 256 == 0 and p.sliceM == (100000 + 63) // 64 * 64 // 256 * 256
     assert p.tileWavesPerTask == 1 and plan(lib, **TILE).tileWavesPerTask == 4       # FUSED: one wave; COUNT with 4 tasks on 256 CUs
     assert plan(lib, **dict(TILE, nStreams=4096)).tileWavesPerTask == 1 and plan(lib, **dict(TILE, tileWaves=8)).tileWavesPerTask == 8
+    # tile_waves_per_task at its thresholds on 256 CUs: 12 tasks a CU and more one wave, 3 and more two, fewer four
+    for n_streams, waves in [(3072, 1), (3071, 2), (768, 2), (767, 4)]:
+        assert plan(lib, **dict(TILE, nStreams=n_streams)).tileWavesPerTask == waves
+    for tile_waves in (0, 2, 16):                                     # FUSED ignores tileWaves
+        assert plan(lib, **dict(TWO, tileWaves=tile_waves)).tileWavesPerTask == 1
     # nused beyond the bucket plan: 64 list entries a ray, the list within 8 GB
     cap = (8 << 30) // DEFER_REC
     p = plan(lib, hasInit=1, nUsed=500, nStreams=1024, maxRays=1 << 20, nRays=1 << 30)
