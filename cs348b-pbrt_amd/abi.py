@@ -18,7 +18,7 @@ PVOL_E_UNSUPPORTED = -5
 PVOL_E_LIMIT = -6
 PVOL_E_SHOOT_FAILED = -7
 
-VOLUME_NONE, VOLUME_HOMOGENEOUS, VOLUME_GRID, VOLUME_RAINBOW = 0, 1, 2, 3
+VOLUME_NONE, VOLUME_HOMOGENEOUS, VOLUME_GRID, VOLUME_RAINBOW, VOLUME_EXPONENTIAL = 0, 1, 2, 3, 4
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT = 0, 1, 2
 MATERIAL_MATTE, MATERIAL_GLASS = 0, 1
 OUT_SPECTRAL, OUT_XYZ = 0, 1
@@ -137,6 +137,10 @@ class SceneHolder:
         if v.kind == VOLUME_GRID:
             self.density = np.ascontiguousarray(b["vol.density"], dtype=np.float32)
             assert self.density.size == v.nx * v.ny * v.nz
+            v.density = self.density.ctypes.data_as(C.POINTER(C.c_float))
+        elif v.kind == VOLUME_EXPONENTIAL:   # {a, b, updir} as the scene gives them (pvol.h: pvol_volume.density), no grid
+            self.density = np.concatenate([np.asarray(b["vol.exp"], np.float32).reshape(2), np.asarray(b["vol.updir"], np.float32).reshape(3)])
+            v.nx = v.ny = v.nz = 0
             v.density = self.density.ctypes.data_as(C.POINTER(C.c_float))
         nl = len(b["lights.kind"])
         self.lights = (Light * max(nl, 1))()

@@ -238,6 +238,32 @@ int pvol_push_scene(pvol_ctx *c) {
     return ok(hipMemcpy(c->ds, &c->hs, sizeof(DevScene), hipMemcpyHostToDevice)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
+// Arguments of an exponential medium (pvol_volume.density = {a, b, updir}), checked without a device: every value finite, updir not
+// of zero length.  up3 gets Normalize(updir) with the reference's operations (core/geometry.h:94-98, :507: the vector divided by
+// its length, which Vector::operator/ does with one reciprocal and three products).
+int pvol_check_exponential(const pvol_volume *v, float *up3) {
+    if (!v || !v->density) return PVOL_E_INVALID;
+    const float *e = v->density;
+    for (int i = 0; i < 5; ++i) if (!(e[i] == e[i]) || fabsf(e[i]) == INFINITY) return PVOL_E_INVALID;
+    const float length = sqrtf(e[2] * e[2] + e[3] * e[3] + e[4] * e[4]);
+    if (!(length > 0.f) || length == INFINITY) return PVOL_E_INVALID;
+    const float inv = 1.f / length;
+    if (up3) for (int i = 0; i < 3; ++i) up3[i] = e[2 + i] * inv;
+    return PVOL_OK;
+}
+
+// a * expf(-b * height) is monotone in the height and the height is linear in the point: the maximum over the extent is at a corner
+float pvol_exponential_max_density(const pvol_volume *v, const float *up3) {
+    float md = 0.f;
+    for (int k = 0; k < 8; ++k) {
+        const float d[3] = {(k & 1) ? v->extent_max[0] - v->extent_min[0] : 0.f, (k & 2) ? v->extent_max[1] - v->extent_min[1] : 0.f,
+                            (k & 4) ? v->extent_max[2] - v->extent_min[2] : 0.f};
+        const float height = d[0] * up3[0] + d[1] * up3[1] + d[2] * up3[2];
+        md = std::max(md, v->density[0] * expf(-v->density[1] * height));
+    }
+    return md;
+}
+
 int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
     if (!c || !s) return PVOL_E_INVALID;
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
@@ -245,7 +271,8 @@ int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
     // Everything is validated and built into temporaries first; the context changes only when nothing can fail any more
     // (a rejected scene leaves the previous one, including its density grid, in place).
     const pvol_volume &v = s->volume;
-    if (v.kind != PVOL_VOLUME_NONE && v.kind != PVOL_VOLUME_HOMOGENEOUS && v.kind != PVOL_VOLUME_GRID && v.kind != PVOL_VOLUME_RAINBOW)
+    if (v.kind != PVOL_VOLUME_NONE && v.kind != PVOL_VOLUME_HOMOGENEOUS && v.kind != PVOL_VOLUME_GRID && v.kind != PVOL_VOLUME_RAINBOW &&
+        v.kind != PVOL_VOLUME_EXPONENTIAL)
         return PVOL_E_UNSUPPORTED;
     if (s->n_lights > PVOL_MAX_LIGHTS || s->n_triangles > PVOL_BVH_MAX_TRIS) return PVOL_E_UNSUPPORTED;
     if ((s->n_lights && !s->lights) || (s->n_triangles && !s->triangles)) return PVOL_E_INVALID;
@@ -256,6 +283,10 @@ int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
         if (!(sp.radius > 0.f) || sp.material < 0 || (uint32_t)sp.material >= std::max(1u, s->n_materials)) return PVOL_E_INVALID;
     }
     if (v.kind == PVOL_VOLUME_GRID && (!v.density || v.nx < 1 || v.ny < 1 || v.nz < 1)) return PVOL_E_INVALID;
+    float expUp[3] = {0.f, 0.f, 0.f};
+    if (v.kind == PVOL_VOLUME_EXPONENTIAL && pvol_check_exponential(&v, expUp) != PVOL_OK) return PVOL_E_INVALID;
+    // (a density that overflows somewhere in the extent is a non-finite value of the medium as well)
+    if (v.kind == PVOL_VOLUME_EXPONENTIAL && pvol_exponential_max_density(&v, expUp) == INFINITY) return PVOL_E_INVALID;
     for (uint32_t i = 0; i < s->n_lights; ++i) {
         const int k = s->lights[i].kind;
         if (k != PVOL_LIGHT_POINT && k != PVOL_LIGHT_SPOT && k != PVOL_LIGHT_DISTANT) return PVOL_E_UNSUPPORTED;
@@ -270,6 +301,12 @@ int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
     h.g = v.g;
     h.nx = v.nx; h.ny = v.ny; h.nz = v.nz;
     h.density = 0;
+    h.expA = h.expB = 0.f;
+    for (int i = 0; i < 3; ++i) h.expUp[i] = 0.f;
+    if (v.kind == PVOL_VOLUME_EXPONENTIAL) {
+        h.expA = v.density[0]; h.expB = v.density[1];
+        for (int i = 0; i < 3; ++i) h.expUp[i] = expUp[i];
+    }
     h.nLights = (int)s->n_lights;
     for (uint32_t i = 0; i < s->n_lights; ++i) {
         const pvol_light &l = s->lights[i];
@@ -388,6 +425,7 @@ int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
         maxDensity = md;
         h.density = newDensity;
     }
+    if (v.kind == PVOL_VOLUME_EXPONENTIAL) maxDensity = pvol_exponential_max_density(&v, h.expUp);
     // commit: kernels of earlier batches may still read the old scene and grid
     if (!ok(hipDeviceSynchronize()) || !ok(hipMemcpy(c->dsh, &hsh, sizeof(hsh), hipMemcpyHostToDevice)) ||
         !ok(hipMemcpy(c->ds, &h, sizeof(DevScene), hipMemcpyHostToDevice))) {
@@ -642,7 +680,7 @@ size_t pvol_rec_stride(int maxSteps, bool grid) {
 
 BatchPlan plan_path(const PlanIn &in) {
     BatchPlan p = {};
-    const bool tile = in.hasTile, grid = in.volKind == PVOL_VOLUME_GRID, homog = in.volKind == PVOL_VOLUME_HOMOGENEOUS;
+    const bool tile = in.hasTile, grid = is_density_region(in.volKind), homog = in.volKind == PVOL_VOLUME_HOMOGENEOUS;   // grid: a DensityRegion
     // Drawn VALUES cannot reach Li()'s result with at most one light and an analytic tau(): such scenes take the
     // ray-parallel kernel, backed by the sequential one if a ray reaches the roulette.
     const bool parOk = in.nLights <= 1 && !grid && !in.hasInit;
@@ -703,7 +741,7 @@ void plan_size(const PlanIn &in, BatchPlan &p) {
     if (p.tile == PVOL_TILE_FUSED) { p.ldsTile = pvol_tile_lds_bytes(in.maxSteps, in.spp, true, in.nTris, false); p.tileWavesPerTask = 1; }
     else if (p.tile != PVOL_TILE_NONE) { p.ldsTile = pvol_tile_lds_bytes(0, in.spp, false, in.nTris, in.distant != 0); p.tileWavesPerTask = tile_waves_per_task(in); }
     if (slicedPath) {
-        const size_t stride = pvol_rec_stride(in.maxSteps, in.volKind == PVOL_VOLUME_GRID);
+        const size_t stride = pvol_rec_stride(in.maxSteps, is_density_region(in.volKind));
         size_t m = ((size_t)4 << 30) / (stride * (size_t)in.nStreams);   // the record budget
         // nused beyond the bucket plan hands every dense lookup of a slice to the exact pass: keep that list within 8 GB
         if (in.nUsed > 100) m = std::min<size_t>(m, std::max<size_t>(64, (((size_t)8 << 30) / sizeof(DeferRec) / 64) / (size_t)in.nStreams));
@@ -760,9 +798,10 @@ LaunchKnobs pvol_read_knobs() {
 static bool roulette_possible(const pvol_ctx *c) {
     float m = 0.f;
     for (int i = 0; i < PVOL_NBINS; ++i) m = std::max(m, c->hs.sigA[i] + c->hs.sigS[i]);
-    // VolumeGrid: trilinear interpolation never exceeds the grid maximum, and the stepped tau() of a segment (samples every
-    // stepSize/2, DensityRegion::tau) can overshoot the segment by one sample: 1.5 x stepSize bounds it
-    const float dens = c->hs.volKind == PVOL_VOLUME_GRID ? 1.5f * c->maxDensity : 1.f;
+    // VolumeGrid: trilinear interpolation never exceeds the grid maximum (exponential: the maximum over the extent's corners), and
+    // the stepped tau() of a segment (samples every stepSize/2, DensityRegion::tau) can overshoot the segment by one sample:
+    // 1.5 x stepSize bounds it
+    const float dens = is_density_region(c->hs.volKind) ? 1.5f * c->maxDensity : 1.f;
     return !(c->hs.stepSize * m * dens < 6.8f);
 }
 
@@ -861,12 +900,13 @@ static int spec_finish(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, cons
     sa.records = pvol_buf<unsigned char>(c, PVOL_BUF_SEG_RECORDS); sa.sliceM = (uint32_t)cap; sa.sliceK = 0; sa.state = 0; sa.status = 0;
     const uint32_t nWaves = (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 16ull);
     if (!ok(hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), b.stream))) return PVOL_E_NO_DEVICE;
-    hipError_t e = replay ? pvol_launch_li_replay(&sa, p.ldsPar, c->hs.candCap, nWaves, b.stream)
-                          : pvol_launch_li_par(&sa, p.ldsPar, c->hs.candCap, false, nWaves, b.stream);
+    const RegionLaunchers &K = pvol_launchers(c->hs.volKind);
+    hipError_t e = replay ? K.liReplay(&sa, p.ldsPar, c->hs.candCap, nWaves, b.stream)
+                          : K.liPar(&sa, p.ldsPar, c->hs.candCap, false, nWaves, b.stream);
     if (!ok(e)) return PVOL_E_NO_DEVICE;
     SurfArgs su = {};
     su.scene = c->ds; su.rays = segRays; su.nRays = (uint32_t)cap; su.out = segOut; su.tau = 0; su.surfOut = 0; su.counters = c->dCounters; su.link = 0; su.spectral = 1;
-    if (!ok(pvol_launch_surface(&su, (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 24ull), b.stream))) return PVOL_E_NO_DEVICE;
+    if (!ok(K.surface(&su, (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 24ull), b.stream))) return PVOL_E_NO_DEVICE;
     SpecComposeArgs ca = {};
     ca.scene = c->ds; ca.link = pvol_buf<uint32_t>(c, PVOL_BUF_SPEC_LINK); ca.info = pvol_buf<SegInfo>(c, PVOL_BUF_SEG_INFO); ca.segOut = segOut; ca.tau = a.tauOut;
     ca.out = b.out; ca.surfOut = b.specSurfOut; ca.first = 0; ca.nRays = b.nRays;
@@ -877,14 +917,15 @@ static int spec_finish(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, cons
 // sampler + camera pre-pass that COUNTs Li()'s draws for the whole batch, once (`t`: the batch as one slice)
 static int run_tile_count(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, const LiArgs &t, const TileArgs *tile) {
     pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
-    return ok(pvol_launch_tile(&t, tile, false, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, &c->lastTileKernel)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return ok(pvol_launchers(c->hs.volKind).tile(&t, tile, false, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, &c->lastTileKernel)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 static int run_par(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a) {
-    hipError_t e = p.groupForm ? pvol_launch_li_group(&a, p.ldsGroup, c->hs.candCap, c->statsOn, p.gWaves, p.fixWaves, 0, b.stream)
-                               : pvol_launch_li_par(&a, p.ldsPar, c->hs.candCap, c->statsOn, p.nWaves, b.stream);
+    const RegionLaunchers &K = pvol_launchers(c->hs.volKind);
+    hipError_t e = p.groupForm ? K.liGroup(&a, p.ldsGroup, c->hs.candCap, c->statsOn, p.gWaves, p.fixWaves, 0, b.stream)
+                               : K.liPar(&a, p.ldsPar, c->hs.candCap, c->statsOn, p.nWaves, b.stream);
     if (ok(e)) {   // runs only if a ray raised needSeq (gate read on the device: no host sync here)
         a.gated = 1;
-        e = pvol_launch_li_seq(&a, p.ldsSeq, c->hs.candCap, c->statsOn, b.stream);
+        e = K.liSeq(&a, p.ldsSeq, c->hs.candCap, c->statsOn, b.stream);
         a.gated = 0;
     }
     if (!ok(e)) return PVOL_E_NO_DEVICE;
@@ -899,16 +940,17 @@ static int run_sliced(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArg
         t.sliceK = 0; t.sliceM = 0xffffffc0u; t.state = 0;
         if (run_tile_count(c, b, p, t, tile) != PVOL_OK) return PVOL_E_NO_DEVICE;
     }
+    const RegionLaunchers &K = pvol_launchers(c->hs.volKind);
     for (uint32_t k = 0; k < p.nSlices; ++k) {
         a.sliceK = k;
         hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), b.stream);
         if (p.specCap && spec_pool_reset(c, tile, p.specCap, b.stream) != PVOL_OK) return PVOL_E_NO_DEVICE;
         if (p.tile == PVOL_TILE_FUSED) {
             pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
-            if (!ok(pvol_launch_tile(&a, tile, true, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, &c->lastTileKernel))) return PVOL_E_NO_DEVICE;
+            if (!ok(K.tile(&a, tile, true, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, &c->lastTileKernel))) return PVOL_E_NO_DEVICE;
         }
         pvol_phase_mark(c, b.stream, PVOL_PHASE_MARCH);   // incl. the RNG-only resolve pass of a slice where there is one
-        if (!ok(pvol_launch_li_slice(&a, p.ldsResolve, p.ldsPar, c->hs.candCap, c->statsOn, p.nWaves, b.stream, p.resolve != 0, p.groupForm, p.ldsGroup,
+        if (!ok(K.liSlice(&a, p.ldsResolve, p.ldsPar, c->hs.candCap, c->statsOn, p.nWaves, b.stream, p.resolve != 0, p.groupForm, p.ldsGroup,
                                      p.gWaves, p.fixWaves))) return PVOL_E_NO_DEVICE;
         // this slice's segments: their Li() from the records the pre-pass left, then the fold into the slice's camera samples
         if (p.specCap && spec_finish(c, b, p, a, true) != PVOL_OK) return PVOL_E_NO_DEVICE;
@@ -917,7 +959,7 @@ static int run_sliced(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArg
 }
 
 static int run_seq(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a) {
-    return ok(pvol_launch_li_seq(&a, p.ldsSeq, c->hs.candCap, c->statsOn, b.stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return ok(pvol_launchers(c->hs.volKind).liSeq(&a, p.ldsSeq, c->hs.candCap, c->statsOn, b.stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 // Scratch of the plan's sizes, all of it before the first enqueue of the batch.

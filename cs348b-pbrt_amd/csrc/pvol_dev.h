@@ -23,6 +23,13 @@
 #define PVOL_MAX_SPHERES 8
 #define PVOL_MAX_RING 8   // search radius in cells: rings of (dy,dz) rows, 8r rows per ring <= 64 lanes
 
+// the DensityRegions (core/volume.h:66-99): sigma_a/sigma_s/sigma_t/Lve are constant spectra times Density(WorldToVolume(p)), tau() is
+// the stepped sum with drawn offsets.  Host and device code alike ask this instead of naming a kind.
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline bool is_density_region(int kind) { return kind == PVOL_VOLUME_GRID || kind == PVOL_VOLUME_EXPONENTIAL; }
+
 struct DevLight {
     int32_t kind;
     float pos[3];
@@ -98,6 +105,8 @@ struct DevScene {
     float rkEstimate;         // k-th nearest distance^2 expected at the map's mean density (first guess of a cold lookup)
     DevSurface surf;                  // surface integrator, disabled unless pvol_set_surface_integrator enabled it
     const DevShootScene *shootScene;  // materials of the triangles (device copy of the shooter's scene)
+    // ExponentialDensity (volumes/exponential.h:43-68): density a * expf(-b * Dot(Pobj - extent.pMin, upDir)); upDir normalised on the host
+    float expA, expB, expUp[3];
 };
 
 // One lookup li_group_kernel hands to li_fixup_kernel (pvol_group_dev.h)

@@ -61,7 +61,7 @@ __global__ void scatter_photons_kernel(GridBuildArgs a, const uint32_t *order, f
     uint32_t src = order[j];
     float x = a.p[3 * src], y = a.p[3 * src + 1], z = a.p[3 * src + 2];
     bool inside = true;
-    if (a.volKind != PVOL_VOLUME_GRID) {
+    if (!is_density_region(a.volKind)) {
         const float *m = a.w2v;
         float xp = m[0] * x + m[1] * y + m[2] * z + m[3];
         float yp = m[4] * x + m[5] * y + m[6] * z + m[7];

@@ -44,7 +44,8 @@
 //   REPLAY  scenes where drawn VALUES reach the result (> 1 light: the per-step light choice; VolumeGrid: the tau() offsets): the
 //           rays come slice by slice with the per-step records of the RNG pre-pass (pvol_march.hip: li_geo / li_resolve_lite /
 //           li_resolve / the fused tile pre-pass), one record slot per ray, and the kernel neither counts draws nor touches streams;
-//   GRID    VolumeGridDensity (volumes/volumegrid.cpp:39-57): trilinear density per lane, DensityRegion::tau (core/volume.cpp:
+//   GRID    a DensityRegion -- VolumeGridDensity (volumes/volumegrid.cpp:39-57), trilinear density per lane, or in the second
+//           compilation (pvol_region_exp.h) ExponentialDensity (volumes/exponential.h:58-62) --, DensityRegion::tau (core/volume.cpp:
 //           296-310) stepped per lane with the recorded offsets.  tau_b = sigma_t_b x (a scalar), so the forward formulation holds.
 // nused > GRP_PLAN_KMAX (C3: 500) keeps only the fixed-radius plan: when everything within maxDist fits the bucket the lanes
 // with fewer than nused photons are served here (most of C3's lookups: < 10 photons -> 0), the dense ones go to li_fixup_kernel.
@@ -72,7 +73,7 @@ __device__ float grid_tau_lane(const DevScene &S, V3 o, V3 d, float mint, float 
     float dsum = 0.f;
     t0 += u * stepSize;
     while (t0 < t1) {
-        dsum += grid_density(S, xform_point(S.w2v, rn.o + rn.d * t0));
+        dsum += region_density(S, xform_point(S.w2v, rn.o + rn.d * t0));
         t0 += stepSize;
     }
     return dsum * stepSize;
@@ -478,7 +479,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                 if (act) tcur += step;
                 const V3 pv = xform_point(S.w2v, p);
                 // density factor of sigma_a / sigma_s / Le at p (homogeneous.h:64-75: inside ? 1 : 0; volume.h:81-92: Density(p))
-                const float dens = !act ? 0.f : (GRID ? grid_density(S, pv) : (box_inside(S.extLo, S.extHi, pv) ? 1.f : 0.f));
+                const float dens = !act ? 0.f : (GRID ? region_density(S, pv) : (box_inside(S.extLo, S.extHi, pv) ? 1.f : 0.f));
                 const bool inP = dens != 0.f;
                 float lenStep = 0.f;   // tau of the step = sigma_t x lenStep
                 if (act) {

@@ -37,6 +37,38 @@ extern "C" size_t pvol_tile_lds_bytes(int maxSteps, uint32_t spp, bool fused, in
 extern "C" hipError_t pvol_launch_tile(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask,
                                        const char **form);
 extern "C" hipError_t pvol_launch_li_par(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, hipStream_t stream);
+// The launchers of one compilation of the marching kernels: VolumeGridDensity (and every medium that is no density region) or, from
+// pvol_march_exp.hip, ExponentialDensity (pvol_region_exp.h).  The host asks pvol_launchers(kind) wherever a launched kernel may
+// evaluate a density; launchers that never do (spec_compose, spec_fill) are called directly.
+struct RegionLaunchers {
+    decltype(&pvol_launch_li_seq) liSeq;
+    decltype(&pvol_launch_li_slice) liSlice;
+    decltype(&pvol_launch_li_group) liGroup;
+    decltype(&pvol_launch_li_replay) liReplay;
+    decltype(&pvol_launch_li_par) liPar;
+    decltype(&pvol_launch_surface) surface;
+    decltype(&pvol_launch_tile) tile;
+};
+#if !PVOL_REGION_EXP   /* undefined or 0: the first compilation and the host units */
+extern "C" hipError_t pvol_launch_li_seq_exp(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, hipStream_t stream);
+extern "C" hipError_t pvol_launch_li_slice_exp(const LiArgs *args, size_t ldsResolve, size_t ldsReplay, int candCap, bool stats,
+                                               uint32_t nWaves, hipStream_t stream, bool resolve, int groupForm, size_t ldsGroup, uint32_t nGroupWaves,
+                                               uint32_t nFixWaves);
+extern "C" hipError_t pvol_launch_li_group_exp(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, uint32_t nFixWaves,
+                                               int replay, hipStream_t stream);
+extern "C" hipError_t pvol_launch_li_replay_exp(const LiArgs *args, size_t ldsReplay, int candCap, uint32_t nWaves, hipStream_t stream);
+extern "C" hipError_t pvol_launch_li_par_exp(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, hipStream_t stream);
+extern "C" hipError_t pvol_launch_surface_exp(const SurfArgs *a, uint32_t nWaves, hipStream_t stream);
+extern "C" hipError_t pvol_launch_tile_exp(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream,
+                                           int wavesPerTask, const char **form);
+static inline const RegionLaunchers &pvol_launchers(int volKind) {
+    static const RegionLaunchers base = {pvol_launch_li_seq, pvol_launch_li_slice, pvol_launch_li_group, pvol_launch_li_replay, pvol_launch_li_par,
+                                         pvol_launch_surface, pvol_launch_tile};
+    static const RegionLaunchers expo = {pvol_launch_li_seq_exp, pvol_launch_li_slice_exp, pvol_launch_li_group_exp, pvol_launch_li_replay_exp,
+                                         pvol_launch_li_par_exp, pvol_launch_surface_exp, pvol_launch_tile_exp};
+    return volKind == PVOL_VOLUME_EXPONENTIAL ? expo : base;
+}
+#endif
 extern "C" hipError_t pvol_build_grid(const GridBuildArgs *args, float4 *pos4, float4 *alpha4, float4 *wi4,
                                       uint32_t *cellStart, uint32_t *subStart, hipStream_t stream);
 extern "C" hipError_t pvol_build_bvh(const float *dTri, const int32_t *dMat, const int32_t *dFlip, uint32_t n, float pad, float4 *tris,
@@ -188,7 +220,7 @@ enum { PVOL_PATH_PAR, PVOL_PATH_SLICED, PVOL_PATH_SEQ };
 enum { PVOL_TILE_NONE, PVOL_TILE_COUNT, PVOL_TILE_GRID_COUNT, PVOL_TILE_FUSED };
 struct BatchPlan {
     int32_t rc, path, tile;
-    int32_t groupForm;        // li_group_kernel's form: 0 none, 1 homogeneous (PAR: no records), 2 VolumeGrid
+    int32_t groupForm;        // li_group_kernel's form: 0 none, 1 homogeneous (PAR: no records), 2 density region (VolumeGrid, exponential)
     int32_t fixGroup, liteResolve;
     int32_t resolve;          // SLICED: the slice runs its own resolve pass (no FUSED pre-pass wrote the records)
     uint32_t recStride, sliceM, nSlices, nWaves, gWaves, fixWaves; int32_t tileWavesPerTask;
@@ -217,6 +249,11 @@ int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream);
 void *pvol_rccl_symbol(const char *name);
 // plan_size(plan_path(in)) for the tests; like pvol_rccl_symbol not part of include/pvol.h
 void pvol_plan_batch(const PlanIn *in, BatchPlan *out);
+// pvol_set_scene's check of an exponential medium's arguments (PVOL_OK or PVOL_E_INVALID), reachable without a device for the tests;
+// up3 (optional) gets the normalised updir
+int pvol_check_exponential(const pvol_volume *v, float *up3);
+// the largest density of a checked exponential medium over its extent (feeds roulette_possible like a VolumeGrid's maximum); up3: the normalised updir
+float pvol_exponential_max_density(const pvol_volume *v, const float *up3);
 }
 
 // ImageFilm's crop window behind the *_window entry points: a NULL window is the whole frame (crop 0 1 0 1), which is what the

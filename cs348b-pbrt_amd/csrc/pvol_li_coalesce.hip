@@ -131,7 +131,7 @@ static void run_batch(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
     if (!c->haveScene) { for (uint32_t i = 0; i < n; ++i) req[i]->rc = PVOL_E_NO_SCENE; return; }
     if (!ok(hipSetDevice(c->params.device))) { for (uint32_t i = 0; i < n; ++i) req[i]->rc = PVOL_E_NO_DEVICE; return; }
-    const uint32_t piece = pvol_li_piece(c->hs.maxSteps, c->hs.volKind == PVOL_VOLUME_GRID, n);
+    const uint32_t piece = pvol_li_piece(c->hs.maxSteps, is_density_region(c->hs.volKind), n);
     for (uint32_t b = 0; b < n; b += piece) run_piece(c, req + b, std::min(piece, n - b));
 }
 

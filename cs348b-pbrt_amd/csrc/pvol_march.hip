@@ -452,7 +452,7 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
     const f4 Y = ld4(S.cieY, q);
     const int nLights = S.nLights;
     const bool rainbow = (S.volKind == PVOL_VOLUME_RAINBOW);
-    const bool grid = (S.volKind == PVOL_VOLUME_GRID);
+    const bool grid = is_region(S.volKind);
     RayD ray;
     ray.o = v3(pr.o[0], pr.o[1], pr.o[2]);
     ray.d = v3(pr.d[0], pr.d[1], pr.d[2]);
@@ -568,7 +568,7 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
                 tScale = 2.f;
                 recByte |= 0x80u;
             }
-            const float dens = analytic ? (inP ? 1.f : 0.f) : grid_density(S, pv);   // homogeneous.h:64-75 / volume.h:81-92
+            const float dens = analytic ? (inP ? 1.f : 0.f) : region_density(S, pv);   // homogeneous.h:64-75 / volume.h:81-92
             f4 ss = sigS * dens, sa = sigA * dens;
             f4 L_d = mk4(0.f), L_ii = mk4(0.f), L_i;
             const bool unit = (dens == 1.f);
@@ -691,7 +691,7 @@ template <bool STATS, int MODE, int NREG>
 __device__ int march_ray_blocked(const DevScene &S, const LiArgs &A, const pvol_ray &pr, Rng &rng, MarchLds &M, int lane,
                                  WaveCounters &wc, f4 *LvOut, f4 *TrOut, RayRec rec, TauRec *tauRec = nullptr) {
     static_assert(MODE == MODE_PAR || MODE == MODE_REPLAY, "ray-parallel modes only");
-    if (S.volKind == PVOL_VOLUME_GRID || S.volKind == PVOL_VOLUME_NONE || A.transmittanceOnly) return 2;
+    if (is_region(S.volKind) || S.volKind == PVOL_VOLUME_NONE || A.transmittanceOnly) return 2;
     const int q = lane & 7;
     const f4 sigA = ld4(S.sigA, q), sigS = ld4(S.sigS, q);
     const f4 sigT = sigA + sigS;
@@ -1073,7 +1073,7 @@ __global__ __launch_bounds__(LANES, PVOL_WPE) void li_resolve_kernel(LiArgs A) {
         __syncthreads();
     }
     WaveCounters wc = {};
-    const bool grid = (S.volKind == PVOL_VOLUME_GRID);
+    const bool grid = is_region(S.volKind);
     const uint32_t end = min(st.n_rays, begin + A.sliceM);
     for (uint32_t k = begin; k < end; ++k) {
         const size_t ri = (size_t)st.first_ray + k;
@@ -1119,7 +1119,7 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
     rng.draws = 0;
     WaveCounters wc = {};
     unsigned long long tk0 = STATS ? stamp() : 0ull;
-    const bool grid = (S.volKind == PVOL_VOLUME_GRID);
+    const bool grid = is_region(S.volKind);
     const uint32_t chunksPerSlice = (A.sliceM + CHUNK_RAYS - 1) / CHUNK_RAYS;
     const unsigned long long nChunks = (unsigned long long)chunksPerSlice * A.nStreams;
     for (;;) {
@@ -1183,7 +1183,7 @@ __device__ int geo_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr, R
         const bool on = lane < cnt;
         const V3 p = ray.o + ray.d * tMine;
         const V3 pv = xform_point(S.w2v, p);
-        const float dens = !on ? 0.f : (grid ? grid_density(S, pv) : (box_inside(S.extLo, S.extHi, pv) ? 1.f : 0.f));
+        const float dens = !on ? 0.f : (grid ? region_density(S, pv) : (box_inside(S.extLo, S.extHi, pv) ? 1.f : 0.f));
         unsigned int mask = 0u;
         if (on && dens != 0.f && !blackS1 && S.nLights > 0) {   // sigma_s * dens is black iff dens == 0 or sigma_s is
             mask = 0x80u;
@@ -1225,7 +1225,7 @@ __global__ __launch_bounds__(LANES) void li_geo_kernel(LiArgs A) {
     const DevScene &S = *A.scene;
     const int lane = threadIdx.x;
     const int q = lane & 7;
-    const bool grid = (S.volKind == PVOL_VOLUME_GRID);
+    const bool grid = is_region(S.volKind);
     const f4 sigS = ld4(S.sigS, q);
     const bool blackS1 = spec_is_black(sigS);
     unsigned int lightBlackMask = 0u;
@@ -1345,7 +1345,7 @@ __global__ __launch_bounds__(LANES) void li_resolve_lite_kernel(LiArgs A) {
         rng.draws = (A.sliceK == 0) ? st.start_draw : st.end_draw;
         __syncthreads();
     }
-    const bool grid = (S.volKind == PVOL_VOLUME_GRID);
+    const bool grid = is_region(S.volKind);
     const int nLights = S.nLights;
     const uint32_t end = min(st.n_rays, begin + A.sliceM);
     for (uint32_t k = begin; k < end; ++k) {
@@ -1395,7 +1395,7 @@ extern "C" hipError_t pvol_launch_li_par(const LiArgs *args, size_t ldsBytes, in
 }
 
 // one slice: resolve (wave per stream) then replay; chunkCounter must be zero before the replay.
-// groupForm: 0 = li_replay_kernel (one wave per ray), 1 / 2 = li_group_kernel's replay form (homogeneous / VolumeGrid: one ray per lane)
+// groupForm: 0 = li_replay_kernel (one wave per ray), 1 / 2 = li_group_kernel's replay form (homogeneous / density region: one ray per lane)
 // followed by its exact-lookup pass and, gated on a hand-over list overflow, li_replay_kernel as the backup
 extern "C" hipError_t pvol_launch_li_group(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, uint32_t nFixWaves,
                                            int replay, hipStream_t stream);

@@ -247,11 +247,30 @@ __device__ float grid_density(const DevScene &S, V3 Pobj) {
     float d1 = lerpf(dy, d01, d11);
     return lerpf(dz, d0, d1);
 }
+// ExponentialDensity::Density, volumes/exponential.h:58-62
+__device__ __forceinline__ float exp_density(const DevScene &S, V3 Pobj) {
+    if (!box_inside(S.extLo, S.extHi, Pobj)) return 0.f;
+    const float height = dot(Pobj - v3(S.extLo[0], S.extLo[1], S.extLo[2]), v3(S.expUp[0], S.expUp[1], S.expUp[2]));
+    return S.expA * expf(-S.expB * height);
+}
+// The density region of this compilation.  Every kernel that marches a medium is compiled twice (pvol_region_exp.h): once with
+// VolumeGridDensity::Density, once with ExponentialDensity::Density, so neither form carries the other's code or registers.  Device
+// code asks is_region(); host code asks is_density_region() (pvol_dev.h) and picks the launcher of the scene's kind.
+#ifndef PVOL_REGION_EXP
+#define PVOL_REGION_EXP 0
+#endif
+#if PVOL_REGION_EXP
+#define is_region(kind) ((kind) == PVOL_VOLUME_EXPONENTIAL)
+#define region_density exp_density
+#else   /* the very expressions the kernels held before there was a second region */
+#define is_region(kind) ((kind) == PVOL_VOLUME_GRID)
+#define region_density grid_density
+#endif
 // density factor of sigma_a/sigma_s/sigma_t/Lve at a world point: homogeneous.h:64-75 (Inside ? 1 : 0),
 // core/volume.h:81-92 (Density)
 __device__ __forceinline__ float vol_density(const DevScene &S, V3 p) {
     V3 q = xform_point(S.w2v, p);
-    if (S.volKind == PVOL_VOLUME_GRID) return grid_density(S, q);
+    if (is_region(S.volKind)) return region_density(S, q);
     return box_inside(S.extLo, S.extHi, q) ? 1.f : 0.f;
 }
 // HG phase (core/volume.cpp:150-154); homogeneous p() also tests Inside (homogeneous.h:76-79)
@@ -262,12 +281,12 @@ __device__ __forceinline__ float phase_hg(V3 w, V3 wp, float g) {
     return 1.f / (4.f * K_PI) * (1.f - g * g) / powf(1.f + g * g - 2.f * g * costheta, 1.5f);
 }
 __device__ __forceinline__ float vol_phase(const DevScene &S, V3 p, V3 wi, V3 wo) {
-    if (S.volKind != PVOL_VOLUME_GRID && !box_inside(S.extLo, S.extHi, xform_point(S.w2v, p))) return 0.f;
+    if (!is_region(S.volKind) && !box_inside(S.extLo, S.extHi, xform_point(S.w2v, p))) return 0.f;
     return phase_hg(wi, wo, S.g);
 }
 // tau(): homogeneous.h:80-84 analytic; DensityRegion::tau core/volume.cpp:296-310 stepped.
 __device__ f4 vol_tau(const DevScene &S, const RayD &r, float stepSize, float u, f4 sigT) {
-    if (S.volKind != PVOL_VOLUME_GRID) {
+    if (!is_region(S.volKind)) {
         float t0, t1;
         if (!vol_intersect(S, r, &t0, &t1)) return mk4(0.f);
         V3 a = r.o + r.d * t0, b = r.o + r.d * t1;

@@ -130,7 +130,7 @@ __device__ float transmittance_bins(const DevScene &S, V3 o, V3 d, float mint, f
     if (S.volKind == PVOL_VOLUME_NONE) return 1.f;
     RayD r;
     r.o = o; r.d = d; r.mint = mint; r.maxt = maxt;
-    if (S.volKind != PVOL_VOLUME_GRID) {   // homogeneous.h:80-84
+    if (!is_region(S.volKind)) {   // homogeneous.h:80-84
         float t0, t1, lenAB = 0.f;
         const bool hit = vol_intersect(S, r, &t0, &t1);
         if (hit) { V3 a = o + d * t0, b = o + d * t1; lenAB = len(a - b); }
@@ -147,7 +147,7 @@ __device__ float transmittance_bins(const DevScene &S, V3 o, V3 d, float mint, f
     t0 += offset * step;
     float tau = 0.f;
     while (t0 < t1) {
-        const float D = grid_density(S, xform_point(S.w2v, rn.o + rn.d * t0));
+        const float D = region_density(S, xform_point(S.w2v, rn.o + rn.d * t0));
         tau += sigTl * D;
         t0 += step;
     }
@@ -468,7 +468,7 @@ __device__ int march_grid(PathCtx &C, V3 rayO, V3 dn, float t_i, float *t0io, fl
         if (hit) {
             float tt = ta + offset * step;
             while (tt < tb && K < GRID_KMAX) {
-                C.dbuf[K * LANES + lane] = grid_density(S, xform_point(S.w2v, rn.o + rn.d * tt));
+                C.dbuf[K * LANES + lane] = region_density(S, xform_point(S.w2v, rn.o + rn.d * tt));
                 ++K;
                 tt += step;
             }
@@ -534,7 +534,7 @@ __device__ void follow_photon(PathCtx &C, V3 rayO, V3 rayD, float rayMint, float
             const float t_i = t0;
             const float xi = rng_float<true>(C.rng, lane);
             bool interaction = false;
-            if (S.volKind != PVOL_VOLUME_GRID) {
+            if (!is_region(S.volKind)) {
                 interaction = march_analytic(C, rayO, rn.d, t_i, &t0, t1, xi, lane);
             } else {
                 int g = march_grid(C, rayO, rn.d, t_i, &t0, t1, xi, lane);

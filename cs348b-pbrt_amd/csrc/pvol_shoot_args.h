@@ -74,6 +74,9 @@ struct PlaceArgs {
 
 extern "C" {
 hipError_t pvol_launch_shoot(const ShootArgs *a, hipStream_t stream);
+#if !PVOL_REGION_EXP   /* undefined or 0: the first compilation and the host units */
+hipError_t pvol_launch_shoot_exp(const ShootArgs *a, hipStream_t stream);   // pvol_shoot_exp.hip: through an exponential medium
+#endif
 size_t pvol_shoot_state_words(void);
 hipError_t pvol_launch_merge(const MergeArgs *m, hipStream_t stream);
 hipError_t pvol_launch_merge_surface(const SurfMergeArgs *m, hipStream_t stream);

@@ -311,11 +311,13 @@ int shoot(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, Ex
     A.scene = c->ds; A.shoot = c->dsh; A.nTasks = L; A.stateIn = B.stateA; A.stateOut = B.stateA; A.halton = B.halton; A.flags = B.flags;
     A.localPhotons = B.localPhotons; A.localCounts = B.localCounts; A.cap = cap; A.stats = B.stats; A.init = 1;
     A.localSurf = B.localSurf; A.localSurfKind = B.localSurfKind; A.capS = capS; A.localRad = B.localRad; A.capR = capR; A.keepSurface = keep ? 1 : 0;
-    A.gridVolume = c->hs.volKind == PVOL_VOLUME_GRID ? 1 : 0;
+    A.gridVolume = is_density_region(c->hs.volKind) ? 1 : 0;
+    // the shooter's compilation for the medium's Density() (pvol_region_exp.h)
+    const auto launchShoot = c->hs.volKind == PVOL_VOLUME_EXPONENTIAL ? pvol_launch_shoot_exp : pvol_launch_shoot;
     A.blockPaths = blockSize;
     A.taskIds = B.taskIds;   // null with no communicator: slot == task
     if (localRc == PVOL_OK && L && !((!X.comm || ok(hipMemcpy(B.taskIds, ids.data(), sizeof(uint32_t) * L, hipMemcpyHostToDevice))) &&
-                                     ok(pvol_launch_shoot(&A, 0)) && ok(hipDeviceSynchronize())))
+                                     ok(launchShoot(&A, 0)) && ok(hipDeviceSynchronize())))
         localRc = PVOL_E_NO_DEVICE;
     A.init = 0;
     A.stateOut = B.stateB;
@@ -357,7 +359,7 @@ int shoot(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, Ex
             redo = false;
             if (localRc != PVOL_OK || !L) break;
             unsigned long long rs[8];
-            if (!ok(hipMemset(B.stats, 0, sizeof(rs))) || !ok(pvol_launch_shoot(&A, 0)) ||
+            if (!ok(hipMemset(B.stats, 0, sizeof(rs))) || !ok(launchShoot(&A, 0)) ||
                 !ok(hipMemcpy(localCounts, B.localCounts, sizeof(uint32_t) * 8 * (size_t)L, hipMemcpyDeviceToHost)) ||
                 !ok(hipMemcpy(rs, B.stats, sizeof(rs), hipMemcpyDeviceToHost))) { localRc = PVOL_E_NO_DEVICE; break; }
             uint32_t most = 0, mostS = 0, mostR = 0;

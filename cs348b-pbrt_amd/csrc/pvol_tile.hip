@@ -369,7 +369,7 @@ extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *c
                 sa.counters = c->dCounters;
                 const unsigned long long groups = (nRays + 63) / 64;
                 pvol_phase_mark(c, stream, PVOL_PHASE_SURFACE);
-                if (!ok(pvol_launch_surface(&sa, (uint32_t)std::min<unsigned long long>(groups, (unsigned long long)c->nCU * 24ull), stream)))
+                if (!ok(pvol_launchers(c->hs.volKind).surface(&sa, (uint32_t)std::min<unsigned long long>(groups, (unsigned long long)c->nCU * 24ull), stream)))
                     return PVOL_E_NO_DEVICE;
             }
             pvol_phase_mark(c, stream, PVOL_PHASE_FILM);

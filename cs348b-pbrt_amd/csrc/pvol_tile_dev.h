@@ -185,7 +185,7 @@ __device__ uint32_t tile_count_draws(const DevScene &S, const CountConsts &C, co
             if (nSlices > 1 && ((j >> 1) % nSlices) != slice) continue;
             const V3 pvA = xform_point(C.w2v, pA), pvB = xform_point(C.w2v, pB);
             bool inA, inB = j + 1 < nSamples;
-            if (C.volKind == PVOL_VOLUME_GRID) { inA = grid_density(S, pvA) != 0.f; inB = inB && grid_density(S, pvB) != 0.f; }
+            if (is_region(C.volKind)) { inA = region_density(S, pvA) != 0.f; inB = inB && region_density(S, pvB) != 0.f; }
             else { inA = box_inside(C.lo, C.hi, pvA); inB = inB && box_inside(C.lo, C.hi, pvB); }
             if (!inA && !inB) continue;
             bool occA = false, occB = false;
@@ -208,7 +208,7 @@ __device__ uint32_t tile_count_draws(const DevScene &S, const CountConsts &C, co
         if (nSlices > 1 && (j % nSlices) != slice) continue;
         const V3 pv = xform_point(C.w2v, p);
         // sigma_s(p) black: outside a homogeneous extent, or zero density of a VolumeGrid (volumegrid.cpp:39-57)
-        if (C.volKind == PVOL_VOLUME_GRID ? grid_density(S, pv) == 0.f : !box_inside(C.lo, C.hi, pv)) continue;
+        if (is_region(C.volKind) ? region_density(S, pv) == 0.f : !box_inside(C.lo, C.hi, pv)) continue;
         RayD vis;
         if (C.lightKind == PVOL_LIGHT_DISTANT) {
             vis.o = p; vis.d = v3(C.ldir[0], C.ldir[1], C.ldir[2]); vis.mint = 0.f; vis.maxt = INFINITY;
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
         __syncthreads();
     }
     WaveCounters wc = {};
-    const bool grid = (S.volKind == PVOL_VOLUME_GRID);
+    const bool grid = is_region(S.volKind);
     const uint32_t end = min(st.n_rays, begin + A.sliceM);
     const int4 w = T.windows[sidx];
     const uint32_t width = (uint32_t)(w.y - w.x);

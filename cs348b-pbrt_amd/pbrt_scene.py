@@ -7,7 +7,7 @@ Covered: Film "image" (resolution, cropwindow), Sampler "lowdiscrepancy" (pixels
 VolumeIntegrator "photonvolume" parameters (incl. what CreatePhotonShooter reads from both, core/photonshooter.cpp:529-548),
 Camera "perspective", the transform directives (Identity, Translate, Scale, Rotate, LookAt, Transform, ConcatTransform,
 TransformBegin/End, AttributeBegin/End, ReverseOrientation), WorldBegin/End, LightSource "point" / "spot" / "distant", Material
-"matte" / "glass" (with the fork's "Vn"), Shape "trianglemesh" / "sphere", Volume "homogeneous" / "rainbow" / "volumegrid", Include.
+"matte" / "glass" (with the fork's "Vn"), Shape "trianglemesh" / "sphere", Volume "homogeneous" / "rainbow" / "volumegrid" / "exponential", Include.
 Anything else raises Unsupported with the directive's name and line: nothing is skipped silently.
 
 Arithmetic is float32 in the reference's operation order (Matrix4x4::Mul, Transform::operator(), Rotate, LookAt, the
@@ -497,19 +497,22 @@ class _Builder:
         self.lights.append(L)
 
     def volume_region(self, name, ps):
-        kinds = {"homogeneous": 1, "volumegrid": 2, "rainbow": 3}
+        kinds = {"homogeneous": 1, "volumegrid": 2, "rainbow": 3, "exponential": 4}
         if name not in kinds:
             raise Unsupported('Volume "%s"' % name)
         if self.volume is not None:
             raise Unsupported("more than one Volume (AggregateVolume)")
         v = {"kind": kinds[name], "v2w": self.ctm, "sigma_a": ps.spectrum("sigma_a", 0.0), "sigma_s": ps.spectrum("sigma_s", 0.0),
              "le": ps.spectrum("Le", 0.0), "g": ps.f("g", 0.0), "p0": ps.point("p0", (0, 0, 0)), "p1": ps.point("p1", (1, 1, 1)),
-             "dims": np.zeros(3, np.int32), "density": None}
+             "dims": np.zeros(3, np.int32), "density": None, "exp": None}
         if name == "volumegrid":   # volumes/volumegrid.cpp:60-84
             v["dims"] = np.array([ps.i("nx", 1), ps.i("ny", 1), ps.i("nz", 1)], np.int32)
             v["density"] = np.array(ps.one("density", ("float",), []), F)
             if len(v["density"]) != int(np.prod(v["dims"])):
                 raise ValueError("volumegrid: density has %d values, nx*ny*nz = %d" % (len(v["density"]), int(np.prod(v["dims"]))))
+        if name == "exponential":   # volumes/exponential.cpp:39-53; updir stays as given (the library normalises it)
+            v["exp"] = np.array([ps.f("a", 1.0), ps.f("b", 1.0)], F)
+            v["updir"] = ps.point("updir", (0, 1, 0))
         self.volume = v
 
 
@@ -654,6 +657,9 @@ def load(path):
                   "vol.le": v["le"], "vol.g": np.array([v["g"]], F), "vol.dims": v["dims"]})
         if v["density"] is not None:
             d["vol.density"] = v["density"]
+        if v["exp"] is not None:
+            d["vol.exp"] = v["exp"]
+            d["vol.updir"] = np.asarray(v["updir"], F)
     L = b.lights
     d["lights.kind"] = np.array([x["kind"] for x in L], np.int32)
     d["lights.pos"] = np.concatenate([x["pos"] for x in L]).astype(F) if L else np.zeros(0, F)

@@ -52,7 +52,8 @@ typedef enum pvol_volume_kind {
     PVOL_VOLUME_NONE = 0,
     PVOL_VOLUME_HOMOGENEOUS = 1,  /* volumes/homogeneous.h:43-89 */
     PVOL_VOLUME_GRID = 2,         /* volumes/volumegrid.{h,cpp}  */
-    PVOL_VOLUME_RAINBOW = 3       /* volumes/rainbow.{h,cpp} (homogeneous + rainbowReflection) */
+    PVOL_VOLUME_RAINBOW = 3,      /* volumes/rainbow.{h,cpp} (homogeneous + rainbowReflection) */
+    PVOL_VOLUME_EXPONENTIAL = 4   /* volumes/exponential.h:43-68 (density a * expf(-b * height) inside the extent) */
 } pvol_volume_kind;
 
 typedef struct pvol_volume {
@@ -63,7 +64,10 @@ typedef struct pvol_volume {
     pvol_spectrum sigma_a, sigma_s, le;
     float g;                            /* HG asymmetry (core/volume.cpp:150-154)        */
     int32_t nx, ny, nz;                 /* grid only                                     */
-    const float *density;               /* grid only: nx*ny*nz floats, x fastest (volumegrid.h:60-65) */
+    const float *density;               /* grid: nx*ny*nz floats, x fastest (volumegrid.h:60-65).  exponential: 5 floats
+                                           {a, b, updir.x, updir.y, updir.z} with nx = ny = nz = 0; updir is as the scene
+                                           file gives it, pvol_set_scene normalises it as Normalize() does (exponential.h:51)
+                                           and answers PVOL_E_INVALID for NULL, a non-finite value or a zero-length updir */
 } pvol_volume;
 
 typedef enum pvol_light_kind {

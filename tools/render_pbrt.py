@@ -12,7 +12,7 @@ window's size, info["window"] says where it lies; the sampler then covers the wi
 random streams are those of the reference's crop render, not a cut-out of the full frame's.  The surface integrator (direct lighting +
 caustic estimate on matte surfaces) is switched on when the scene asks for "photonmap" and the device path
 covers it (matte and glass surfaces -- the specular recursion included --, a homogeneous or rainbow medium at any nused and
-phase function, or no medium; no indirect map); otherwise (a VolumeGrid, an indirect map) Ls = 0 and the image holds the
+phase function, or no medium; no indirect map); otherwise (a VolumeGrid or exponential medium, an indirect map) Ls = 0 and the image holds the
 volume term alone -- the tool says which.  info["render_s"]: wall seconds of the frame's render_tasks (shoot excluded)."""
 import argparse
 import importlib
