@@ -1,6 +1,6 @@
-// pvol_api.hip -- the C ABI of include/pvol.h: context, scene flattening to the device layout,
-// photon-map upload + grid build, kernel launches.  There is NO CPU fallback: every entry point
-// that needs the GPU returns PVOL_E_NO_DEVICE when HIP is unusable.
+// pvol_api.hip -- the C ABI of include/pvol.h: context lifetime, the plan of a batch, kernel launches, the host batches and the
+// statistics (the scene is in pvol_scene_host.hip, the photon maps in pvol_map_host.hip).  There is NO CPU fallback: every entry
+// point that needs the GPU returns PVOL_E_NO_DEVICE when HIP is unusable.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -67,37 +67,18 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     pvol_ctx *c = new (std::nothrow) pvol_ctx();
     if (!c) return PVOL_E_NO_MEMORY;
     c->params = *params;
-    c->haveScene = false;
-    memset(&c->hs, 0, sizeof(c->hs));
-    c->ds = 0; c->dDensity = 0;
-    c->nPhotons = 0;
-    c->dRawP = c->dRawWi = c->dRawAlpha = 0;
-    c->dPos4 = c->dAlpha4 = c->dWi4 = 0;
-    c->dCellStart = 0;
-    c->dCounters = 0;
-    c->dWords = 0;
-    c->nCU = 256;
     { const char *fs = getenv("PVOL_FORCE_SEQ"); c->forceSeq = fs && fs[0] == '1'; }
     { const char *ng = getenv("PVOL_NO_GROUP"); c->noGroup = ng && ng[0] == '1'; }
     { const char *nl = getenv("PVOL_NO_LITE"); c->noLite = nl && nl[0] == '1'; }
-    { const char *gw = getenv("PVOL_GROUP_WAVES"); c->groupWavesPerCU = gw ? std::max(1, atoi(gw)) : 12; }
-    { const char *tw = getenv("PVOL_TILE_WAVES"); c->tileWaves = tw ? std::max(0, atoi(tw)) : 0; }
+    { const char *gw = getenv("PVOL_GROUP_WAVES"); if (gw) c->groupWavesPerCU = std::max(1, atoi(gw)); }
+    { const char *tw = getenv("PVOL_TILE_WAVES"); if (tw) c->tileWaves = std::max(0, atoi(tw)); }
     // li_fixup_kernel / li_fixup_group_kernel waves per CU (C3, 8 spp frame: 16.3 s at 8, 13.9 s at 16)
-    { const char *fw = getenv("PVOL_FIX_WAVES"); c->fixWavesPerCU = fw ? std::max(1, atoi(fw)) : 16; }
+    { const char *fw = getenv("PVOL_FIX_WAVES"); if (fw) c->fixWavesPerCU = std::max(1, atoi(fw)); }
     // PVOL_LI_COALESCE=<max_batch>: the default of pvol_set_li_coalescing, for callers that cannot call it (an unchanged binding)
     { const char *lc = getenv("PVOL_LI_COALESCE"); const long v = lc ? atol(lc) : 0; c->coMaxBatch = (v > 1 && v <= PVOL_LI_MAX_BATCH) ? (uint32_t)v : 0u; }
     { hipDeviceProp_t prop; if (ok(hipGetDeviceProperties(&prop, params->device))) c->nCU = prop.multiProcessorCount; }
-    c->statsOn = false;
-    c->timeMs = 0; c->launches = 0;
-    c->dsh = 0;
-    memset(&c->hsh, 0, sizeof(c->hsh));
-    memset(c->shootStats, 0, sizeof(c->shootStats));
-    if (!ok(hipMalloc(&c->ds, sizeof(DevScene))) || !ok(hipMalloc(&c->dCounters, sizeof(DevCounters))) || !ok(hipMalloc(&c->dWords, 16)) ||
-        !ok(hipMalloc(&c->dsh, sizeof(DevShootScene))) || !ok(hipMemset(c->dCounters, 0, sizeof(DevCounters)))) {
-        if (c->ds) hipFree(c->ds);
-        if (c->dsh) hipFree(c->dsh);
-        if (c->dCounters) hipFree(c->dCounters);
-        if (c->dWords) hipFree(c->dWords);
+    if (!c->ds.alloc(1) || !c->dCounters.alloc(1) || !c->dWords.alloc(4) || !c->dsh.alloc(1) ||
+        !ok(hipMemset(c->dCounters.get(), 0, sizeof(DevCounters)))) {
         delete c;
         return PVOL_E_NO_DEVICE;
     }
@@ -105,127 +86,19 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     return PVOL_OK;
 }
 
-void pvol_free_photons(pvol_ctx *c) {
-    if (c->dRawP) hipFree(c->dRawP);
-    if (c->dRawWi) hipFree(c->dRawWi);
-    if (c->dRawAlpha) hipFree(c->dRawAlpha);
-    if (c->dPos4) hipFree(c->dPos4);
-    if (c->dAlpha4) hipFree(c->dAlpha4);
-    if (c->dWi4) hipFree(c->dWi4);
-    if (c->dCellStart) hipFree(c->dCellStart);
-    if (c->dSubStart) hipFree(c->dSubStart);
-    c->dSubStart = 0;
-    c->dRawP = c->dRawWi = c->dRawAlpha = 0;
-    c->dPos4 = c->dAlpha4 = c->dWi4 = 0;
-    c->dCellStart = 0;
-    c->nPhotons = 0;
-}
-
+// every device allocation of the context is held by an owner (pvol_host.h): deleting the context frees them
 void pvol_destroy(pvol_ctx *c) {
     if (!c) return;
     hipSetDevice(c->params.device);
     hipDeviceSynchronize();
-    pvol_free_photons(c);
-    pvol_free_surface_stores(c);
-    pvol_free_caustic_map(c);
-    for (DevBuf &b : c->buf) if (b.p) hipFree(b.p);
-    pvol_free_li_staging(c);
     for (auto &p : c->pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     for (auto &p : c->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     for (auto &p : c->phaseMarks) hipEventDestroy(p.second);
     for (auto &e : c->phasePool) hipEventDestroy(e);
-    if (c->dDensity) hipFree(c->dDensity);
-    if (c->dBvhNodes) hipFree(c->dBvhNodes);
-    if (c->dBvhTris) hipFree(c->dBvhTris);
     if (c->groupFilmEv) hipEventDestroy(c->groupFilmEv);
     if (c->groupStageEv) hipEventDestroy(c->groupStageEv);
-    if (c->ds) hipFree(c->ds);
-    if (c->dsh) hipFree(c->dsh);
-    if (c->dCounters) hipFree(c->dCounters);
-    if (c->dWords) hipFree(c->dWords);
+    pvol_free_li_staging(c);
     delete c;
-}
-
-// ---- host evaluation of the light-power CDF (ComputeLightSamplingCDF core/integrator.cpp:261-268,
-// Distribution1D montecarlo.h:56-76), fp32 in the reference's order (this file is built with
-// -ffp-contract=off)
-static float host_spec_y(const pvol_scene *s, const float *c30) {
-    float yy = 0.f;
-    for (int i = 0; i < 30; ++i) yy += s->cie_y.c[i] * c30[i];
-    return yy * float(700 - 400) / float(106.856895f * 30);
-}
-static void world_sphere(const pvol_scene *s, float c[3], float *rad) {   // BBox::BoundingSphere, core/geometry.cpp:60-63
-    bool inside = true;
-    for (int a = 0; a < 3; ++a) {
-        c[a] = .5f * s->world_min[a] + .5f * s->world_max[a];
-        inside = inside && c[a] >= s->world_min[a] && c[a] <= s->world_max[a];
-    }
-    float dx = c[0] - s->world_max[0], dy = c[1] - s->world_max[1], dz = c[2] - s->world_max[2];
-    *rad = inside ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.f;
-}
-static const float kPiF = 3.14159265358979323846f;
-static float light_power_y(const pvol_scene *s, const pvol_light &l, float worldRadius) {
-    float p[30];
-    for (int i = 0; i < 30; ++i) {
-        float I = l.intensity.c[i];
-        if (l.kind == PVOL_LIGHT_SPOT) p[i] = I * 2.f * kPiF * (1.f - .5f * (l.cos_falloff_start + l.cos_total_width));   // spot.cpp:72-75
-        else if (l.kind == PVOL_LIGHT_POINT) p[i] = I * (4.f * kPiF);                                                      // point.cpp:60-62
-        else p[i] = I * kPiF * worldRadius * worldRadius;                                                                  // distant.cpp:58-63
-    }
-    return host_spec_y(s, p);
-}
-
-static int fill_shoot_scene(const pvol_ctx *c, const pvol_scene *s, DevShootScene &H) {
-    memset(&H, 0, sizeof(H));
-    if (s->n_materials > PVOL_MAX_MATERIALS) return PVOL_E_UNSUPPORTED;
-    if (s->n_materials && !s->materials) return PVOL_E_INVALID;
-    H.nMats = (int)s->n_materials;
-    for (uint32_t i = 0; i < s->n_materials; ++i) {
-        const pvol_material &m = s->materials[i];
-        if (m.kind != PVOL_MATERIAL_MATTE && m.kind != PVOL_MATERIAL_GLASS) return PVOL_E_UNSUPPORTED;
-        DevMaterial &d = H.mats[i];
-        d.kind = m.kind; d.ior = m.ior; d.vn = m.vn; d.nBxdf = 0;
-        bool kdBlack = true, krBlack = true, ktBlack = true;
-        for (int b = 0; b < 30; ++b) {
-            d.kd[b] = m.kd.c[b]; d.kr[b] = m.kr.c[b]; d.kt[b] = m.kt.c[b];
-            kdBlack = kdBlack && m.kd.c[b] == 0.f; krBlack = krBlack && m.kr.c[b] == 0.f; ktBlack = ktBlack && m.kt.c[b] == 0.f;
-        }
-        if (m.kind == PVOL_MATERIAL_MATTE) { if (!kdBlack) d.bxdfType[d.nBxdf++] = 1 | 4; }          // Lambertian
-        else { if (!krBlack) d.bxdfType[d.nBxdf++] = 1 | 16; if (!ktBlack) d.bxdfType[d.nBxdf++] = 2 | 16; }
-    }
-    for (uint32_t i = 0; i < s->n_triangles; ++i) {
-        int mi = s->triangles[i].material;
-        if (mi < 0 || (uint32_t)mi >= std::max(1u, s->n_materials)) return PVOL_E_INVALID;
-        if (s->n_triangles <= PVOL_MAX_TRIS) {   // a larger scene keeps both in its hierarchy's leaves (pvol_bvh.hip)
-            H.triMat[i] = mi;
-            H.triFlip[i] = s->triangles[i].flip_normal;
-        }
-    }
-    world_sphere(s, H.worldCenter, &H.worldRadius);
-    int n = (int)s->n_lights;
-    for (int i = 0; i < n; ++i) {
-        memcpy(H.l2w[i], s->lights[i].light_to_world, sizeof(float) * 12);
-        H.lightFunc[i] = light_power_y(s, s->lights[i], H.worldRadius);
-    }
-    if (n > 0) {
-        H.lightCdf[0] = 0.f;
-        for (int i = 1; i < n + 1; ++i) H.lightCdf[i] = H.lightCdf[i - 1] + H.lightFunc[i - 1] / n;
-        H.lightFuncInt = H.lightCdf[n];
-        if (H.lightFuncInt == 0.f) { for (int i = 1; i < n + 1; ++i) H.lightCdf[i] = float(i) / float(n); }
-        else { for (int i = 1; i < n + 1; ++i) H.lightCdf[i] /= H.lightFuncInt; }
-    }
-    H.shooterStep = c->params.shooter_step_size;
-    H.maxPhotonDepth = c->params.max_photon_depth;
-    H.finalGather = c->params.final_gather;
-    H.nCausticWanted = c->params.n_caustic_photons;
-    H.nIndirectWanted = c->params.n_indirect_photons;
-    H.nVolumeWanted = c->params.n_volume_photons;
-    return PVOL_OK;
-}
-
-static void pad32(float *dst, const pvol_spectrum &s) {
-    for (int i = 0; i < 30; ++i) dst[i] = s.c[i];
-    dst[30] = dst[31] = 0.f;
 }
 
 int pvol_get_accel_info(pvol_ctx *c, double *out2) {
@@ -235,440 +108,7 @@ int pvol_get_accel_info(pvol_ctx *c, double *out2) {
 }
 
 int pvol_push_scene(pvol_ctx *c) {
-    return ok(hipMemcpy(c->ds, &c->hs, sizeof(DevScene), hipMemcpyHostToDevice)) ? PVOL_OK : PVOL_E_NO_DEVICE;
-}
-
-// Arguments of an exponential medium (pvol_volume.density = {a, b, updir}), checked without a device: every value finite, updir not
-// of zero length.  up3 gets Normalize(updir) with the reference's operations (core/geometry.h:94-98, :507: the vector divided by
-// its length, which Vector::operator/ does with one reciprocal and three products).
-int pvol_check_exponential(const pvol_volume *v, float *up3) {
-    if (!v || !v->density) return PVOL_E_INVALID;
-    const float *e = v->density;
-    for (int i = 0; i < 5; ++i) if (!(e[i] == e[i]) || fabsf(e[i]) == INFINITY) return PVOL_E_INVALID;
-    const float length = sqrtf(e[2] * e[2] + e[3] * e[3] + e[4] * e[4]);
-    if (!(length > 0.f) || length == INFINITY) return PVOL_E_INVALID;
-    const float inv = 1.f / length;
-    if (up3) for (int i = 0; i < 3; ++i) up3[i] = e[2 + i] * inv;
-    return PVOL_OK;
-}
-
-// a * expf(-b * height) is monotone in the height and the height is linear in the point: the maximum over the extent is at a corner
-float pvol_exponential_max_density(const pvol_volume *v, const float *up3) {
-    float md = 0.f;
-    for (int k = 0; k < 8; ++k) {
-        const float d[3] = {(k & 1) ? v->extent_max[0] - v->extent_min[0] : 0.f, (k & 2) ? v->extent_max[1] - v->extent_min[1] : 0.f,
-                            (k & 4) ? v->extent_max[2] - v->extent_min[2] : 0.f};
-        const float height = d[0] * up3[0] + d[1] * up3[1] + d[2] * up3[2];
-        md = std::max(md, v->density[0] * expf(-v->density[1] * height));
-    }
-    return md;
-}
-
-int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
-    if (!c || !s) return PVOL_E_INVALID;
-    std::lock_guard<std::recursive_mutex> api(c->apiMu);
-    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    // Everything is validated and built into temporaries first; the context changes only when nothing can fail any more
-    // (a rejected scene leaves the previous one, including its density grid, in place).
-    const pvol_volume &v = s->volume;
-    if (v.kind != PVOL_VOLUME_NONE && v.kind != PVOL_VOLUME_HOMOGENEOUS && v.kind != PVOL_VOLUME_GRID && v.kind != PVOL_VOLUME_RAINBOW &&
-        v.kind != PVOL_VOLUME_EXPONENTIAL)
-        return PVOL_E_UNSUPPORTED;
-    if (s->n_lights > PVOL_MAX_LIGHTS || s->n_triangles > PVOL_BVH_MAX_TRIS) return PVOL_E_UNSUPPORTED;
-    if ((s->n_lights && !s->lights) || (s->n_triangles && !s->triangles)) return PVOL_E_INVALID;
-    if (s->n_spheres > PVOL_MAX_SPHERES) return PVOL_E_UNSUPPORTED;
-    if (s->n_spheres && !s->spheres) return PVOL_E_INVALID;
-    for (uint32_t i = 0; i < s->n_spheres; ++i) {
-        const pvol_sphere &sp = s->spheres[i];
-        if (!(sp.radius > 0.f) || sp.material < 0 || (uint32_t)sp.material >= std::max(1u, s->n_materials)) return PVOL_E_INVALID;
-    }
-    if (v.kind == PVOL_VOLUME_GRID && (!v.density || v.nx < 1 || v.ny < 1 || v.nz < 1)) return PVOL_E_INVALID;
-    float expUp[3] = {0.f, 0.f, 0.f};
-    if (v.kind == PVOL_VOLUME_EXPONENTIAL && pvol_check_exponential(&v, expUp) != PVOL_OK) return PVOL_E_INVALID;
-    // (a density that overflows somewhere in the extent is a non-finite value of the medium as well)
-    if (v.kind == PVOL_VOLUME_EXPONENTIAL && pvol_exponential_max_density(&v, expUp) == INFINITY) return PVOL_E_INVALID;
-    for (uint32_t i = 0; i < s->n_lights; ++i) {
-        const int k = s->lights[i].kind;
-        if (k != PVOL_LIGHT_POINT && k != PVOL_LIGHT_SPOT && k != PVOL_LIGHT_DISTANT) return PVOL_E_UNSUPPORTED;
-    }
-    DevScene h = c->hs;   // keeps the photon-map fields, everything else is replaced
-    memset(&h.surf, 0, sizeof(h.surf));   // the surface integrator belongs to the scene it was enabled on
-    h.shootScene = c->dsh;
-    h.volKind = v.kind;
-    for (int i = 0; i < 3; ++i) { h.extLo[i] = v.extent_min[i]; h.extHi[i] = v.extent_max[i]; }
-    memcpy(h.w2v, v.world_to_volume, sizeof(h.w2v));
-    pad32(h.sigA, v.sigma_a); pad32(h.sigS, v.sigma_s); pad32(h.le, v.le);
-    h.g = v.g;
-    h.nx = v.nx; h.ny = v.ny; h.nz = v.nz;
-    h.density = 0;
-    h.expA = h.expB = 0.f;
-    for (int i = 0; i < 3; ++i) h.expUp[i] = 0.f;
-    if (v.kind == PVOL_VOLUME_EXPONENTIAL) {
-        h.expA = v.density[0]; h.expB = v.density[1];
-        for (int i = 0; i < 3; ++i) h.expUp[i] = expUp[i];
-    }
-    h.nLights = (int)s->n_lights;
-    for (uint32_t i = 0; i < s->n_lights; ++i) {
-        const pvol_light &l = s->lights[i];
-        DevLight &d = h.lights[i];
-        d.kind = l.kind;
-        for (int k = 0; k < 3; ++k) { d.pos[k] = l.pos[k]; d.dir[k] = l.dir[k]; }
-        memcpy(d.w2l, l.world_to_light, sizeof(float) * 12);
-        d.cosTotalWidth = l.cos_total_width;
-        d.cosFalloffStart = l.cos_falloff_start;
-        pad32(d.intensity, l.intensity);
-    }
-    h.nSpheres = (int)s->n_spheres;
-    memset(h.spheres, 0, sizeof(h.spheres));
-    for (uint32_t i = 0; i < s->n_spheres; ++i) {
-        const pvol_sphere &sp = s->spheres[i];
-        DevSphere &d = h.spheres[i];
-        memcpy(d.o2w, sp.object_to_world, sizeof(d.o2w));
-        memcpy(d.w2o, sp.world_to_object, sizeof(d.w2o));
-        d.radius = sp.radius; d.zmin = sp.z_min; d.zmax = sp.z_max; d.thetaMin = sp.theta_min; d.thetaMax = sp.theta_max; d.phiMax = sp.phi_max;
-        d.mat = sp.material; d.flip = sp.flip_normal;
-    }
-    const bool big = s->n_triangles > PVOL_MAX_TRIS;
-    h.nTris = big ? 0 : (int)s->n_triangles;
-    h.bvhNodes = 0; h.bvhTris = 0; h.nBvhTris = 0;
-    for (uint32_t i = 0; i < s->n_triangles && !big; ++i) {
-        const pvol_triangle &t = s->triangles[i];
-        for (int k = 0; k < 3; ++k) { h.tris[i].p1[k] = t.p[0][k]; h.tris[i].p2[k] = t.p[1][k]; h.tris[i].p3[k] = t.p[2][k]; }
-    }
-    pad32(h.cieX, s->cie_x); pad32(h.cieY, s->cie_y); pad32(h.cieZ, s->cie_z);
-    h.stepSize = c->params.step_size;
-    h.maxDist = c->params.max_dist;
-    h.maxDistSq = c->params.max_dist * c->params.max_dist;  // photonvolume.h:18
-    h.nUsed = c->params.n_used;
-    h.candCap = ((c->params.n_used + 63) / 64) * 64 + 192;
-    // march-step bound: diagonal of the volume's world bound / stepSize (rays are clipped to the extent)
-    h.maxSteps = 0;
-    // (every scene with a medium: a one-light homogeneous scene reaches the record plan too -- pvol_li with the caller's live
-    // RNG state takes the RESOLVE + REPLAY path -- and with maxSteps 0 every such ray was reported as PVOL_E_LIMIT)
-    if (v.kind != PVOL_VOLUME_NONE) {
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int k = 0; k < 8; ++k) {
-            float x = (k & 1) ? v.extent_max[0] : v.extent_min[0], y = (k & 2) ? v.extent_max[1] : v.extent_min[1],
-                  z = (k & 4) ? v.extent_max[2] : v.extent_min[2];
-            const float *m = v.volume_to_world;
-            float w[3] = {m[0] * x + m[1] * y + m[2] * z + m[3], m[4] * x + m[5] * y + m[6] * z + m[7], m[8] * x + m[9] * y + m[10] * z + m[11]};
-            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], w[a]); hi[a] = std::max(hi[a], w[a]); }
-        }
-        double diag = sqrt((double)(hi[0] - lo[0]) * (hi[0] - lo[0]) + (double)(hi[1] - lo[1]) * (hi[1] - lo[1]) + (double)(hi[2] - lo[2]) * (hi[2] - lo[2]));
-        double steps = diag / c->params.step_size * 1.05 + 4;
-        if (steps > 12000) return PVOL_E_LIMIT;
-        h.maxSteps = ((int)steps + 63) & ~63;
-    }
-    DevShootScene hsh;
-    {
-        int rc = fill_shoot_scene(c, s, hsh);
-        if (rc != PVOL_OK) return rc;
-    }
-    // more triangles than the embedded array: LBVH on the device
-    float4 *newNodes = 0, *newTris = 0;
-    double bvhMs = 0.0;
-    std::vector<int32_t> triMat(s->n_triangles);
-    for (uint32_t i = 0; i < s->n_triangles; ++i) triMat[i] = s->triangles[i].material;
-    for (uint32_t i = 0; i < s->n_spheres; ++i) triMat.push_back(s->spheres[i].material);   // the surface integrator's matte check covers them
-    if (big) {
-        const uint32_t n = s->n_triangles;
-        std::vector<float> tv((size_t)n * 9);
-        std::vector<int32_t> fl(n);
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < n; ++i) {
-            const pvol_triangle &t = s->triangles[i];
-            for (int v3i = 0; v3i < 3; ++v3i)
-                for (int k = 0; k < 3; ++k) {
-                    const float x = t.p[v3i][k];
-                    if (!(x == x) || fabsf(x) == INFINITY) return PVOL_E_INVALID;
-                    tv[(size_t)i * 9 + 3 * v3i + k] = x;
-                    lo[k] = std::min(lo[k], x); hi[k] = std::max(hi[k], x);
-                }
-            fl[i] = t.flip_normal;
-        }
-        const double diag = sqrt((double)(hi[0] - lo[0]) * (hi[0] - lo[0]) + (double)(hi[1] - lo[1]) * (hi[1] - lo[1]) +
-                                 (double)(hi[2] - lo[2]) * (hi[2] - lo[2]));
-        float *dTri = 0;
-        int32_t *dMat = 0, *dFlip = 0;
-        bool good = ok(hipMalloc(&dTri, tv.size() * 4)) && ok(hipMalloc(&dMat, (size_t)n * 4)) && ok(hipMalloc(&dFlip, (size_t)n * 4)) &&
-                    ok(hipMalloc(&newTris, (size_t)n * 3 * sizeof(float4))) && ok(hipMalloc(&newNodes, (size_t)(n - 1) * 4 * sizeof(float4))) &&
-                    ok(hipMemcpy(dTri, tv.data(), tv.size() * 4, hipMemcpyHostToDevice)) &&
-                    ok(hipMemcpy(dMat, triMat.data(), (size_t)n * 4, hipMemcpyHostToDevice)) &&
-                    ok(hipMemcpy(dFlip, fl.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        if (good) {
-            hipEvent_t e0, e1;
-            hipEventCreate(&e0); hipEventCreate(&e1);
-            hipEventRecord(e0, 0);
-            good = ok(pvol_build_bvh(dTri, dMat, dFlip, n, (float)(1e-5 * diag), newTris, newNodes, 0));
-            hipEventRecord(e1, 0);
-            hipEventSynchronize(e1);
-            float ms = 0.f;
-            hipEventElapsedTime(&ms, e0, e1);
-            bvhMs = ms;
-            hipEventDestroy(e0); hipEventDestroy(e1);
-        }
-        if (dTri) hipFree(dTri);
-        if (dMat) hipFree(dMat);
-        if (dFlip) hipFree(dFlip);
-        if (!good) { if (newTris) hipFree(newTris); if (newNodes) hipFree(newNodes); return PVOL_E_NO_MEMORY; }
-        h.bvhNodes = newNodes; h.bvhTris = newTris; h.nBvhTris = (int)n;
-    }
-    float *newDensity = 0;
-    float maxDensity = 1.f;
-    if (v.kind == PVOL_VOLUME_GRID) {
-        size_t nb = sizeof(float) * (size_t)v.nx * v.ny * v.nz;
-        auto dropBvh = [&]() { if (newTris) hipFree(newTris); if (newNodes) hipFree(newNodes); };
-        if (!ok(hipMalloc(&newDensity, nb))) { dropBvh(); return PVOL_E_NO_MEMORY; }
-        if (!ok(hipMemcpy(newDensity, v.density, nb, hipMemcpyHostToDevice))) { hipFree(newDensity); dropBvh(); return PVOL_E_NO_DEVICE; }
-        float md = 0.f;
-        for (size_t i = 0; i < nb / sizeof(float); ++i) md = std::max(md, v.density[i]);
-        maxDensity = md;
-        h.density = newDensity;
-    }
-    if (v.kind == PVOL_VOLUME_EXPONENTIAL) maxDensity = pvol_exponential_max_density(&v, h.expUp);
-    // commit: kernels of earlier batches may still read the old scene and grid
-    if (!ok(hipDeviceSynchronize()) || !ok(hipMemcpy(c->dsh, &hsh, sizeof(hsh), hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(c->ds, &h, sizeof(DevScene), hipMemcpyHostToDevice))) {
-        if (newDensity) hipFree(newDensity);
-        if (newTris) hipFree(newTris);
-        if (newNodes) hipFree(newNodes);
-        pvol_push_scene(c);   // best effort: put the device copy of the previous scene back
-        hipMemcpy(c->dsh, &c->hsh, sizeof(c->hsh), hipMemcpyHostToDevice);
-        return PVOL_E_NO_DEVICE;
-    }
-    if (c->dDensity) hipFree(c->dDensity);
-    c->dDensity = newDensity;
-    if (c->dBvhNodes) hipFree(c->dBvhNodes);
-    if (c->dBvhTris) hipFree(c->dBvhTris);
-    c->dBvhNodes = newNodes; c->dBvhTris = newTris;
-    c->bvhBuildMs = bvhMs;
-    c->triMatHost.swap(triMat);
-    c->maxDensity = maxDensity;
-    pvol_free_caustic_map(c);   // the surface integrator belongs to the scene it was enabled on (h.surf is zero)
-    c->hs = h;
-    c->hsh = hsh;
-    c->haveScene = true;
-    return PVOL_OK;
-}
-
-static void choose_grid(pvol_ctx *c, const float *p, uint32_t n) {
-    DevScene &h = c->hs;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (uint32_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], p[3 * i + a]); hi[a] = std::max(hi[a], p[3 * i + a]); }
-    double ext[3], vol = 1;
-    const float maxDist = c->params.max_dist;
-    for (int a = 0; a < 3; ++a) { ext[a] = std::max((double)hi[a] - lo[a], 1e-3 * maxDist); vol *= ext[a]; }
-    // aim at ~4 photons per cell, never more than PVOL_MAX_RING rings per lookup, at most 2^24 cells
-    double cell = cbrt(vol * 1.4 / std::max(1u, n));   // ~1.4 photons per cell measured best on MI355X (profiles/)
-    if (c->params.grid_cell_scale > 0.f) cell *= c->params.grid_cell_scale;
-    cell = std::max(cell, (double)maxDist / PVOL_MAX_RING * 1.0001);
-    for (;;) {
-        double cells = 1;
-        for (int a = 0; a < 3; ++a) cells *= floor(ext[a] / cell) + 1;
-        if (cells <= 16777216.0) break;
-        cell *= 1.26;
-    }
-    h.cellSize = (float)cell;
-    h.invCell = 1.f / h.cellSize;
-    for (int a = 0; a < 3; ++a) {
-        h.gridLo[a] = lo[a];
-        h.gdim[a] = (int)floor(ext[a] / cell) + 1;
-    }
-    h.ringMax = (int)ceil(maxDist / h.cellSize);
-    if (h.ringMax > PVOL_MAX_RING) h.ringMax = PVOL_MAX_RING;
-    if (h.ringMax < 1) h.ringMax = 1;
-    // radius^2 of the ball that holds nUsed photons at the map's mean density: where a lookup with nothing better starts
-    h.rkEstimate = (float)pow((double)c->params.n_used * vol / ((double)std::max(1u, n) * 4.18879020478639), 2.0 / 3.0);
-}
-
-int pvol_finish_map(pvol_ctx *c, uint32_t n, const float *hostPositions) {
-    DevScene &h = c->hs;
-    choose_grid(c, hostPositions, n);
-    size_t ncells = (size_t)h.gdim[0] * h.gdim[1] * h.gdim[2];
-    bool good = ok(hipMalloc(&c->dPos4, sizeof(float4) * (size_t)n)) && ok(hipMalloc(&c->dAlpha4, sizeof(float4) * 8 * (size_t)n)) &&
-                ok(hipMalloc(&c->dWi4, sizeof(float4) * (size_t)n)) && ok(hipMalloc(&c->dCellStart, sizeof(uint32_t) * (ncells + 1)));
-    if (!good) { pvol_free_photons(c); pvol_push_scene(c); return PVOL_E_NO_MEMORY; }
-    GridBuildArgs g;
-    g.p = c->dRawP; g.wi = c->dRawWi; g.alpha = c->dRawAlpha; g.n = n;
-    for (int a = 0; a < 3; ++a) { g.lo[a] = h.gridLo[a]; g.gdim[a] = h.gdim[a]; g.extLo[a] = h.extLo[a]; g.extHi[a] = h.extHi[a]; }
-    g.inv = h.invCell;
-    g.sub = 1;
-    g.volKind = h.volKind;
-    memcpy(g.w2v, h.w2v, sizeof(g.w2v));
-    good = ok(pvol_build_grid(&g, c->dPos4, c->dAlpha4, c->dWi4, c->dCellStart, 0, 0));
-    if (!good) { pvol_free_photons(c); pvol_push_scene(c); return PVOL_E_NO_DEVICE; }
-    // clumpy map (an average photon shares its cell with more than 64 others -- pinkfloyd's beams: 4 700): sort again with
-    // the 4 x 4 x 4 second level.  PVOL_SUBGRID=0/1 forces it off/on.
-    h.subStart = 0;
-    {
-        double sq = 0.0;
-        const char *ev = getenv("PVOL_SUBGRID");
-        bool want = false;
-        if (ev) want = atoi(ev) != 0;
-        else if (ok(pvol_grid_occupancy(c->dCellStart, (uint32_t)ncells, &sq, 0))) want = sq / (double)n > 64.0;
-        if (want && ncells * 64 < 0xfffffff0ull) {
-            if (ok(hipMalloc(&c->dSubStart, sizeof(uint32_t) * (ncells * 64 + 1)))) {
-                g.sub = 4;
-                if (!ok(pvol_build_grid(&g, c->dPos4, c->dAlpha4, c->dWi4, c->dCellStart, c->dSubStart, 0))) { pvol_free_photons(c); pvol_push_scene(c); return PVOL_E_NO_DEVICE; }
-                h.subStart = c->dSubStart;
-            } else {
-                c->dSubStart = 0;   // no room for the table: the coarse level alone is complete
-                (void)hipGetLastError();
-            }
-        }
-    }
-    c->nPhotons = n;
-    h.nPhotons = n; h.cellStart = c->dCellStart; h.pos4 = c->dPos4; h.alpha4 = c->dAlpha4; h.wi4 = c->dWi4;
-    return pvol_push_scene(c);
-}
-
-int pvol_upload_photons(pvol_ctx *c, const float *p, const float *wi, const float *alpha, uint32_t n) {
-    if (!c) return PVOL_E_INVALID;
-    if (!c->haveScene) return PVOL_E_NO_SCENE;
-    if (n && (!p || !wi || !alpha)) return PVOL_E_INVALID;
-    std::lock_guard<std::recursive_mutex> api(c->apiMu);
-    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    hipDeviceSynchronize();
-    pvol_free_photons(c);
-    DevScene &h = c->hs;
-    h.nPhotons = 0; h.cellStart = 0; h.subStart = 0; h.pos4 = 0; h.alpha4 = 0; h.wi4 = 0;
-    if (n == 0) return pvol_push_scene(c);
-    bool good = ok(hipMalloc(&c->dRawP, sizeof(float) * 3 * (size_t)n)) && ok(hipMalloc(&c->dRawWi, sizeof(float) * 3 * (size_t)n)) &&
-                ok(hipMalloc(&c->dRawAlpha, sizeof(float) * 30 * (size_t)n));
-    if (!good) { pvol_free_photons(c); pvol_push_scene(c); return PVOL_E_NO_MEMORY; }
-    good = ok(hipMemcpy(c->dRawP, p, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice)) &&
-           ok(hipMemcpy(c->dRawWi, wi, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice)) &&
-           ok(hipMemcpy(c->dRawAlpha, alpha, sizeof(float) * 30 * (size_t)n, hipMemcpyHostToDevice));
-    if (!good) { pvol_free_photons(c); pvol_push_scene(c); return PVOL_E_NO_DEVICE; }
-    return pvol_finish_map(c, n, p);
-}
-
-void pvol_free_caustic_map(pvol_ctx *c) {
-    if (c->dCPos4) hipFree(c->dCPos4);
-    if (c->dCAlpha4) hipFree(c->dCAlpha4);
-    if (c->dCWi4) hipFree(c->dCWi4);
-    if (c->dCCellStart) hipFree(c->dCCellStart);
-    c->dCPos4 = c->dCAlpha4 = c->dCWi4 = 0; c->dCCellStart = 0;
-    memset(&c->hs.surf, 0, sizeof(c->hs.surf));
-    c->specOn = false;
-}
-
-// PhotonIntegrator::Li in front of the volume term (include/pvol.h).  The caustic map gets the volume map's cell layout
-// (pvol_grid.hip) with cells of about maxdist / 2: a lookup gathers everything within maxdist, never fewer.
-int pvol_set_surface_integrator(pvol_ctx *c, const pvol_surface_params *sp, const float *p, const float *wo, const float *alpha, uint32_t n) {
-    if (!c) return PVOL_E_INVALID;
-    if (!c->haveScene) return PVOL_E_NO_SCENE;
-    std::lock_guard<std::recursive_mutex> api(c->apiMu);
-    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    if (!sp) {
-        hipDeviceSynchronize();
-        pvol_free_caustic_map(c);
-        c->specOn = false;
-        return pvol_push_scene(c);
-    }
-    if (sp->n_used < 1 || !(sp->max_dist > 0.f) || sp->max_specular_depth < 0) return PVOL_E_INVALID;
-    // matte and glass: a specular BSDF brings the recursion of SpecularReflect / SpecularTransmit (core/integrator.cpp:177-262,
-    // pvol_spec_dev.h), walked for "maxspeculardepth" up to SPEC_MAX_DEPTH (the reference's default)
-    bool anySpecular = false;
-    for (size_t i = 0; i < c->triMatHost.size(); ++i) {
-        const int kind = c->hsh.mats[c->triMatHost[i]].kind;
-        if (kind == PVOL_MATERIAL_GLASS) anySpecular = true;
-        else if (kind != PVOL_MATERIAL_MATTE) return PVOL_E_UNSUPPORTED;
-    }
-    for (int i = 0; i < c->hs.nSpheres; ++i) {
-        const int kind = c->hsh.mats[c->hs.spheres[i].mat].kind;
-        if (kind == PVOL_MATERIAL_GLASS) anySpecular = true;
-        else if (kind != PVOL_MATERIAL_MATTE) return PVOL_E_UNSUPPORTED;
-    }
-    if (anySpecular && sp->max_specular_depth > SPEC_MAX_DEPTH) return PVOL_E_UNSUPPORTED;
-    // an indirect map makes PhotonIntegrator::Li gather: the final gather, or LPhoton(indirectMap) with 144 more rho draws
-    // (photonmap.cpp:183-309).  None of that radiance and none of those draws exist here yet, so such an integrator is
-    // refused by name rather than rendered wrong -- whether the map is the caller's (n_indirect_photons) or the store of
-    // the last pvol_preprocess.
-    if (sp->n_indirect_photons > 0) return PVOL_E_UNSUPPORTED;
-    if (sp->use_preprocess_store) {
-        if (!c->surfKept) return PVOL_E_INVALID;   // nothing was kept: params.keep_surface_photons was 0, or no pvol_preprocess yet
-        if (c->surf[2].n > 0) return PVOL_E_UNSUPPORTED;
-    }
-    uint32_t nPaths = sp->n_caustic_paths;
-    std::vector<float> hp;
-    const float *dP = 0, *dWo = 0, *dAlpha = 0;
-    float *up[3] = {0, 0, 0};
-    auto drop = [&]() { for (int i = 0; i < 3; ++i) if (up[i]) hipFree(up[i]); };
-    if (sp->use_preprocess_store) {   // device to device; the positions come back once for the grid bounds
-        const pvol_ctx::SurfStore &st = c->surf[0];
-        n = st.n; nPaths = st.nPaths;
-        dP = st.p; dWo = st.wo; dAlpha = st.alpha;
-        hp.resize(3 * (size_t)n);
-        if (n && !ok(hipMemcpy(hp.data(), dP, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
-        p = hp.data();
-    } else if (n) {
-        if (!p || !wo || !alpha) return PVOL_E_INVALID;
-        const size_t nb[3] = {sizeof(float) * 3 * (size_t)n, sizeof(float) * 3 * (size_t)n, sizeof(float) * 30 * (size_t)n};
-        const float *src[3] = {p, wo, alpha};
-        for (int i = 0; i < 3; ++i) {
-            if (!ok(hipMalloc(&up[i], nb[i]))) { drop(); return PVOL_E_NO_MEMORY; }
-            if (!ok(hipMemcpy(up[i], src[i], nb[i], hipMemcpyHostToDevice))) { drop(); return PVOL_E_NO_DEVICE; }
-        }
-        dP = up[0]; dWo = up[1]; dAlpha = up[2];
-    }
-    if (n && nPaths == 0) { drop(); return PVOL_E_INVALID; }
-    hipDeviceSynchronize();
-    pvol_free_caustic_map(c);
-    DevSurface &sf = c->hs.surf;
-    sf.enabled = 1; sf.nLookup = sp->n_used; sf.maxSpecularDepth = sp->max_specular_depth; sf.nCausticPaths = (int32_t)nPaths;
-    c->specOn = anySpecular && sp->max_specular_depth > 1;
-    sf.maxDistSq = sp->max_dist * sp->max_dist;   // photonmap.cpp:345-346
-    sf.nPhotons = 0;
-    if (n) {
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < n; ++i)
-            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], p[3 * i + a]); hi[a] = std::max(hi[a], p[3 * i + a]); }
-        double cell = 0.5 * sp->max_dist, ext[3];
-        for (int a = 0; a < 3; ++a) ext[a] = std::max((double)hi[a] - lo[a], 1e-3 * sp->max_dist);
-        for (;;) {
-            double cells = 1;
-            for (int a = 0; a < 3; ++a) cells *= floor(ext[a] / cell) + 1;
-            if (cells <= 16777216.0) break;
-            cell *= 1.26;
-        }
-        sf.cellSize = (float)cell; sf.invCell = 1.f / sf.cellSize;
-        size_t ncells = 1;
-        for (int a = 0; a < 3; ++a) { sf.gridLo[a] = lo[a]; sf.gdim[a] = (int)floor(ext[a] / cell) + 1; ncells *= (size_t)sf.gdim[a]; }
-        bool good = ok(hipMalloc(&c->dCPos4, sizeof(float4) * (size_t)n)) && ok(hipMalloc(&c->dCAlpha4, sizeof(float4) * 8 * (size_t)n)) &&
-                    ok(hipMalloc(&c->dCWi4, sizeof(float4) * (size_t)n)) && ok(hipMalloc(&c->dCCellStart, sizeof(uint32_t) * (ncells + 1)));
-        if (!good) { drop(); pvol_free_caustic_map(c); pvol_push_scene(c); return PVOL_E_NO_MEMORY; }
-        GridBuildArgs g;
-        memset(&g, 0, sizeof(g));
-        g.p = dP; g.wi = dWo; g.alpha = dAlpha; g.n = n;
-        for (int a = 0; a < 3; ++a) { g.lo[a] = sf.gridLo[a]; g.gdim[a] = sf.gdim[a]; }
-        g.inv = sf.invCell;
-        g.volKind = PVOL_VOLUME_GRID;   // no Inside() filter: surface photons count wherever they lie
-        g.sub = 1;
-        good = ok(pvol_build_grid(&g, c->dCPos4, c->dCAlpha4, c->dCWi4, c->dCCellStart, 0, 0));
-        if (!good) { drop(); pvol_free_caustic_map(c); pvol_push_scene(c); return PVOL_E_NO_DEVICE; }
-        sf.nPhotons = n; sf.cellStart = c->dCCellStart; sf.pos4 = c->dCPos4; sf.alpha4 = c->dCAlpha4; sf.wi4 = c->dCWi4;
-    }
-    drop();
-    return pvol_push_scene(c);
-}
-
-int pvol_photon_count(pvol_ctx *c, uint32_t *n) {
-    if (!c || !n) return PVOL_E_INVALID;
-    *n = c->nPhotons;
-    return PVOL_OK;
-}
-
-int pvol_download_photons(pvol_ctx *c, float *p, float *wi, float *alpha, uint32_t capacity) {
-    if (!c || !p || !wi || !alpha) return PVOL_E_INVALID;
-    uint32_t n = std::min(capacity, c->nPhotons);
-    if (!n) return PVOL_OK;
-    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    bool good = ok(hipMemcpy(p, c->dRawP, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost)) &&
-                ok(hipMemcpy(wi, c->dRawWi, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost)) &&
-                ok(hipMemcpy(alpha, c->dRawAlpha, sizeof(float) * 30 * (size_t)n, hipMemcpyDeviceToHost));
-    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return ok(hipMemcpy(c->ds.get(), &c->hs, sizeof(DevScene), hipMemcpyHostToDevice)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 // ---- the plan of a batch (pvol_host.h): no HIP call, no context, no environment up to pvol_plan_batch
@@ -821,9 +261,8 @@ static PlanIn plan_input(const pvol_ctx *c, const BatchArgs &b) {
 bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream) {
     if (want <= b.bytes) return true;
     hipStreamSynchronize(stream);   // an earlier batch may still read the old buffer
-    if (b.p) hipFree(b.p);
-    b.p = 0; b.bytes = 0;
-    if (!ok(hipMalloc(&b.p, want))) { b.p = 0; return false; }
+    b.bytes = 0;
+    if (!b.p.alloc(want)) return false;
     b.bytes = want;
     return true;
 }
@@ -881,8 +320,8 @@ static int spec_pool_reset(pvol_ctx *c, TileArgs *t, size_t cap, hipStream_t str
     memset(&c->hSegStream, 0, sizeof(pvol_stream)); c->hSegStream.n_rays = (uint32_t)cap;
     pvol_ray *segRays = pvol_buf<pvol_ray>(c, PVOL_BUF_SEG_RAYS);
     uint32_t *segCounter = pvol_buf<uint32_t>(c, PVOL_BUF_SEG_COUNTER);
-    if (!ok(hipMemsetAsync(segCounter, 0, 16, stream)) || !ok(hipMemcpyAsync(c->buf[PVOL_BUF_SEG_STREAM].p, &c->hSegStream, sizeof(pvol_stream), hipMemcpyHostToDevice, stream)) ||
-        !ok(pvol_launch_spec_fill(segRays, (uint32_t)cap, stream)) || !ok(hipMemsetAsync(c->buf[PVOL_BUF_SEG_OUT].p, 0, sizeof(float) * 60 * cap, stream)))
+    if (!ok(hipMemsetAsync(segCounter, 0, 16, stream)) || !ok(hipMemcpyAsync(pvol_buf<pvol_stream>(c, PVOL_BUF_SEG_STREAM), &c->hSegStream, sizeof(pvol_stream), hipMemcpyHostToDevice, stream)) ||
+        !ok(pvol_launch_spec_fill(segRays, (uint32_t)cap, stream)) || !ok(hipMemsetAsync(pvol_buf<float>(c, PVOL_BUF_SEG_OUT), 0, sizeof(float) * 60 * cap, stream)))
         return PVOL_E_NO_DEVICE;
     t->specOn = 1; t->segRays = segRays; t->segInfo = pvol_buf<SegInfo>(c, PVOL_BUF_SEG_INFO); t->segCounter = segCounter; t->segCap = (uint32_t)cap;
     t->segRecords = pvol_buf<unsigned char>(c, PVOL_BUF_SEG_RECORDS);
@@ -899,16 +338,16 @@ static int spec_finish(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, cons
     sa.out = segOut; sa.draws = 0; sa.initState = 0; sa.finalState = 0; sa.tauOut = 0; sa.defer = 0; sa.deferCount = 0; sa.deferCap = 0; sa.gated = 0;
     sa.records = pvol_buf<unsigned char>(c, PVOL_BUF_SEG_RECORDS); sa.sliceM = (uint32_t)cap; sa.sliceK = 0; sa.state = 0; sa.status = 0;
     const uint32_t nWaves = (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 16ull);
-    if (!ok(hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), b.stream))) return PVOL_E_NO_DEVICE;
+    if (!ok(hipMemsetAsync(c->dWords.get(), 0, 4 * sizeof(uint32_t), b.stream))) return PVOL_E_NO_DEVICE;
     const RegionLaunchers &K = pvol_launchers(c->hs.volKind);
     hipError_t e = replay ? K.liReplay(&sa, p.ldsPar, c->hs.candCap, nWaves, b.stream)
                           : K.liPar(&sa, p.ldsPar, c->hs.candCap, false, nWaves, b.stream);
     if (!ok(e)) return PVOL_E_NO_DEVICE;
     SurfArgs su = {};
-    su.scene = c->ds; su.rays = segRays; su.nRays = (uint32_t)cap; su.out = segOut; su.tau = 0; su.surfOut = 0; su.counters = c->dCounters; su.link = 0; su.spectral = 1;
+    su.scene = c->ds.get(); su.rays = segRays; su.nRays = (uint32_t)cap; su.out = segOut; su.tau = 0; su.surfOut = 0; su.counters = c->dCounters.get(); su.link = 0; su.spectral = 1;
     if (!ok(K.surface(&su, (uint32_t)std::min<unsigned long long>((cap + 63) / 64, (unsigned long long)c->nCU * 24ull), b.stream))) return PVOL_E_NO_DEVICE;
     SpecComposeArgs ca = {};
-    ca.scene = c->ds; ca.link = pvol_buf<uint32_t>(c, PVOL_BUF_SPEC_LINK); ca.info = pvol_buf<SegInfo>(c, PVOL_BUF_SEG_INFO); ca.segOut = segOut; ca.tau = a.tauOut;
+    ca.scene = c->ds.get(); ca.link = pvol_buf<uint32_t>(c, PVOL_BUF_SPEC_LINK); ca.info = pvol_buf<SegInfo>(c, PVOL_BUF_SEG_INFO); ca.segOut = segOut; ca.tau = a.tauOut;
     ca.out = b.out; ca.surfOut = b.specSurfOut; ca.first = 0; ca.nRays = b.nRays;
     return ok(pvol_launch_spec_compose(&ca, b.stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
@@ -943,7 +382,7 @@ static int run_sliced(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArg
     const RegionLaunchers &K = pvol_launchers(c->hs.volKind);
     for (uint32_t k = 0; k < p.nSlices; ++k) {
         a.sliceK = k;
-        hipMemsetAsync(c->dWords, 0, 4 * sizeof(uint32_t), b.stream);
+        hipMemsetAsync(c->dWords.get(), 0, 4 * sizeof(uint32_t), b.stream);
         if (p.specCap && spec_pool_reset(c, tile, p.specCap, b.stream) != PVOL_OK) return PVOL_E_NO_DEVICE;
         if (p.tile == PVOL_TILE_FUSED) {
             pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
@@ -1004,16 +443,16 @@ int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
     TileArgs tile;   // the tile driver's arguments, completed here with the segment pool of the specular recursion
     if (b.tile) tile = *b.tile;
     LiArgs a = {};
-    a.scene = c->ds; a.rays = b.rays; a.streams = b.streams; a.nStreams = b.nStreams; a.nRays = b.nRays; a.outputKind = b.outputKind;
-    a.out = b.out; a.draws = b.draws; a.initState = b.initState; a.finalState = b.finalState; a.counters = c->dCounters;
-    a.transmittanceOnly = b.transOnly; a.chunkCounter = c->dWords; a.needSeq = c->dWords + 1; a.gated = 0;
+    a.scene = c->ds.get(); a.rays = b.rays; a.streams = b.streams; a.nStreams = b.nStreams; a.nRays = b.nRays; a.outputKind = b.outputKind;
+    a.out = b.out; a.draws = b.draws; a.initState = b.initState; a.finalState = b.finalState; a.counters = c->dCounters.get();
+    a.transmittanceOnly = b.transOnly; a.chunkCounter = c->dWords.get(); a.needSeq = c->dWords.get() + 1; a.gated = 0;
     a.tauOut = b.tauOut; a.status = b.status; a.grpGuess = in.knobs.groupGuess;
     if (p.groupForm) {
-        a.defer = pvol_buf<DeferRec>(c, PVOL_BUF_DEFER); a.deferCount = c->dWords + 2;
+        a.defer = pvol_buf<DeferRec>(c, PVOL_BUF_DEFER); a.deferCount = c->dWords.get() + 2;
         a.deferCap = (uint32_t)std::min<size_t>(c->buf[PVOL_BUF_DEFER].bytes / sizeof(DeferRec), 0xffffffffu);
         if (p.path == PVOL_PATH_SLICED) { a.fxgWiden = in.knobs.fxgWiden; a.fxgAim = in.knobs.fxgAim; }
     }
-    if (p.path == PVOL_PATH_PAR) hipMemsetAsync(c->dWords, 0, 3 * sizeof(uint32_t), stream);
+    if (p.path == PVOL_PATH_PAR) hipMemsetAsync(c->dWords.get(), 0, 3 * sizeof(uint32_t), stream);
     if (p.tile == PVOL_TILE_COUNT) {   // outside the timed region of the march kernel; the march keeps the pre-pass's slice fields
         a.sliceK = 0; a.sliceM = 0xffffffc0u; a.state = 0;
         if (p.specCap) rc = spec_pool_reset(c, &tile, p.specCap, stream);
@@ -1034,10 +473,10 @@ int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
 
 static int check_errors(pvol_ctx *c) {
     DevCounters h;
-    if (!ok(hipMemcpy(&h, c->dCounters, sizeof(h), hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
+    if (!ok(hipMemcpy(&h, c->dCounters.get(), sizeof(h), hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
     if (h.nErrors) {
         unsigned long long zero = 0;
-        hipMemcpy(&c->dCounters->nErrors, &zero, sizeof(zero), hipMemcpyHostToDevice);
+        hipMemcpy(&c->dCounters.get()->nErrors, &zero, sizeof(zero), hipMemcpyHostToDevice);
         return PVOL_E_LIMIT;
     }
     return PVOL_OK;
@@ -1084,47 +523,34 @@ static int host_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, pvol_st
     }
     if (!nStreams || !nRays) return PVOL_OK;
     const size_t width = transOnly ? 60 : (outputKind == PVOL_OUT_SPECTRAL ? 60 : 4);
-    pvol_ray *dRays = 0; pvol_stream *dStreams = 0; float *dOut = 0; uint32_t *dDraws = 0, *dState = 0;
-    int rc = PVOL_OK;
-    bool good = ok(hipMalloc(&dRays, sizeof(pvol_ray) * (size_t)nRays)) && ok(hipMalloc(&dStreams, sizeof(pvol_stream) * (size_t)nStreams)) &&
-                ok(hipMalloc(&dOut, sizeof(float) * width * nRays)) && ok(hipMalloc(&dDraws, sizeof(uint32_t) * (size_t)nRays));
-    if (good && mtState) good = ok(hipMalloc(&dState, sizeof(uint32_t) * 625 * (size_t)nStreams));
-    if (!good) rc = PVOL_E_NO_MEMORY;
-    if (rc == PVOL_OK) {
-        good = ok(hipMemcpy(dRays, rays, sizeof(pvol_ray) * (size_t)nRays, hipMemcpyHostToDevice)) &&
-               ok(hipMemcpy(dStreams, streams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyHostToDevice)) &&
-               ok(hipMemset(dOut, 0, sizeof(float) * width * nRays));
-        if (good && mtState) good = ok(hipMemcpy(dState, mtState, sizeof(uint32_t) * 625 * (size_t)nStreams, hipMemcpyHostToDevice));
-        if (!good) rc = PVOL_E_NO_DEVICE;
-    }
-    if (rc == PVOL_OK) {
-        BatchArgs b = {};
-        b.rays = dRays; b.nRays = nRays; b.streams = dStreams; b.nStreams = nStreams; b.outputKind = transOnly ? PVOL_OUT_SPECTRAL : outputKind;
-        b.out = dOut; b.draws = dDraws; b.initState = dState; b.finalState = dState; b.transOnly = transOnly; b.maxRaysPerStream = maxRays;
-        rc = pvol_launch_batch(c, b);
-    }
+    DevPtr<pvol_ray> dRays; DevPtr<pvol_stream> dStreams; DevPtr<float> dOut; DevPtr<uint32_t> dDraws, dState;
+    if (!dRays.alloc(nRays) || !dStreams.alloc(nStreams) || !dOut.alloc(width * nRays) || !dDraws.alloc(nRays) ||
+        (mtState && !dState.alloc(625 * (size_t)nStreams)))
+        return PVOL_E_NO_MEMORY;
+    bool good = ok(hipMemcpy(dRays.get(), rays, sizeof(pvol_ray) * (size_t)nRays, hipMemcpyHostToDevice)) &&
+                ok(hipMemcpy(dStreams.get(), streams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyHostToDevice)) &&
+                ok(hipMemset(dOut.get(), 0, sizeof(float) * width * nRays));
+    if (good && mtState) good = ok(hipMemcpy(dState.get(), mtState, sizeof(uint32_t) * 625 * (size_t)nStreams, hipMemcpyHostToDevice));
+    if (!good) return PVOL_E_NO_DEVICE;
+    BatchArgs b = {};
+    b.rays = dRays.get(); b.nRays = nRays; b.streams = dStreams.get(); b.nStreams = nStreams; b.outputKind = transOnly ? PVOL_OUT_SPECTRAL : outputKind;
+    b.out = dOut.get(); b.draws = dDraws.get(); b.initState = dState.get(); b.finalState = dState.get(); b.transOnly = transOnly; b.maxRaysPerStream = maxRays;
+    int rc = pvol_launch_batch(c, b);
     if (rc == PVOL_OK && !ok(hipStreamSynchronize(0))) rc = PVOL_E_NO_DEVICE;
     if (rc == PVOL_OK) rc = check_errors(c);
-    if (rc == PVOL_OK) {
-        if (transOnly) {
-            // kernel wrote [Lv(30) | T(30)] rows; the ABI returns T only
-            std::vector<float> tmp(width * nRays);
-            good = ok(hipMemcpy(tmp.data(), dOut, sizeof(float) * width * nRays, hipMemcpyDeviceToHost));
-            if (good) for (uint32_t i = 0; i < nRays; ++i) memcpy(out + (size_t)i * 30, tmp.data() + (size_t)i * 60 + 30, sizeof(float) * 30);
-        } else {
-            good = ok(hipMemcpy(out, dOut, sizeof(float) * width * nRays, hipMemcpyDeviceToHost));
-        }
-        good = good && ok(hipMemcpy(streams, dStreams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyDeviceToHost));
-        if (good && draws) good = ok(hipMemcpy(draws, dDraws, sizeof(uint32_t) * (size_t)nRays, hipMemcpyDeviceToHost));
-        if (good && mtState) good = ok(hipMemcpy(mtState, dState, sizeof(uint32_t) * 625 * (size_t)nStreams, hipMemcpyDeviceToHost));
-        if (!good) rc = PVOL_E_NO_DEVICE;
+    if (rc != PVOL_OK) return rc;
+    if (transOnly) {
+        // kernel wrote [Lv(30) | T(30)] rows; the ABI returns T only
+        std::vector<float> tmp(width * nRays);
+        good = ok(hipMemcpy(tmp.data(), dOut.get(), sizeof(float) * width * nRays, hipMemcpyDeviceToHost));
+        if (good) for (uint32_t i = 0; i < nRays; ++i) memcpy(out + (size_t)i * 30, tmp.data() + (size_t)i * 60 + 30, sizeof(float) * 30);
+    } else {
+        good = ok(hipMemcpy(out, dOut.get(), sizeof(float) * width * nRays, hipMemcpyDeviceToHost));
     }
-    if (dRays) hipFree(dRays);
-    if (dStreams) hipFree(dStreams);
-    if (dOut) hipFree(dOut);
-    if (dDraws) hipFree(dDraws);
-    if (dState) hipFree(dState);
-    return rc;
+    good = good && ok(hipMemcpy(streams, dStreams.get(), sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyDeviceToHost));
+    if (good && draws) good = ok(hipMemcpy(draws, dDraws.get(), sizeof(uint32_t) * (size_t)nRays, hipMemcpyDeviceToHost));
+    if (good && mtState) good = ok(hipMemcpy(mtState, dState.get(), sizeof(uint32_t) * 625 * (size_t)nStreams, hipMemcpyDeviceToHost));
+    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 int pvol_li_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, pvol_stream *streams, uint32_t nStreams, int outputKind,
@@ -1172,7 +598,7 @@ int pvol_get_stats(pvol_ctx *c, pvol_stats *out, int reset) {
     if (!c || !out) return PVOL_E_INVALID;
     if (!ok(hipSetDevice(c->params.device)) || !ok(hipDeviceSynchronize())) return PVOL_E_NO_DEVICE;
     DevCounters h;
-    if (!ok(hipMemcpy(&h, c->dCounters, sizeof(h), hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
+    if (!ok(hipMemcpy(&h, c->dCounters.get(), sizeof(h), hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
     memset(out, 0, sizeof(*out));
     out->n_rays = h.nRays; out->n_steps = h.nSteps; out->n_tested = h.nTested; out->n_kept = h.nKept;
     out->n_lookups_lt10 = h.nLookupsLt10; out->n_shadow_unoccluded = h.nShadowUnoccluded;
@@ -1180,7 +606,7 @@ int pvol_get_stats(pvol_ctx *c, pvol_stats *out, int reset) {
     out->group_guess_failed = h.diag[0]; out->group_plan_skipped = h.diag[1]; out->cy_fallback = h.diag[2];
     out->group_deferred_overflow = h.diag[3]; out->group_deferred_too_few = h.diag[4]; out->group_attempts = h.diag[5];
     out->cy_search = h.cySearch; out->cy_select = h.cySelect; out->cy_flux = h.cyFlux; out->cy_total = h.cyTotal;
-    if (reset && !ok(hipMemset(c->dCounters, 0, sizeof(DevCounters)))) return PVOL_E_NO_DEVICE;
+    if (reset && !ok(hipMemset(c->dCounters.get(), 0, sizeof(DevCounters)))) return PVOL_E_NO_DEVICE;
     return PVOL_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pvol_dev.h"
+#include "pvol_host.h"   // DevPtr
 
 struct BvhBuildArgs {
     const float *tri;        // [n][9] world-space vertices, upload order
@@ -144,46 +145,37 @@ __global__ void bvh_fit_kernel(BvhBuildArgs a, const unsigned long long *keys, c
     }
 }
 
-#define BVH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = e_; goto done; } } while (0)
+#define BVH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 // tris: [n][3] float4, nodes: [n-1][4] float4 (device, allocated by the caller).  Synchronous on `stream`.
 extern "C" hipError_t pvol_build_bvh(const float *dTri, const int32_t *dMat, const int32_t *dFlip, uint32_t n, float pad, float4 *tris,
                                      float4 *nodes, hipStream_t stream) {
     if (n < 2) return hipErrorInvalidValue;
-    hipError_t rc = hipSuccess;
     BvhBuildArgs a;
     a.tri = dTri; a.mat = dMat; a.flip = dFlip; a.n = n; a.pad = pad;
-    uint32_t *bounds = 0, *arrived = 0;
-    unsigned long long *keys = 0, *keysSorted = 0;
-    int2 *children = 0, *range = 0;
-    int *parent = 0;
-    float *box = 0;
-    void *tmp = 0;
+    DevPtr<uint32_t> bounds, arrived;
+    DevPtr<unsigned long long> keys, keysSorted;
+    DevPtr<int2> children, range;
+    DevPtr<int> parent;
+    DevPtr<float> box;
+    DevPtr<unsigned char> tmp;
     size_t tmpBytes = 0;
     const uint32_t hb[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
     const int T = 256;
     const uint32_t B = (n + T - 1) / T;
-    BVH_TRY(hipMalloc(&bounds, 6 * 4));
-    BVH_TRY(hipMalloc(&keys, (size_t)n * 8));
-    BVH_TRY(hipMalloc(&keysSorted, (size_t)n * 8));
-    BVH_TRY(hipMalloc(&children, (size_t)n * sizeof(int2)));
-    BVH_TRY(hipMalloc(&range, (size_t)n * sizeof(int2)));
-    BVH_TRY(hipMalloc(&parent, (size_t)(2 * n) * 4));
-    BVH_TRY(hipMalloc(&box, (size_t)(2 * n) * 6 * 4));
-    BVH_TRY(hipMalloc(&arrived, (size_t)n * 4));
-    BVH_TRY(hipMemcpyAsync(bounds, hb, sizeof(hb), hipMemcpyHostToDevice, stream));
-    BVH_TRY(hipMemsetAsync(arrived, 0, (size_t)n * 4, stream));
-    hipLaunchKernelGGL(bvh_bounds_kernel, dim3(B), dim3(T), 0, stream, a, bounds);
-    hipLaunchKernelGGL(bvh_keys_kernel, dim3(B), dim3(T), 0, stream, a, bounds, keys);
-    BVH_TRY(hipcub::DeviceRadixSort::SortKeys(0, tmpBytes, keys, keysSorted, (int)n, 0, 62, stream));
-    BVH_TRY(hipMalloc(&tmp, tmpBytes));
-    BVH_TRY(hipcub::DeviceRadixSort::SortKeys(tmp, tmpBytes, keys, keysSorted, (int)n, 0, 62, stream));
-    hipLaunchKernelGGL(bvh_tree_kernel, dim3(B), dim3(T), 0, stream, keysSorted, (int)n, children, range, parent);
-    hipLaunchKernelGGL(bvh_fit_kernel, dim3(B), dim3(T), 0, stream, a, keysSorted, children, range, parent, box, arrived, tris, nodes);
+    if (!bounds.alloc(6) || !keys.alloc(n) || !keysSorted.alloc(n) || !children.alloc(n) || !range.alloc(n) || !parent.alloc(2 * (size_t)n) ||
+        !box.alloc(2 * (size_t)n * 6) || !arrived.alloc(n))
+        return hipErrorOutOfMemory;
+    BVH_TRY(hipMemcpyAsync(bounds.get(), hb, sizeof(hb), hipMemcpyHostToDevice, stream));
+    BVH_TRY(hipMemsetAsync(arrived.get(), 0, (size_t)n * 4, stream));
+    hipLaunchKernelGGL(bvh_bounds_kernel, dim3(B), dim3(T), 0, stream, a, bounds.get());
+    hipLaunchKernelGGL(bvh_keys_kernel, dim3(B), dim3(T), 0, stream, a, bounds.get(), keys.get());
+    BVH_TRY(hipcub::DeviceRadixSort::SortKeys(0, tmpBytes, keys.get(), keysSorted.get(), (int)n, 0, 62, stream));
+    if (!tmp.alloc(tmpBytes)) return hipErrorOutOfMemory;
+    BVH_TRY(hipcub::DeviceRadixSort::SortKeys(tmp.get(), tmpBytes, keys.get(), keysSorted.get(), (int)n, 0, 62, stream));
+    hipLaunchKernelGGL(bvh_tree_kernel, dim3(B), dim3(T), 0, stream, keysSorted.get(), (int)n, children.get(), range.get(), parent.get());
+    hipLaunchKernelGGL(bvh_fit_kernel, dim3(B), dim3(T), 0, stream, a, keysSorted.get(), children.get(), range.get(), parent.get(), box.get(),
+                       arrived.get(), tris, nodes);
     BVH_TRY(hipGetLastError());
-    BVH_TRY(hipStreamSynchronize(stream));
-done:
-    hipFree(bounds); hipFree(keys); hipFree(keysSorted); hipFree(children); hipFree(range); hipFree(parent); hipFree(box); hipFree(arrived);
-    hipFree(tmp);
-    return rc;
+    return hipStreamSynchronize(stream);   // the scratch is freed on return
 }

@@ -14,21 +14,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pvol_dev.h"
-
-struct GridBuildArgs {
-    const float *p;      // n x 3 (upload order)
-    const float *wi;     // n x 3
-    const float *alpha;  // n x 30
-    uint32_t n;
-    float lo[3];
-    float inv;
-    int32_t gdim[3];
-    int32_t sub;         // 1, or 4: sort by (cell, 4x4x4 sub-cell) and fill subStart
-    // volume (for the Inside() test of HomogeneousVolumeDensity::p, volumes/homogeneous.h:76-79)
-    int32_t volKind;
-    float extLo[3], extHi[3];
-    float w2v[16];
-};
+#include "pvol_host.h"   // GridBuildArgs, DevPtr
 
 __device__ __forceinline__ int cell_coord(float x, float lo, float inv, int dim) {
     int c = (int)floorf((x - lo) * inv);
@@ -105,14 +91,12 @@ __global__ void occupancy_kernel(const uint32_t *cellStart, uint32_t ncells, dou
     if ((threadIdx.x & 63) == 0 && v != 0.0) atomicAdd(out, v);
 }
 extern "C" hipError_t pvol_grid_occupancy(const uint32_t *cellStart, uint32_t ncells, double *sumSquares, hipStream_t stream) {
-    double *d = 0;
-    hipError_t e = hipMalloc(&d, sizeof(double));
-    if (e != hipSuccess) return e;
-    hipMemsetAsync(d, 0, sizeof(double), stream);
-    hipLaunchKernelGGL(occupancy_kernel, dim3((ncells + 255) / 256), dim3(256), 0, stream, cellStart, ncells, d);
-    e = hipMemcpyAsync(sumSquares, d, sizeof(double), hipMemcpyDeviceToHost, stream);
+    DevPtr<double> d;
+    if (!d.alloc(1)) return hipErrorOutOfMemory;
+    hipMemsetAsync(d.get(), 0, sizeof(double), stream);
+    hipLaunchKernelGGL(occupancy_kernel, dim3((ncells + 255) / 256), dim3(256), 0, stream, cellStart, ncells, d.get());
+    hipError_t e = hipMemcpyAsync(sumSquares, d.get(), sizeof(double), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    hipFree(d);
     return e;
 }
 
@@ -124,43 +108,34 @@ extern "C" hipError_t pvol_build_grid(const GridBuildArgs *args, float4 *pos4, f
     const uint32_t ncells = (uint32_t)args->gdim[0] * args->gdim[1] * args->gdim[2];
     const uint32_t sub3 = args->sub > 1 ? (uint32_t)(args->sub * args->sub * args->sub) : 1u;
     if (sub3 > 1 && (!subStart || (unsigned long long)ncells * sub3 >= 0xffffffffull)) return hipErrorInvalidValue;
-    uint32_t *keysIn = 0, *keysOut = 0, *valsIn = 0, *valsOut = 0;
-    void *temp = 0;
+    DevPtr<uint32_t> keysIn, keysOut, valsIn, valsOut;
+    DevPtr<unsigned char> temp;
     size_t tempBytes = 0;
     hipError_t e = hipSuccess;
-#define CK(x) do { e = (x); if (e != hipSuccess) goto done; } while (0)
-    CK(hipMalloc(&keysIn, sizeof(uint32_t) * n));
-    CK(hipMalloc(&keysOut, sizeof(uint32_t) * n));
-    CK(hipMalloc(&valsIn, sizeof(uint32_t) * n));
-    CK(hipMalloc(&valsOut, sizeof(uint32_t) * n));
-    hipLaunchKernelGGL(cell_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *args, keysIn, valsIn);
+#define CK(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
+    if (!keysIn.alloc(n) || !keysOut.alloc(n) || !valsIn.alloc(n) || !valsOut.alloc(n)) return hipErrorOutOfMemory;
+    hipLaunchKernelGGL(cell_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *args, keysIn.get(), valsIn.get());
     CK(hipGetLastError());
     {
         int bits = 1;
         while ((1ull << bits) < (unsigned long long)ncells * sub3) ++bits;
-        CK(hipcub::DeviceRadixSort::SortPairs(temp, tempBytes, keysIn, keysOut, valsIn, valsOut, (int)n, 0, bits, stream));
-        CK(hipMalloc(&temp, tempBytes));
-        CK(hipcub::DeviceRadixSort::SortPairs(temp, tempBytes, keysIn, keysOut, valsIn, valsOut, (int)n, 0, bits, stream));
+        CK(hipcub::DeviceRadixSort::SortPairs(0, tempBytes, keysIn.get(), keysOut.get(), valsIn.get(), valsOut.get(), (int)n, 0, bits, stream));
+        if (!temp.alloc(tempBytes)) return hipErrorOutOfMemory;
+        CK(hipcub::DeviceRadixSort::SortPairs(temp.get(), tempBytes, keysIn.get(), keysOut.get(), valsIn.get(), valsOut.get(), (int)n, 0, bits, stream));
     }
     {
         unsigned long long threads = (unsigned long long)n * 8ull;
-        hipLaunchKernelGGL(scatter_photons_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, *args, valsOut, pos4, alpha4, wi4);
+        hipLaunchKernelGGL(scatter_photons_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, *args, valsOut.get(), pos4, alpha4, wi4);
         CK(hipGetLastError());
     }
-    hipLaunchKernelGGL(cell_start_kernel, dim3((ncells + 1 + 255) / 256), dim3(256), 0, stream, keysOut, n, ncells, sub3, cellStart);
+    hipLaunchKernelGGL(cell_start_kernel, dim3((ncells + 1 + 255) / 256), dim3(256), 0, stream, keysOut.get(), n, ncells, sub3, cellStart);
     CK(hipGetLastError());
     if (sub3 > 1) {
         const uint32_t nsub = ncells * sub3;
-        hipLaunchKernelGGL(cell_start_kernel, dim3((nsub + 1 + 255) / 256), dim3(256), 0, stream, keysOut, n, nsub, 1u, subStart);
+        hipLaunchKernelGGL(cell_start_kernel, dim3((nsub + 1 + 255) / 256), dim3(256), 0, stream, keysOut.get(), n, nsub, 1u, subStart);
         CK(hipGetLastError());
     }
-    CK(hipStreamSynchronize(stream));
-done:
+    CK(hipStreamSynchronize(stream));   // the scratch is freed on return
 #undef CK
-    if (keysIn) hipFree(keysIn);
-    if (keysOut) hipFree(keysOut);
-    if (valsIn) hipFree(valsIn);
-    if (valsOut) hipFree(valsOut);
-    if (temp) hipFree(temp);
     return e;
 }

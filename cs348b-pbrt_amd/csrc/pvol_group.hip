@@ -211,7 +211,7 @@ extern "C" int pvol_render_frame_group_window(pvol_ctx *const *ctxs, uint32_t n,
         const size_t need = filmBytes * (n - 1);
         if (need > stage.bytes && root->groupStageEv && !ok(hipEventSynchronize(root->groupStageEv))) return PVOL_E_NO_DEVICE;   // the last sum read it
         if (!pvol_reserve(stage, need, s0)) return PVOL_E_NO_MEMORY;
-        float4 *const dStage = (float4 *)stage.p;
+        float4 *const dStage = (float4 *)stage.p.get();
         if (!root->groupStageEv && !ok(hipEventCreateWithFlags(&root->groupStageEv, hipEventDisableTiming))) { root->groupStageEv = 0; return PVOL_E_NO_DEVICE; }
         const int dev0 = root->params.device;
         for (uint32_t i = 1; i < n; ++i) {

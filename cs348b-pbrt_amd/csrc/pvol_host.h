@@ -1,4 +1,4 @@
-// pvol_host.h -- host-side internals shared by pvol_api.hip and pvol_shoot_host.hip
+// pvol_host.h -- host-side internals shared by the host units (pvol_api.hip, pvol_scene_host.hip, pvol_map_host.hip, pvol_shoot_host.hip)
 #ifndef PVOL_HOST_H
 #define PVOL_HOST_H
 #include <hip/hip_runtime.h>
@@ -9,15 +9,42 @@
 #include <vector>
 #include "pvol_dev.h"
 
+#define PVOL_LOCAL __attribute__((visibility("hidden")))   // shared by the host units, not an export of the library
+
+// The one owner of a device allocation: move-only, freed by its destructor.  alloc() frees what it held; a failed hipMalloc leaves
+// it empty and HIP's last error cleared.
+template <class T> struct PVOL_LOCAL DevPtr {
+    DevPtr() {}
+    DevPtr(DevPtr &&o) : p(o.release()) {}
+    DevPtr &operator=(DevPtr &&o) { reset(o.release()); return *this; }
+    DevPtr(const DevPtr &) = delete;
+    DevPtr &operator=(const DevPtr &) = delete;
+    ~DevPtr() { reset(); }
+    bool alloc(size_t count) {
+        reset();
+        if (hipMalloc(&p, sizeof(T) * count) == hipSuccess) return true;
+        p = 0; (void)hipGetLastError();
+        return false;
+    }
+    T *get() const { return p; }
+    T *release() { T *q = p; p = 0; return q; }
+    void reset(T *q = 0) { if (p) hipFree(p); p = q; }
+private:
+    T *p = 0;
+};
+
 // ---- kernels' host entry points (pvol_march.hip, pvol_grid.hip)
 #include "pvol_liargs.h"
 struct GridBuildArgs {
-    const float *p, *wi, *alpha;
+    const float *p;      // n x 3 (upload order)
+    const float *wi;     // n x 3
+    const float *alpha;  // n x 30
     uint32_t n;
     float lo[3];
     float inv;
     int32_t gdim[3];
-    int32_t sub;
+    int32_t sub;         // 1, or 4: sort by (cell, 4x4x4 sub-cell) and fill subStart
+    // volume (for the Inside() test of HomogeneousVolumeDensity::p, volumes/homogeneous.h:76-79)
     int32_t volKind;
     float extLo[3], extHi[3];
     float w2v[16];
@@ -80,7 +107,7 @@ enum { PVOL_PHASE_END = -1, PVOL_PHASE_TILE = 0, PVOL_PHASE_RNG = 1, PVOL_PHASE_
 
 // The context's on-demand device buffers.  pvol_reserve is the one place they are allocated: nothing to do when `want` fits, else it
 // waits for `stream` (an earlier batch may still read the old buffer), frees, and allocates exactly `want` bytes.
-struct DevBuf { void *p = 0; size_t bytes = 0; };
+struct PVOL_LOCAL DevBuf { DevPtr<unsigned char> p; size_t bytes = 0; };
 enum {
     PVOL_BUF_RECORDS, PVOL_BUF_STATE,   // resolve/replay: per-step records of a slice, MT state of every stream
     PVOL_BUF_DEFER,                     // li_group_kernel's deferred lookups (DeferRec)
@@ -93,39 +120,47 @@ enum {
 };
 extern "C" bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream);
 
+// A photon map as the kernels read it (pvol_grid.hip): the photons sorted by cell, the start of every cell and, for a clumpy volume map,
+// of every 4 x 4 x 4 sub-cell.  Built by build_photon_grid (pvol_map_host.hip); the volume map and the surface integrator's caustic map are one each.
+struct PVOL_LOCAL PhotonGrid {
+    DevPtr<float4> pos4, alpha4, wi4;
+    DevPtr<uint32_t> cellStart, subStart;   // subStart: second level of a clumpy map, else empty
+    uint32_t n = 0;
+    float gridLo[3] = {0.f, 0.f, 0.f}, cellSize = 0.f, invCell = 0.f;
+    int32_t gdim[3] = {0, 0, 0};
+    size_t cells() const { return (size_t)gdim[0] * gdim[1] * gdim[2]; }
+};
+
 struct pvol_ctx {
-    pvol_params params;
-    bool haveScene;
-    DevScene hs;         // host copy
-    DevScene *ds;        // device copy
-    float *dDensity;
-    // triangle hierarchy of a scene with more than PVOL_MAX_TRIS triangles (pvol_bvh.hip), else 0
-    float4 *dBvhNodes = 0, *dBvhTris = 0;
+    pvol_params params = {};
+    bool haveScene = false;
+    DevScene hs = {};        // host copy
+    DevPtr<DevScene> ds;     // device copy
+    DevPtr<float> dDensity;
+    // triangle hierarchy of a scene with more than PVOL_MAX_TRIS triangles (pvol_bvh.hip), else empty
+    DevPtr<float4> dBvhNodes, dBvhTris;
     std::vector<int32_t> triMatHost;   // material of every triangle of the scene (host copy, any size)
     double bvhBuildMs = 0.0;
     // photon map
-    uint32_t nPhotons;
-    float *dRawP, *dRawWi, *dRawAlpha;  // upload order (kept for pvol_download_photons)
-    float4 *dPos4, *dAlpha4, *dWi4;
-    uint32_t *dCellStart;
-    uint32_t *dSubStart = 0;   // second level of a clumpy map (pvol_grid.hip), else 0
-    DevCounters *dCounters;
-    uint32_t *dWords;   // [0] chunk counter of the ray-parallel kernels, [1] needSeq flag, [2] length of the deferred-lookup list, [3] chunk counter of a gated backup kernel
-    int nCU;
+    DevPtr<float> dRawP, dRawWi, dRawAlpha;  // upload order (kept for pvol_download_photons)
+    PhotonGrid volMap;
+    DevPtr<DevCounters> dCounters;
+    DevPtr<uint32_t> dWords;   // [0] chunk counter of the ray-parallel kernels, [1] needSeq flag, [2] length of the deferred-lookup list, [3] chunk counter of a gated backup kernel
+    int nCU = 256;
     float maxDensity = 1.f;   // largest density factor of the medium (1 for analytic volumes, max of the grid values)
     bool noLite = false;      // PVOL_NO_LITE=1: keep the geometry inside the sequential resolve pass (testing)
     const char *lastKernel = "";
     const char *lastTileKernel = "";   // pvol_tile_kernel_name: set by the launch itself
-    int fixWavesPerCU;   // li_fixup_kernel waves per CU; PVOL_FIX_WAVES overrides
-    int groupWavesPerCU; // resident li_group_kernel waves per CU (LDS plan: 8); PVOL_GROUP_WAVES overrides
-    bool noGroup;       // PVOL_NO_GROUP=1: keep li_par_kernel (one wave per ray) where li_group_kernel (one ray per lane) would run
-    bool forceSeq;      // PVOL_FORCE_SEQ=1: always take the stream-sequential kernel (testing)
-    bool statsOn;
+    int fixWavesPerCU = 16;   // li_fixup_kernel waves per CU; PVOL_FIX_WAVES overrides
+    int groupWavesPerCU = 12; // resident li_group_kernel waves per CU (LDS plan: 8); PVOL_GROUP_WAVES overrides
+    bool noGroup = false;       // PVOL_NO_GROUP=1: keep li_par_kernel (one wave per ray) where li_group_kernel (one ray per lane) would run
+    bool forceSeq = false;      // PVOL_FORCE_SEQ=1: always take the stream-sequential kernel (testing)
+    bool statsOn = false;
     // kernel timing (HIP events on the launch stream)
     std::vector<std::pair<hipEvent_t, hipEvent_t> > pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t> > pool;
-    double timeMs;
-    uint64_t launches;
+    double timeMs = 0.0;
+    uint64_t launches = 0;
     std::mutex mu;       // event lists only
     // phase timing of the render driver (pvol_enable_phase_timing): marks on the launch stream, a mark opens phase `id` and
     // closes the one before it; PVOL_PHASE_END closes without opening
@@ -137,22 +172,21 @@ struct pvol_ctx {
     // One batch at a time per context: the launches of a batch share dWords / dCounters and the scratch in `buf`.  Host entry points hold it from upload to copy-back (VolumeIntegrator::Li is called from every
     // SamplerRendererTask thread at once, samplerrenderer.cpp:247); device entry points hold it while they enqueue.
     std::recursive_mutex apiMu;
-    DevBuf buf[PVOL_N_BUFS];   // scratch grown on demand (pvol_reserve), freed in one loop by pvol_destroy
+    DevBuf buf[PVOL_N_BUFS];   // scratch grown on demand (pvol_reserve), freed with the context
     // photon shooter
-    DevShootScene hsh;
-    DevShootScene *dsh;
-    uint64_t shootStats[12];
+    DevShootScene hsh = {};
+    DevPtr<DevShootScene> dsh;
+    uint64_t shootStats[12] = {};
     // surface stores of the last pvol_preprocess (kept only with params.keep_surface_photons): kind 0 caustic, 1 direct, 2 indirect
-    struct SurfStore { float *p = 0, *wo = 0, *alpha = 0; uint32_t n = 0, nPaths = 0; } surf[3];
+    struct PVOL_LOCAL SurfStore { DevPtr<float> p, wo, alpha; uint32_t n = 0, nPaths = 0; } surf[3];
     bool surfKept = false;   // the last pvol_preprocess ran with keep_surface_photons and left its stores here
-    float *dRad = 0;       // radiance photons: [n][8] = p(3) n(3) material index, pad
+    DevPtr<float> dRad;    // radiance photons: [n][8] = p(3) n(3) material index, pad
     uint32_t nRad = 0;
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
-    float4 *dCPos4 = 0, *dCAlpha4 = 0, *dCWi4 = 0;
-    uint32_t *dCCellStart = 0;
+    PhotonGrid causticMap;
     // specular recursion of the surface integrator (pvol_spec_dev.h): segments of the camera samples that meet glass
     bool specOn = false;            // the scene holds a specular material and the surface integrator is on
-    pvol_stream hSegStream;         // the segment pool seen as one stream of a ray batch (host copy of PVOL_BUF_SEG_STREAM)
+    pvol_stream hSegStream = {};    // the segment pool seen as one stream of a ray batch (host copy of PVOL_BUF_SEG_STREAM)
     double exchangeSeconds = 0.0;   // last pvol_preprocess: time in its all-gathers (part of prepSeconds[0]; 0 after pvol_preprocess_blocks)
     double prepSeconds[2] = {0.0, 0.0};   // last pvol_preprocess: shooting (all rounds + merges), search-structure build
     // coalesced per-sample calls (pvol_li_coalesce.hip): concurrent pvol_li calls queue here, one of them (the leader) runs
@@ -198,7 +232,7 @@ struct BatchArgs {
     float *specSurfOut;   // specular recursion: where the composition reports the surface term (debug), or 0
 };
 extern "C" int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b);
-template <class T> static inline T *pvol_buf(const pvol_ctx *c, int which) { return (T *)c->buf[which].p; }
+template <class T> static inline T *pvol_buf(const pvol_ctx *c, int which) { return (T *)c->buf[which].p.get(); }
 
 // ---- the plan of a batch: which kernels it takes and every size they need, a pure function of PlanIn.  LaunchKnobs: the
 // environment knobs read once per launch (pvol_read_knobs); 0 = unset, the default applies.
@@ -234,11 +268,11 @@ extern "C" void plan_size(const PlanIn &in, BatchPlan &p);    // the rest, once 
 
 extern "C" {
 void pvol_phase_mark(pvol_ctx *c, hipStream_t stream, int id);
-// finish a photon map whose raw arrays (dRawP/dRawWi/dRawAlpha, n photons) are already on the device
+// finish the volume map whose raw arrays (dRawP/dRawWi/dRawAlpha, n photons) are already on the device (pvol_map_host.hip)
 int pvol_finish_map(pvol_ctx *c, uint32_t n, const float *hostPositions);
-void pvol_free_photons(pvol_ctx *c);
+void pvol_free_photons(pvol_ctx *c);          // empties the volume map, in the context and in its host scene
 void pvol_free_surface_stores(pvol_ctx *c);
-void pvol_free_caustic_map(pvol_ctx *c);
+void pvol_free_caustic_map(pvol_ctx *c);      // empties the caustic map and switches the surface integrator off
 int pvol_push_scene(pvol_ctx *c);
 // pvol_li without the coalescer (pvol_api.hip) and through it (pvol_li_coalesce.hip); arguments already validated
 int pvol_li_lone(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T);
@@ -249,12 +283,29 @@ int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream);
 void *pvol_rccl_symbol(const char *name);
 // plan_size(plan_path(in)) for the tests; like pvol_rccl_symbol not part of include/pvol.h
 void pvol_plan_batch(const PlanIn *in, BatchPlan *out);
+// the status pvol_set_scene gives the scene on a working device, reachable without one for the tests (pvol_scene_host.hip)
+int pvol_check_scene(const pvol_params *params, const pvol_scene *s);
 // pvol_set_scene's check of an exponential medium's arguments (PVOL_OK or PVOL_E_INVALID), reachable without a device for the tests;
 // up3 (optional) gets the normalised updir
 int pvol_check_exponential(const pvol_volume *v, float *up3);
 // the largest density of a checked exponential medium over its extent (feeds roulette_possible like a VolumeGrid's maximum); up3: the normalised updir
 float pvol_exponential_max_density(const pvol_volume *v, const float *up3);
 }
+
+// ---- the scene's device image (pvol_scene_host.hip): everything pvol_set_scene derives from its arguments, a pure
+// function of them -- no HIP call, no context.  `scene` is complete but for what only a device can give: the density grid, the
+// hierarchy, shootScene and the photon-map fields (all zero here).
+struct PVOL_LOCAL SceneImage {
+    DevScene scene;
+    DevShootScene shoot;
+    float maxDensity;               // largest density factor of the medium (1 for analytic volumes, max of the grid values)
+    float bvhPad;                   // a scene that takes the hierarchy: what its boxes are padded by
+    std::vector<int32_t> primMat;   // material of every triangle, then of every sphere
+};
+PVOL_LOCAL int pvol_scene_image(const pvol_params *params, const pvol_scene *s, SceneImage *out);
+
+// writes a map (an empty one included) into the photon-map fields of the host scene (pvol_map_host.hip)
+PVOL_LOCAL void pvol_map_to_scene(const PhotonGrid &G, DevScene &h);
 
 // ImageFilm's crop window behind the *_window entry points: a NULL window is the whole frame (crop 0 1 0 1), which is what the
 // entry points without a window pass

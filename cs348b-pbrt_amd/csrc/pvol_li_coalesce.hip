@@ -92,7 +92,7 @@ static void run_piece(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
     // a PVOL_E_LIMIT of this batch is in its rays' status only (report_limit): the context's shared count is left alone
     if (rc == PVOL_OK)
         good = ok(hipMemcpyAsync(c->coHostOut, devOut, oGate, hipMemcpyDeviceToHost, s)) &&
-               ok(hipMemcpyAsync(c->coHostOut + oGate, c->dWords + 1, 4, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s));
+               ok(hipMemcpyAsync(c->coHostOut + oGate, c->dWords.get() + 1, 4, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s));
     if (rc == PVOL_OK && !good) rc = PVOL_E_NO_DEVICE;
     if (rc != PVOL_OK) { (void)hipGetLastError(); hipStreamSynchronize(s); return failAll(rc); }
     // The gated backups (li_replay_kernel behind li_group_kernel's replay form) redo EVERY stream of a batch when the hand-over

@@ -50,11 +50,8 @@ struct Buffers {   // one rank's block pools and round tables
 }  // namespace
 
 extern "C" void pvol_free_surface_stores(pvol_ctx *c) {
-    for (int k = 0; k < 3; ++k) {
-        hipFree(c->surf[k].p); hipFree(c->surf[k].wo); hipFree(c->surf[k].alpha);
-        c->surf[k] = pvol_ctx::SurfStore();
-    }
-    hipFree(c->dRad); c->dRad = 0; c->nRad = 0;
+    for (int k = 0; k < 3; ++k) c->surf[k] = pvol_ctx::SurfStore();
+    c->dRad.reset(); c->nRad = 0;
     c->surfKept = false;
 }
 
@@ -69,9 +66,9 @@ extern "C" int pvol_download_surface_photons(pvol_ctx *c, int kind, float *p, fl
     const uint32_t n = std::min(capacity, c->surf[kind].n);
     if (!n) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    const bool good = ok(hipMemcpy(p, c->surf[kind].p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost)) &&
-                      ok(hipMemcpy(wo, c->surf[kind].wo, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost)) &&
-                      ok(hipMemcpy(alpha, c->surf[kind].alpha, sizeof(float) * 30 * (size_t)n, hipMemcpyDeviceToHost));
+    const bool good = ok(hipMemcpy(p, c->surf[kind].p.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost)) &&
+                      ok(hipMemcpy(wo, c->surf[kind].wo.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost)) &&
+                      ok(hipMemcpy(alpha, c->surf[kind].alpha.get(), sizeof(float) * 30 * (size_t)n, hipMemcpyDeviceToHost));
     return good ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 extern "C" int pvol_radiance_photon_count(pvol_ctx *c, uint32_t *n) {
@@ -85,7 +82,7 @@ extern "C" int pvol_download_radiance_photons(pvol_ctx *c, float *p, float *nrm,
     if (!n) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
     std::vector<float> rec(8 * (size_t)n);
-    if (!ok(hipMemcpy(rec.data(), c->dRad, sizeof(float) * 8 * (size_t)n, hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
+    if (!ok(hipMemcpy(rec.data(), c->dRad.get(), sizeof(float) * 8 * (size_t)n, hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
     for (uint32_t i = 0; i < n; ++i) {
         memcpy(p + 3 * (size_t)i, &rec[8 * (size_t)i], 12);
         memcpy(nrm + 3 * (size_t)i, &rec[8 * (size_t)i + 3], 12);
@@ -265,8 +262,6 @@ int shoot(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, Ex
     hipDeviceSynchronize();
     pvol_free_photons(c);
     pvol_free_surface_stores(c);
-    DevScene &h = c->hs;
-    h.nPhotons = 0; h.cellStart = 0; h.subStart = 0; h.pos4 = 0; h.alpha4 = 0; h.wi4 = 0;
     memset(c->shootStats, 0, sizeof(c->shootStats));
     c->prepSeconds[0] = c->prepSeconds[1] = 0.0;
     c->exchangeSeconds = 0.0;
@@ -308,7 +303,7 @@ int shoot(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, Ex
     if (!good) localRc = PVOL_E_NO_MEMORY;
 
     ShootArgs A;
-    A.scene = c->ds; A.shoot = c->dsh; A.nTasks = L; A.stateIn = B.stateA; A.stateOut = B.stateA; A.halton = B.halton; A.flags = B.flags;
+    A.scene = c->ds.get(); A.shoot = c->dsh.get(); A.nTasks = L; A.stateIn = B.stateA; A.stateOut = B.stateA; A.halton = B.halton; A.flags = B.flags;
     A.localPhotons = B.localPhotons; A.localCounts = B.localCounts; A.cap = cap; A.stats = B.stats; A.init = 1;
     A.localSurf = B.localSurf; A.localSurfKind = B.localSurfKind; A.capS = capS; A.localRad = B.localRad; A.capR = capR; A.keepSurface = keep ? 1 : 0;
     A.gridVolume = is_density_region(c->hs.volKind) ? 1 : 0;
@@ -529,16 +524,16 @@ int shoot(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, Ex
         const uint64_t cnt[3] = {nCaustic, nDirect, nIndirect};
         const uint32_t paths[3] = {nCausticPaths, nDirectPaths, nIndirectPaths};
         for (int k = 0; k < 3 && rc == PVOL_OK; ++k) {
-            float *dst[3];
+            float *dst[3] = {0, 0, 0};
             rc = gather_store(X, S[1 + k], rank, dst);
             if (rc == PVOL_OK && S[1 + k].plan.rows != cnt[k]) rc = PVOL_E_INVALID;
-            c->surf[k].p = dst[0]; c->surf[k].wo = dst[1]; c->surf[k].alpha = dst[2];
+            c->surf[k].p.reset(dst[0]); c->surf[k].wo.reset(dst[1]); c->surf[k].alpha.reset(dst[2]);
             c->surf[k].n = (uint32_t)cnt[k]; c->surf[k].nPaths = paths[k];
         }
         float *dstR = 0;
         if (rc == PVOL_OK) rc = gather_store(X, S[4], rank, &dstR);
         if (rc == PVOL_OK && S[4].plan.rows != nRadTotal) rc = PVOL_E_INVALID;
-        c->dRad = dstR; c->nRad = (uint32_t)nRadTotal;
+        c->dRad.reset(dstR); c->nRad = (uint32_t)nRadTotal;
         c->surfKept = true;
         if (rc != PVOL_OK) pvol_free_surface_stores(c);
     }
@@ -558,7 +553,7 @@ int shoot(pvol_ctx *c, uint32_t n_tasks, uint32_t block_paths, uint32_t rank, Ex
     // hand the merged arrays to the context and build the search structure
     std::vector<float> hostP(3 * nVolume);
     if (!ok(hipMemcpy(hostP.data(), raw[0], sizeof(float) * 3 * nVolume, hipMemcpyDeviceToHost))) { for (float *a : raw) hipFree(a); return PVOL_E_NO_DEVICE; }
-    c->dRawP = raw[0]; c->dRawWi = raw[1]; c->dRawAlpha = raw[2];
+    c->dRawP.reset(raw[0]); c->dRawWi.reset(raw[1]); c->dRawAlpha.reset(raw[2]);
     const auto tBuild0 = std::chrono::steady_clock::now();
     rc = pvol_finish_map(c, (uint32_t)nVolume, hostP.data());
     hipDeviceSynchronize();

@@ -364,9 +364,9 @@ extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *c
                 SurfArgs sa;
                 memset(&sa, 0, sizeof(sa));
                 sa.link = specOn ? dSpecLink : 0;
-                sa.scene = c->ds; sa.rays = dRays; sa.nRays = (uint32_t)nRays; sa.out = dOut; sa.tau = dTau;
+                sa.scene = c->ds.get(); sa.rays = dRays; sa.nRays = (uint32_t)nRays; sa.out = dOut; sa.tau = dTau;
                 sa.surfOut = surfOut;
-                sa.counters = c->dCounters;
+                sa.counters = c->dCounters.get();
                 const unsigned long long groups = (nRays + 63) / 64;
                 pvol_phase_mark(c, stream, PVOL_PHASE_SURFACE);
                 if (!ok(pvol_launchers(c->hs.volKind).surface(&sa, (uint32_t)std::min<unsigned long long>(groups, (unsigned long long)c->nCU * 24ull), stream)))
