@@ -283,6 +283,8 @@ int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream);
 void *pvol_rccl_symbol(const char *name);
 // plan_size(plan_path(in)) for the tests; like pvol_rccl_symbol not part of include/pvol.h
 void pvol_plan_batch(const PlanIn *in, BatchPlan *out);
+// the shoot's merge (ShootMerge, pvol_shoot_merge.h) replayed over recorded count tables, for the tests (pvol_shoot_host.hip)
+size_t pvol_shoot_merge_replay(const uint32_t *cfg, const uint32_t *tables, uint32_t nTables, uint64_t *out, size_t cap);
 // the status pvol_set_scene gives the scene on a working device, reachable without one for the tests (pvol_scene_host.hip)
 int pvol_check_scene(const pvol_params *params, const pvol_scene *s);
 // pvol_set_scene's check of an exponential medium's arguments (PVOL_OK or PVOL_E_INVALID), reachable without a device for the tests;

@@ -6,6 +6,7 @@ Positions/weights pass through sinf/cosf/expf whose device and glibc versions di
 tolerances; a decision that flips on such an ulp would desynchronise that task's RNG stream, so the
 tests also pin the work counters, which are integer and must match exactly when nothing flipped."""
 import importlib
+import os
 
 import numpy as np
 import pytest
@@ -232,3 +233,50 @@ def test_small_block_mode_is_statistically_the_same_map(pvol):
     lam_r = np.bincount(np.argmax(ar[mono_r] != 0, axis=1), minlength=30) / mono_r.sum()
     lam_s = np.bincount(np.argmax(as_[mono_s] != 0, axis=1), minlength=30) / mono_s.sum()
     assert np.abs(lam_r - lam_s).max() < 0.01, np.abs(lam_r - lam_s).max()            # which wavelengths
+
+
+def _fresh_shoot(pvol, scene_name, n_photons, n_tasks, over, pool_start=None):
+    """One shoot in a context of its own: the 12 stats words, the volume photons and, with the stores kept, those and the radiance photons."""
+    s = load_scene(scene_name)
+    pv = pvol.PhotonVolume(abi.params_from_blob(s, n_volume_photons=n_photons, **over))
+    old = os.environ.pop("PVOL_SHOOT_POOL_START", None)
+    if pool_start is not None:
+        os.environ["PVOL_SHOOT_POOL_START"] = str(pool_start)
+    try:
+        pv.set_scene(abi.SceneHolder(s))
+        pv.preprocess(n_tasks)
+        arrays = list(pv.download_photons())
+        if over.get("keep_surface_photons"):
+            for kind in range(3):
+                arrays += list(pv.surface_photons(kind))
+            arrays += list(pv.radiance_photons())
+        return pv.shoot_stats(), arrays
+    finally:
+        os.environ.pop("PVOL_SHOOT_POOL_START", None)
+        if old is not None:
+            os.environ["PVOL_SHOOT_POOL_START"] = old
+        pv.close()
+
+
+@pytest.mark.parametrize("scene_name,n_photons,n_tasks,over,pools", [
+    ("volumescene_h", 1500, 16, {}, 1),
+    ("pinkfloyd", 4000, 4, {"keep_surface_photons": 1}, 2),
+    # final gather with direct and indirect deposits (test_surface_stores_match_oracle's scene): the radiance pool
+    ("volumescene_h", 150, 2, {"keep_surface_photons": 1, "n_indirect_photons": 40, "n_caustic_photons": 100}, 3)])
+def test_outgrown_pools_redo_the_round_to_the_same_map(pvol, scene_name, n_photons, n_tasks, over, pools):
+    """A round in which a block outgrew a pool is shot again from the saved states with larger pools.  PVOL_SHOOT_POOL_START=1 starts
+    every pool at one record a task, so each pool a scene fills grows, some more than once; the result is the default run's byte for byte."""
+    st, arrays = _fresh_shoot(pvol, scene_name, n_photons, n_tasks, over)
+    # the default run says which pools one record cannot hold: more kept records of a kind than merged blocks means some block
+    # gave more than one (photon pool, surface pool, radiance pool -- `pools` of them on this scene)
+    blocks = st["nshot"] // 4096
+    assert st["stored_volume"] > blocks
+    if pools >= 2:
+        assert st["stored_caustic"] + st["stored_direct"] + st["stored_indirect"] > blocks
+    if pools >= 3:
+        assert len(arrays[-4]) > blocks
+    st1, arrays1 = _fresh_shoot(pvol, scene_name, n_photons, n_tasks, over, pool_start=1)
+    assert st1 == st and len(st) == 12
+    assert len(arrays1) == len(arrays)
+    for a, b in zip(arrays1, arrays):
+        assert np.asarray(a).tobytes() == np.asarray(b).tobytes()
