@@ -201,7 +201,7 @@ struct SurfArgs {
     int32_t spectral;      // 1: `out` holds 60 floats per ray (Lv[30], T[30], the segments of the specular recursion): T (.) Ls is added to Lv
 };
 
-// Tile driver (pvol_tile_dev.h, pvol_tile.hip): what a SamplerRendererTask needs besides the scene.
+// Tile driver (pvol_tile_dev.h, filled by pvol_render_host.hip): what a SamplerRendererTask needs besides the scene.
 struct TileArgs {
     float r2c[16], c2w[16];        // PerspectiveCamera::RasterToCamera, Camera::CameraToWorld
     float shutterOpen, shutterClose;

@@ -188,14 +188,9 @@ extern "C" int pvol_render_frame_group_window(pvol_ctx *const *ctxs, uint32_t n,
         std::lock_guard<std::recursive_mutex> api(c->apiMu);
         if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
         const hipStream_t s = streamOf(i);
-        uint32_t nIds = 0;
-        pvol_partition_tasks(smp->n_tasks, i, n, 0, 0, &nIds);
-        std::vector<uint32_t> ids(nIds);
-        pvol_partition_tasks(smp->n_tasks, i, n, ids.data(), nIds, &nIds);
         // the root's last reduce (stage copies, sum, resolve) may still be reading this film
         if (root->groupStageEv && !ok(hipStreamWaitEvent(s, root->groupStageEv, 0))) return PVOL_E_NO_DEVICE;
-        if (!ok(hipMemsetAsync(dPixels[i], 0, filmBytes, s))) return PVOL_E_NO_DEVICE;
-        const int r = pvol_render_tasks_window_device(c, camera, film, window, smp, ids.data(), nIds, dPixels[i], 0, s);
+        const int r = render_share(c, camera, film, window, smp, i, n, dPixels[i], s);
         if (r != PVOL_OK || i == 0) return r;
         if (!c->groupFilmEv && !ok(hipEventCreateWithFlags(&c->groupFilmEv, hipEventDisableTiming))) { c->groupFilmEv = 0; return PVOL_E_NO_DEVICE; }
         return ok(hipEventRecord(c->groupFilmEv, s)) ? PVOL_OK : PVOL_E_NO_DEVICE;

@@ -1,4 +1,5 @@
-// pvol_host.h -- host-side internals shared by the host units (pvol_api.hip, pvol_scene_host.hip, pvol_map_host.hip, pvol_shoot_host.hip)
+// pvol_host.h -- host-side internals shared by the host units (pvol_api.hip, pvol_scene_host.hip, pvol_map_host.hip, pvol_shoot_host.hip,
+// pvol_render_host.hip)
 #ifndef PVOL_HOST_H
 #define PVOL_HOST_H
 #include <hip/hip_runtime.h>
@@ -114,7 +115,7 @@ enum {
     PVOL_BUF_TAU, PVOL_BUF_SPEC_LINK,   // per sample of a render batch: the T the surface term is attenuated by (TauRec); its segments (one word)
     PVOL_BUF_SEG_RAYS, PVOL_BUF_SEG_INFO, PVOL_BUF_SEG_OUT, PVOL_BUF_SEG_RECORDS,   // segment pool of the specular recursion: rays, SegInfo, 60 floats, records,
     PVOL_BUF_SEG_COUNTER, PVOL_BUF_SEG_STREAM,   // ... its fill counter (16 bytes) and the pool seen as one pvol_stream
-    PVOL_BUF_TILE_RAYS, PVOL_BUF_TILE_XY, PVOL_BUF_TILE_OUT, PVOL_BUF_TILE_STREAMS, PVOL_BUF_TILE_WINDOWS,   // tile driver (pvol_tile.hip)
+    PVOL_BUF_TILE_RAYS, PVOL_BUF_TILE_XY, PVOL_BUF_TILE_OUT, PVOL_BUF_TILE_STREAMS, PVOL_BUF_TILE_WINDOWS,   // render driver (pvol_render_host.hip)
     PVOL_BUF_LI_IN, PVOL_BUF_LI_OUT,    // device staging of the coalesced per-sample batches (pvol_li_coalesce.hip)
     PVOL_BUF_GROUP_STAGE, PVOL_N_BUFS   // pvol_render_frame_group: the other contexts' films next to the root's
 };
@@ -285,6 +286,9 @@ void *pvol_rccl_symbol(const char *name);
 void pvol_plan_batch(const PlanIn *in, BatchPlan *out);
 // the shoot's merge (ShootMerge, pvol_shoot_merge.h) replayed over recorded count tables, for the tests (pvol_shoot_host.hip)
 size_t pvol_shoot_merge_replay(const uint32_t *cfg, const uint32_t *tables, uint32_t nTables, uint64_t *out, size_t cap);
+// the plan of a render call (RenderPlan below) flattened for the tests (pvol_render_host.hip)
+size_t pvol_render_plan_flat(const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window, const pvol_sampler *smp,
+                             const uint32_t *taskIds, uint32_t nTaskIds, const int32_t *flags, int64_t tileBatchRays, uint64_t *out, size_t cap);
 // the status pvol_set_scene gives the scene on a working device, reachable without one for the tests (pvol_scene_host.hip)
 int pvol_check_scene(const pvol_params *params, const pvol_scene *s);
 // pvol_set_scene's check of an exponential medium's arguments (PVOL_OK or PVOL_E_INVALID), reachable without a device for the tests;
@@ -320,4 +324,44 @@ static inline pvol_film_window pvol_window_or_full(const pvol_film *f, const pvo
     pvol_film_window full = {0, 0, f->x_resolution, f->y_resolution};
     return full;
 }
+static inline bool film_ok(const pvol_film *f) {
+    return f && f->x_resolution > 0 && f->y_resolution > 0 && f->filter_xwidth > 0.f && f->filter_ywidth > 0.f &&
+           f->filter_xwidth <= 3.f && f->filter_ywidth <= 3.f;
+}
+// the splat of n samples into the film (pvol_tile.hip); window == NULL: the whole frame, through the full-frame kernel
+PVOL_LOCAL int film_add(pvol_ctx *c, const pvol_film *film, const pvol_film_window *window, const float *dXY, const float *dXYZ, uint32_t stride,
+                        uint64_t n, int guard, float *dPixels, hipStream_t stream);
+
+// ---- the plan of a render call (pvol_render_host.hip): every check of pvol_render_tasks_window_device, every task's
+// sub-window and sample count, and the cut of the task list into batches with all a batch reserves and uploads -- a pure function of its
+// arguments: no HIP call, no context, no environment.
+// One task's sub-window (Sampler::ComputeSubWindow) and its camera samples; pvol_render_sample_count sums the same
+static inline uint64_t pvol_task_samples(const pvol_sampler *s, uint32_t task, int32_t win[4]) {
+    pvol_compute_sub_window(s, task, win);
+    return (uint64_t)(win[1] - win[0]) * (uint64_t)(win[3] - win[2]) * s->pixel_samples;
+}
+struct RenderBatch {
+    uint32_t b0, b1;       // the batch is tasks [b0, b1) of the list; its stream table and windows are the plan's entries [b0, b1)
+    uint32_t maxRays;      // samples of its largest task
+    int32_t surfOn, specOn;
+    uint64_t nRays;        // camera samples of the batch
+    uint64_t doneRays;     // ... and of the batches in front of it: where its debug records go
+    uint64_t want[7];      // bytes reserved: PVOL_BUF_TILE_RAYS .. PVOL_BUF_TILE_WINDOWS, PVOL_BUF_TAU, PVOL_BUF_SPEC_LINK
+};
+struct PVOL_LOCAL RenderPlan {
+    int rc;
+    TileArgs tile;                       // what depends on camera and sampler only; the batch adds its buffers
+    uint64_t batchRays;                  // the work-buffer budget of a batch, in camera samples
+    std::vector<int32_t> win;            // per task of the list: x0, x1, y0, y1
+    std::vector<uint64_t> count;         // per task: camera samples
+    std::vector<pvol_stream> streams;    // per task: seed = task number, first_ray = samples in front of it within its batch
+    std::vector<RenderBatch> batches;
+};
+// surfOn: the surface integrator is on; specOn: ... and the scene holds a specular material; tileBatchRays: LaunchKnobs::tileBatchRays
+PVOL_LOCAL RenderPlan pvol_render_plan(const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window, const pvol_sampler *smp,
+                                       const uint32_t *taskIds, uint32_t nTaskIds, bool havePixels, bool haveScene, bool surfOn, bool specOn,
+                                       int64_t tileBatchRays);
+// One rank's share of a frame: its tasks (pvol_partition_tasks) into its own film, zeroed first.  The caller has the context's device set.
+PVOL_LOCAL int render_share(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window, const pvol_sampler *smp,
+                            uint32_t rank, uint32_t nRanks, float *dPixels, hipStream_t stream);
 #endif

@@ -1,5 +1,5 @@
 // pvol_liargs.h -- the argument block of the Li() kernels, ONE definition for the kernels (pvol_march.hip) and the host code that
-// fills it (pvol_api.hip, pvol_tile.hip through pvol_host.h)
+// fills it (pvol_api.hip, pvol_render_host.hip through pvol_host.h)
 #ifndef PVOL_LIARGS_H
 #define PVOL_LIARGS_H
 #include "pvol_dev.h"

@@ -1,7 +1,8 @@
-// pvol_tile.hip -- tile driver, SURVEY 8(f)-1: host side of pvol_render_tasks_device, the image film kernels
-// (ImageFilm::AddSample / WriteRGB, film/image.cpp:78-137,178-214) and the small host restatements the
-// boundary needs (Gaussian filter table, Sampler::ComputeSubWindow).  The per-task sampler/camera kernel is
-// pvol_tile_dev.h (compiled with the march kernels).
+// pvol_tile.hip -- the image film and the small host restatements at the boundary of the render driver (pvol_render_host.hip): the film
+// kernels (ImageFilm::AddSample / WriteRGB, film/image.cpp:78-137,178-214), film_add and the film entry points; the Gaussian filter
+// table, Sampler::ComputeSubWindow, the sample count of a task list and ImageFilm's crop-window arithmetic; the round-robin deal of a
+// frame's tasks to ranks and the run-time binding of RCCL.  The per-task sampler/camera kernel is pvol_tile_dev.h (compiled with the
+// march kernels).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -10,7 +11,6 @@
 #include <vector>
 
 #include <dlfcn.h>
-#include <rccl/rccl.h>   // types and enums only: the library is bound at run time (pvol_rccl_symbol)
 
 #include "pvol_host.h"
 #include "pvol_math.h"
@@ -56,13 +56,10 @@ extern "C" uint64_t pvol_render_sample_count(const pvol_sampler *s, const uint32
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; ++i) {
         int32_t w[4];
-        pvol_compute_sub_window(s, taskIds[i], w);
-        total += (uint64_t)(w[1] - w[0]) * (uint64_t)(w[3] - w[2]) * s->pixel_samples;
+        total += pvol_task_samples(s, taskIds[i], w);
     }
     return total;
 }
-
-static bool film_ok(const pvol_film *f);
 
 // ImageFilm's constructor: the film image extent of a crop window (film/image.cpp:48-51)
 extern "C" int pvol_film_window_from_crop(const pvol_film *film, const float *crop, pvol_film_window *out) {
@@ -217,10 +214,6 @@ __global__ void film_resolve_kernel(int nPix, const float *pixels, float *rgb) {
     rgb[3 * i] = r; rgb[3 * i + 1] = g; rgb[3 * i + 2] = b;
 }
 
-static bool film_ok(const pvol_film *f) {
-    return f && f->x_resolution > 0 && f->y_resolution > 0 && f->filter_xwidth > 0.f && f->filter_ywidth > 0.f &&
-           f->filter_xwidth <= 3.f && f->filter_ywidth <= 3.f;
-}
 static DevFilm dev_film(const pvol_film *f) {
     DevFilm F;
     F.xres = f->x_resolution; F.yres = f->y_resolution;
@@ -230,9 +223,8 @@ static DevFilm dev_film(const pvol_film *f) {
     return F;
 }
 
-// window == NULL: the whole frame, through the full-frame kernel
-static int film_add(pvol_ctx *c, const pvol_film *film, const pvol_film_window *window, const float *dXY, const float *dXYZ, uint32_t stride,
-                    uint64_t n, int guard, float *dPixels, hipStream_t stream) {
+int film_add(pvol_ctx *c, const pvol_film *film, const pvol_film_window *window, const float *dXY, const float *dXYZ, uint32_t stride,
+             uint64_t n, int guard, float *dPixels, hipStream_t stream) {
     if (!n) return PVOL_OK;
     const DevFilm F = dev_film(film);
     const unsigned long long blocks = (n + 255ull) / 256ull;
@@ -271,130 +263,7 @@ extern "C" int pvol_film_resolve_device(pvol_ctx *c, const pvol_film *film, cons
     return pvol_film_resolve_window_device(c, film, 0, dPixels, dRgb, hipStream);
 }
 
-// ------------------------------------------------------------------------------------------ render
-// The sampler carries the sample extent (the window's own, pvol_film_sample_extent, or any other): every size below -- the tasks'
-// sub-windows, the batches, the work buffers, the debug records -- comes from it, and only the splat reads the window.
-extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window,
-                                               const pvol_sampler *smp, const uint32_t *taskIds, uint32_t nTaskIds, float *dPixels,
-                                               const pvol_render_debug *debug, void *hipStream) {
-    if (!c || !camera || !smp || !film_ok(film) || !pvol_window_ok(film, window) || (nTaskIds && !taskIds) || !dPixels) return PVOL_E_INVALID;
-    if (!c->haveScene) return PVOL_E_NO_SCENE;
-    const uint32_t spp = smp->pixel_samples;
-    if (spp == 0 || (spp & (spp - 1)) || spp > PVOL_MAX_PIXEL_SAMPLES) return PVOL_E_INVALID;   // LDSampler rounds up to a power of two itself
-    if (camera->lens_radius != 0.f) return PVOL_E_UNSUPPORTED;
-    if (smp->n1d_count > PVOL_MAX_SAMPLE_ARRAYS || smp->n2d_count > PVOL_MAX_SAMPLE_ARRAYS) return PVOL_E_LIMIT;
-    if (smp->scatter_index >= smp->n1d_count || smp->n1d[smp->scatter_index] != 1) return PVOL_E_INVALID;
-    if (smp->n_tasks == 0 || smp->x_end < smp->x_start || smp->y_end < smp->y_start) return PVOL_E_INVALID;
-    for (uint32_t i = 0; i < nTaskIds; ++i) if (taskIds[i] >= smp->n_tasks) return PVOL_E_INVALID;
-    std::lock_guard<std::recursive_mutex> api(c->apiMu);   // the work buffers and launch scratch live in the context
-    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    hipStream_t stream = (hipStream_t)hipStream;
-
-    TileArgs T;
-    memset(&T, 0, sizeof(T));
-    memcpy(T.r2c, camera->raster_to_camera, sizeof(T.r2c));
-    memcpy(T.c2w, camera->camera_to_world, sizeof(T.c2w));
-    T.shutterOpen = camera->shutter_open; T.shutterClose = camera->shutter_close;
-    T.spp = spp; T.n1dCount = smp->n1d_count; T.n2dCount = smp->n2d_count;
-    memcpy(T.n1d, smp->n1d, sizeof(T.n1d));
-    memcpy(T.n2d, smp->n2d, sizeof(T.n2d));
-    T.scatterIndex = smp->scatter_index;
-#ifdef PVOL_TIMING_KNOBS   // timing experiments only (tools/tile_debug_*.sh build with it): every knob gives WRONG images and stream
-                           // positions, so the shipped library does not read the variable at all
-    if (const char *dbg = getenv("PVOL_TILE_DEBUG")) T.debugSkip = (uint32_t)atoi(dbg);
-#endif
-
-    // batches of tasks bounded by the work-buffer budget (rays 48 B + xy 8 B + XYZ 16 B per sample)
-    const int64_t knob = pvol_read_knobs().tileBatchRays;
-    const size_t batchRays = std::min<size_t>(knob > 0 ? (size_t)knob : (size_t)256 << 20, 0xfffff000u);
-    std::vector<int32_t> win(4 * (size_t)nTaskIds);
-    std::vector<uint64_t> count(nTaskIds);
-    for (uint32_t i = 0; i < nTaskIds; ++i) {
-        pvol_compute_sub_window(smp, taskIds[i], &win[4 * i]);
-        count[i] = (uint64_t)(win[4 * i + 1] - win[4 * i]) * (uint64_t)(win[4 * i + 3] - win[4 * i + 2]) * spp;
-        if (count[i] > batchRays) return PVOL_E_LIMIT;
-    }
-    uint64_t doneRays = 0;
-    for (uint32_t b0 = 0; b0 < nTaskIds;) {
-        uint32_t b1 = b0;
-        uint64_t nRays = 0;
-        uint32_t maxRays = 0;
-        while (b1 < nTaskIds && nRays + count[b1] <= batchRays) { nRays += count[b1]; maxRays = std::max<uint32_t>(maxRays, (uint32_t)count[b1]); ++b1; }
-        const uint32_t nStreams = b1 - b0;
-        std::vector<pvol_stream> hs(nStreams);
-        uint64_t first = 0;
-        for (uint32_t i = 0; i < nStreams; ++i) {
-            memset(&hs[i], 0, sizeof(pvol_stream));
-            hs[i].seed = taskIds[b0 + i];          // RNG rng(taskNum), samplerrenderer.cpp:73
-            hs[i].first_ray = (uint32_t)first;
-            hs[i].n_rays = (uint32_t)count[b0 + i];
-            first += count[b0 + i];
-        }
-        const bool surfOn = c->hs.surf.enabled != 0 && nRays;
-        const bool specOn = surfOn && c->specOn;
-        // work buffers; with the surface integrator every sample's T, with specular surfaces in view a link word per sample (its segments)
-        const size_t want[] = {std::max<size_t>(sizeof(pvol_ray) * nRays, 64), std::max<size_t>(8 * nRays, 64), std::max<size_t>(16 * nRays, 64),
-                               sizeof(pvol_stream) * nStreams, 16 * (size_t)nStreams};
-        for (int i = 0; i < 5; ++i) if (!pvol_reserve(c->buf[PVOL_BUF_TILE_RAYS + i], want[i], stream)) return PVOL_E_NO_MEMORY;
-        if (!pvol_reserve(c->buf[PVOL_BUF_TAU], surfOn ? sizeof(TauRec) * nRays : 0, stream) ||
-            !pvol_reserve(c->buf[PVOL_BUF_SPEC_LINK], specOn ? 4 * nRays : 0, stream)) return PVOL_E_NO_MEMORY;
-        pvol_ray *dRays = pvol_buf<pvol_ray>(c, PVOL_BUF_TILE_RAYS);
-        float *dXY = pvol_buf<float>(c, PVOL_BUF_TILE_XY), *dOut = pvol_buf<float>(c, PVOL_BUF_TILE_OUT);
-        pvol_stream *dStreams = pvol_buf<pvol_stream>(c, PVOL_BUF_TILE_STREAMS);
-        int4 *dWin = pvol_buf<int4>(c, PVOL_BUF_TILE_WINDOWS);
-        TauRec *dTau = pvol_buf<TauRec>(c, PVOL_BUF_TAU);
-        uint32_t *dSpecLink = pvol_buf<uint32_t>(c, PVOL_BUF_SPEC_LINK);
-        // the previous batch's kernels still read the buffers: these copies are ordered behind them on `stream`
-        if (!ok(hipMemcpyAsync(dStreams, hs.data(), sizeof(pvol_stream) * nStreams, hipMemcpyHostToDevice, stream)) ||
-            !ok(hipMemcpyAsync(dWin, &win[4 * (size_t)b0], 16 * (size_t)nStreams, hipMemcpyHostToDevice, stream)))
-            return PVOL_E_NO_DEVICE;
-        if (!ok(hipStreamSynchronize(stream))) return PVOL_E_NO_DEVICE;   // hs / win are host temporaries
-        T.windows = dWin; T.rays = dRays; T.xy = dXY;
-        T.specOn = specOn; T.specLink = specOn ? dSpecLink : 0;
-        if (specOn && !ok(hipMemsetAsync(dSpecLink, 0, 4 * nRays, stream))) return PVOL_E_NO_DEVICE;
-        if (nRays) {
-            float *const surfOut = debug && debug->d_surf_xyz ? debug->d_surf_xyz + 3 * doneRays : 0;
-            BatchArgs b = {};
-            b.rays = dRays; b.nRays = (uint32_t)nRays; b.streams = dStreams; b.nStreams = nStreams; b.outputKind = PVOL_OUT_XYZ; b.out = dOut;
-            b.maxRaysPerStream = maxRays; b.tile = &T; b.stream = stream;
-            b.tauOut = surfOn ? dTau : 0; b.specSurfOut = specOn ? surfOut : 0;
-            int rc = pvol_launch_batch(c, b);
-            if (rc != PVOL_OK) return rc;
-            if (surfOn) {   // Ls of PhotonIntegrator::Li, composed as T * Ls + Lvi (samplerrenderer.cpp:95-97)
-                SurfArgs sa;
-                memset(&sa, 0, sizeof(sa));
-                sa.link = specOn ? dSpecLink : 0;
-                sa.scene = c->ds.get(); sa.rays = dRays; sa.nRays = (uint32_t)nRays; sa.out = dOut; sa.tau = dTau;
-                sa.surfOut = surfOut;
-                sa.counters = c->dCounters.get();
-                const unsigned long long groups = (nRays + 63) / 64;
-                pvol_phase_mark(c, stream, PVOL_PHASE_SURFACE);
-                if (!ok(pvol_launchers(c->hs.volKind).surface(&sa, (uint32_t)std::min<unsigned long long>(groups, (unsigned long long)c->nCU * 24ull), stream)))
-                    return PVOL_E_NO_DEVICE;
-            }
-            pvol_phase_mark(c, stream, PVOL_PHASE_FILM);
-            rc = film_add(c, film, window, dXY, dOut, 4, nRays, 1, dPixels, stream);
-            pvol_phase_mark(c, stream, PVOL_PHASE_END);
-            if (rc != PVOL_OK) return rc;
-        }
-        if (debug) {
-            if (debug->d_rays && nRays) hipMemcpyAsync(debug->d_rays + doneRays, dRays, sizeof(pvol_ray) * nRays, hipMemcpyDeviceToDevice, stream);
-            if (debug->d_image_xy && nRays) hipMemcpyAsync(debug->d_image_xy + 2 * doneRays, dXY, 8 * nRays, hipMemcpyDeviceToDevice, stream);
-            if (debug->d_xyz && nRays) hipMemcpyAsync(debug->d_xyz + 4 * doneRays, dOut, 16 * nRays, hipMemcpyDeviceToDevice, stream);
-            if (debug->d_streams) hipMemcpyAsync(debug->d_streams + b0, dStreams, sizeof(pvol_stream) * nStreams, hipMemcpyDeviceToDevice, stream);
-        }
-        doneRays += nRays;
-        b0 = b1;
-    }
-    return PVOL_OK;
-}
-extern "C" int pvol_render_tasks_device(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *smp,
-                                        const uint32_t *taskIds, uint32_t nTaskIds, float *dPixels, const pvol_render_debug *debug,
-                                        void *hipStream) {
-    return pvol_render_tasks_window_device(c, camera, film, 0, smp, taskIds, nTaskIds, dPixels, debug, hipStream);
-}
-
-// ------------------------------------------------------------------------------------------ multi-GPU frame (north_star)
+// ------------------------------------------------------------------------------------------ tasks of a rank, RCCL
 // The frame's render tasks dealt round-robin to the ranks: rank r renders tasks r, r + n, r + 2n, ... so that every rank's share
 // is spread over the whole frame (SamplerRenderer::Render's task loop, renderers/samplerrenderer.cpp:206-221, cut n ways).
 extern "C" int pvol_partition_tasks(uint32_t nTasks, uint32_t rank, uint32_t nRanks, uint32_t *outIds, uint32_t capacity, uint32_t *nOut) {
@@ -419,36 +288,4 @@ extern "C" void *pvol_rccl_symbol(const char *name) {
             if ((lib = dlopen(nm, RTLD_NOW | RTLD_GLOBAL))) break;
     });
     return lib ? dlsym(lib, name) : 0;
-}
-typedef ncclResult_t (*nccl_reduce_fn)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, int, ncclComm_t, hipStream_t);
-
-// One rank of an N-GPU frame: its share of the render tasks into its own film (the window's pixels), ONE ncclReduce(sum) of the film to rank 0
-// (the Gaussian filter splats across tile borders, film/image.cpp:82-134, so tiles cannot simply be gathered), resolve on rank 0.
-// Every rank holds the whole photon map beforehand: pvol_preprocess with the same seeds on each rank, or pvol_preprocess_ranks,
-// which shares the shoot and leaves the same map on all of them.
-extern "C" int pvol_render_frame_ranks_window(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_film_window *window,
-                                              const pvol_sampler *smp, uint32_t rank, uint32_t nRanks, void *ncclComm, float *dPixels,
-                                              float *dRgb, void *hipStream) {
-    if (!c || !smp || !film_ok(film) || !pvol_window_ok(film, window) || !dPixels || !nRanks || rank >= nRanks) return PVOL_E_INVALID;
-    if (nRanks > 1 && !ncclComm) return PVOL_E_INVALID;
-    nccl_reduce_fn reduce = 0;
-    if (nRanks > 1 && !(reduce = (nccl_reduce_fn)pvol_rccl_symbol("ncclReduce"))) return PVOL_E_NO_DEVICE;   // no RCCL in reach
-    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    hipStream_t stream = (hipStream_t)hipStream;
-    uint32_t n = 0;
-    pvol_partition_tasks(smp->n_tasks, rank, nRanks, 0, 0, &n);
-    std::vector<uint32_t> ids(n);
-    pvol_partition_tasks(smp->n_tasks, rank, nRanks, ids.data(), n, &n);
-    const pvol_film_window w = pvol_window_or_full(film, window);
-    const size_t nFloats = (size_t)w.x_pixel_count * w.y_pixel_count * 4;
-    if (!ok(hipMemsetAsync(dPixels, 0, nFloats * sizeof(float), stream))) return PVOL_E_NO_DEVICE;
-    int rc = pvol_render_tasks_window_device(c, camera, film, window, smp, ids.data(), n, dPixels, 0, hipStream);
-    if (rc != PVOL_OK) return rc;
-    if (nRanks > 1 && reduce(dPixels, dPixels, nFloats, ncclFloat, ncclSum, 0, (ncclComm_t)ncclComm, stream) != ncclSuccess) return PVOL_E_NO_DEVICE;
-    if (rank == 0 && dRgb) rc = pvol_film_resolve_window_device(c, film, window, dPixels, dRgb, hipStream);
-    return rc;
-}
-extern "C" int pvol_render_frame_ranks(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, const pvol_sampler *smp,
-                                       uint32_t rank, uint32_t nRanks, void *ncclComm, float *dPixels, float *dRgb, void *hipStream) {
-    return pvol_render_frame_ranks_window(c, camera, film, 0, smp, rank, nRanks, ncclComm, dPixels, dRgb, hipStream);
 }

@@ -249,36 +249,50 @@ def _rel_l2(got, ref):
     return np.linalg.norm(got - ref, axis=1) / np.maximum(np.linalg.norm(ref, axis=1), 1e-4 * scale)
 
 
+def _surface_context(name, cases, caustic_tag):
+    """The capture `name` and a context with its scene, photon map and the capture's surface integrator (caustic map caustic_<tag>.bin)."""
+    from conftest import GOLD, blob
+    s, p, cam, film, smp, c = load_render_case(name)
+    cb = blob.load(os.path.join(GOLD, "caustic_%s.bin" % caustic_tag))
+    pv = _pvol().PhotonVolume(p)
+    try:
+        pv.set_scene(abi.SceneHolder(s))
+        pv.upload_photons(*load_photons(cases[name][1]))
+        pv.set_surface_integrator(int(c["surf.params.i"][0]), float(c["surf.params.f"][0]), 5, bool(c["surf.params.i"][1]),
+                                  (cb["p"].reshape(-1, 3), cb["wo"].reshape(-1, 3), cb["alpha"].reshape(-1, 30)), int(cb["n_paths"][0]))
+    except Exception:
+        pv.close()
+        raise
+    return pv, cam, film, smp, c
+
+
+def _check_surface_capture(r, c, film):
+    """Draws in front of every volume Li() and the stream ends exactly; Ls, T * Ls + Lvi and the film within 1e-4."""
+    np.testing.assert_array_equal(r["xy"].ravel(), c["samples.image"])
+    np.testing.assert_array_equal(r["rays"]["maxt"], c["rays.t"][1::2])
+    np.testing.assert_array_equal(r["rays"]["rng_skip"], c["rays.skip"])          # sampler draws + the surface integrator's (its whole tree)
+    np.testing.assert_array_equal(r["streams"]["end_draw"], c["task.end_draw"])
+    ref_s = c["surf.xyz"].reshape(-1, 3)
+    err = _rel_l2(r["surf_xyz"], ref_s)
+    assert err.max() <= 1e-4, "surface Li per-sample rel L2 %.3g at %d" % (err.max(), err.argmax())
+    ref = c["xyzT"].reshape(-1, 4)
+    err = _rel_l2(r["xyzT"][:, :3], ref[:, :3])
+    assert err.max() <= 1e-4, "T * Ls + Lvi per-sample rel L2 %.3g at %d" % (err.max(), err.argmax())
+    refpix = c["film.pixels"].reshape(film.y_resolution, film.x_resolution, 4)
+    np.testing.assert_allclose(r["pixels"], refpix, rtol=1e-4, atol=1e-5 * np.abs(refpix).max())
+
+
 @pytest.mark.parametrize("name", list(RENDER_SURF_CASES))
 def test_surface_integrator_matches_reference_capture(torch_cuda, name):
     """The reference's own PhotonIntegrator + PhotonVolumeIntegrator records (oracle/ref_capture.cpp `render ... surface`):
     draws in front of every volume Li() and the stream ends exactly; Ls, T * Ls + Lvi and the film within 1e-4."""
-    from conftest import GOLD, blob
-    pvol = _pvol()
-    s, p, cam, film, smp, c = load_render_case(name)
-    cb = blob.load(os.path.join(GOLD, "caustic_vh.bin"))
-    pv = pvol.PhotonVolume(p)
+    pv, cam, film, smp, c = _surface_context(name, RENDER_SURF_CASES, "vh")
     try:
-        pv.set_scene(abi.SceneHolder(s))
-        pv.upload_photons(*load_photons(RENDER_SURF_CASES[name][1]))
-        pv.set_surface_integrator(int(c["surf.params.i"][0]), float(c["surf.params.f"][0]), 5, bool(c["surf.params.i"][1]),
-                                  (cb["p"].reshape(-1, 3), cb["wo"].reshape(-1, 3), cb["alpha"].reshape(-1, 30)), int(cb["n_paths"][0]))
         n = len(c["samples.time"])
         r = _render_surface(torch_cuda, pv, cam, film, smp, c["tasks"], n)
         assert pv.march_kernel_name() == "li_group_kernel"
-        np.testing.assert_array_equal(r["xy"].ravel(), c["samples.image"])
-        np.testing.assert_array_equal(r["rays"]["maxt"], c["rays.t"][1::2])
-        np.testing.assert_array_equal(r["rays"]["rng_skip"], c["rays.skip"])          # sampler draws + the surface integrator's
-        np.testing.assert_array_equal(r["streams"]["end_draw"], c["task.end_draw"])
-        ref_s = c["surf.xyz"].reshape(-1, 3)
-        assert (ref_s.sum(1) > 0).mean() > 0.5
-        err = _rel_l2(r["surf_xyz"], ref_s)
-        assert err.max() <= 1e-4, "surface Li per-sample rel L2 %.3g at %d" % (err.max(), err.argmax())
-        ref = c["xyzT"].reshape(-1, 4)
-        err = _rel_l2(r["xyzT"][:, :3], ref[:, :3])
-        assert err.max() <= 1e-4, "T * Ls + Lvi per-sample rel L2 %.3g at %d" % (err.max(), err.argmax())
-        refpix = c["film.pixels"].reshape(film.y_resolution, film.x_resolution, 4)
-        np.testing.assert_allclose(r["pixels"], refpix, rtol=1e-4, atol=1e-5 * np.abs(refpix).max())
+        assert (c["surf.xyz"].reshape(-1, 3).sum(1) > 0).mean() > 0.5
+        _check_surface_capture(r, c, film)
         # switched off again: the volume-only records of the same frame come back
         pv.set_surface_integrator(off=True)
         r0 = _render_surface(torch_cuda, pv, cam, film, smp, c["tasks"], n)
@@ -295,32 +309,105 @@ def test_specular_recursion_matches_reference_capture(torch_cuda, name):
     surface draws and its own volume Li() walked in the stream's order (two lights: the FUSED pre-pass), the segments' radiance
     folded back through f |cos| / pdf and the transmittances.  Against the reference's own records: draws in front of every
     camera sample's volume Li() and the stream ends exactly; surface radiance, T * Ls + Lvi and the film within 1e-4."""
-    from conftest import GOLD, blob
+    pv, cam, film, smp, c = _surface_context(name, RENDER_SPECULAR_CASES, RENDER_SPECULAR_CASES[name][1])
+    try:
+        r = _render_surface(torch_cuda, pv, cam, film, smp, c["tasks"], len(c["samples.time"]))
+        assert (c["surf.draws"] > 151).sum() > 20                                      # samples through the glass: nested Li() draws
+        _check_surface_capture(r, c, film)
+    finally:
+        pv.close()
+
+
+def _task_counts(smp, tasks):
+    return [_pvol().render_sample_count(smp, [t]) for t in tasks]
+
+
+class _batch_rays:
+    """PVOL_TILE_BATCH_RAYS (read at every render call) for the length of a with block."""
+    def __init__(self, value):
+        self.env = {} if value is None else {"PVOL_TILE_BATCH_RAYS": str(value)}
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.env}
+        os.environ.update(self.env)
+
+    def __exit__(self, *exc):
+        _restore(self.old)
+
+
+@pytest.mark.parametrize("name,cases", [("vh_surf", RENDER_SURF_CASES), ("pf_surf", RENDER_SPECULAR_CASES)])
+def test_surface_and_specular_captures_in_several_batches(torch_cuda, name, cases):
+    """The batch budget at the largest task's sample count: every batch after the first reserves and fills its own TauRec (and, with
+    glass in view, link) buffer and reports the surface term at 3 * (samples of the batches before it).  Same bars as unbatched."""
+    pv, cam, film, smp, c = _surface_context(name, cases, cases[name][1])
+    try:
+        counts = _task_counts(smp, c["tasks"])
+        assert sum(counts) == len(c["samples.time"]) > 2 * max(counts)   # at least three batches
+        with _batch_rays(max(counts)):
+            r = _render_surface(torch_cuda, pv, cam, film, smp, c["tasks"], sum(counts))
+        _check_surface_capture(r, c, film)
+    finally:
+        pv.close()
+
+
+def test_three_cuts_of_one_frame_agree(torch_cuda):
+    """vh in one batch, in batches of the largest task, and of the largest plus the smallest non-empty task: the cut moves no ray, no
+    image sample and no stream end by a bit, and every cut passes the capture's bars."""
+    pv, s, p, cam, film, smp, c, old = _make("vh")
+    try:
+        counts = _task_counts(smp, c["tasks"])
+        big, small = max(counts), min(n for n in counts if n)
+        cuts = []
+        for knob in (None, big, big + small):
+            with _batch_rays(knob):
+                cuts.append(_render(torch_cuda, pv, cam, film, smp, c["tasks"], sum(counts)))
+        for r in cuts:
+            _check_against_capture(r, c, film)
+        for r in cuts[1:]:
+            assert r["rays"].tobytes() == cuts[0]["rays"].tobytes()
+            np.testing.assert_array_equal(r["xy"], cuts[0]["xy"])
+            np.testing.assert_array_equal(r["streams"]["end_draw"], cuts[0]["streams"]["end_draw"])
+    finally:
+        pv.close()
+        _restore(old)
+
+
+def test_a_refused_render_leaves_no_phase_open(torch_cuda):
+    """Phase timing on.  A render refused by its plan (thin-lens camera) and one refused by the batch's plan (surface integrator over
+    a VolumeGrid: pvol_launch_batch, PVOL_E_UNSUPPORTED) charge nothing to SURFACE or FILM, and the good render after them reports
+    its own TILE, MARCH and FILM.  Both refusals come before the first mark: no status return of the ABI lies behind one (what
+    follows a mark fails only with the device, PVOL_E_NO_DEVICE), so the closing of an open phase is not reachable from here."""
+    import ctypes as C
     pvol = _pvol()
-    s, p, cam, film, smp, c = load_render_case(name)
-    tag = RENDER_SPECULAR_CASES[name][1]
-    cb = blob.load(os.path.join(GOLD, "caustic_%s.bin" % tag))
+    s, p, cam, film, smp, c = load_render_case("grid16")
+    n = len(c["samples.time"])
     pv = pvol.PhotonVolume(p)
+
+    def phases():
+        torch_cuda.cuda.synchronize()
+        v = (C.c_double * 6)()
+        assert pvol.lib().pvol_get_phase_ms(pv._h, v, 1) == abi.PVOL_OK
+        assert np.isfinite(list(v)).all()
+        return list(v)
     try:
         pv.set_scene(abi.SceneHolder(s))
-        pv.upload_photons(*load_photons(tag))
-        pv.set_surface_integrator(int(c["surf.params.i"][0]), float(c["surf.params.f"][0]), 5, bool(c["surf.params.i"][1]),
-                                  (cb["p"].reshape(-1, 3), cb["wo"].reshape(-1, 3), cb["alpha"].reshape(-1, 30)), int(cb["n_paths"][0]))
-        n = len(c["samples.time"])
-        r = _render_surface(torch_cuda, pv, cam, film, smp, c["tasks"], n)
-        np.testing.assert_array_equal(r["xy"].ravel(), c["samples.image"])
-        np.testing.assert_array_equal(r["rays"]["maxt"], c["rays.t"][1::2])
-        assert (c["surf.draws"] > 151).sum() > 20                                      # samples through the glass: nested Li() draws
-        np.testing.assert_array_equal(r["rays"]["rng_skip"], c["rays.skip"])          # sampler + the whole tree of the surface integrator
-        np.testing.assert_array_equal(r["streams"]["end_draw"], c["task.end_draw"])
-        ref_s = c["surf.xyz"].reshape(-1, 3)
-        err = _rel_l2(r["surf_xyz"], ref_s)
-        assert err.max() <= 1e-4, "surface Li per-sample rel L2 %.3g at %d" % (err.max(), err.argmax())
-        ref = c["xyzT"].reshape(-1, 4)
-        err = _rel_l2(r["xyzT"][:, :3], ref[:, :3])
-        assert err.max() <= 1e-4, "T * Ls + Lvi per-sample rel L2 %.3g at %d" % (err.max(), err.argmax())
-        refpix = c["film.pixels"].reshape(film.y_resolution, film.x_resolution, 4)
-        np.testing.assert_allclose(r["pixels"], refpix, rtol=1e-4, atol=1e-5 * np.abs(refpix).max())
+        pv.upload_photons(*load_photons(RENDER_CASES["grid16"][1]))
+        pv.enable_phase_timing(True)
+        lens = abi.make_camera(c["camera.raster_to_camera"], c["camera.camera_to_world"], lens_radius=0.1)
+        with pytest.raises(pvol.PvolError) as e:
+            _render(torch_cuda, pv, lens, film, smp, c["tasks"], n)
+        assert e.value.status == abi.PVOL_E_UNSUPPORTED
+        ms = phases()
+        assert ms[3] == 0 and ms[4] == 0
+        pv.set_surface_integrator(50, 0.1)
+        with pytest.raises(pvol.PvolError) as e:
+            _render_surface(torch_cuda, pv, cam, film, smp, c["tasks"], n)
+        assert e.value.status == abi.PVOL_E_UNSUPPORTED
+        pv.set_surface_integrator(off=True)
+        r = _render(torch_cuda, pv, cam, film, smp, c["tasks"], n)
+        ms = phases()
+        assert ms[0] > 0 and ms[2] > 0 and ms[4] > 0 and ms[3] == 0
+        _check_against_capture(r, c, film)
     finally:
         pv.close()
 
