@@ -163,6 +163,13 @@ class SceneHolder:
         self.tris["flip_normal"][:nt] = b["tris.flip"]
         s.n_triangles = nt
         s.triangles = self.tris.ctypes.data_as(C.POINTER(Triangle))
+        # per-vertex shading normals (optional key "tris.n", [nt, 9]): not part of pvol_scene, PhotonVolume.set_scene hands them to
+        # pvol_set_triangle_normals
+        self.tri_normals = None
+        if "tris.n" in b:
+            self.tri_normals = np.ascontiguousarray(b["tris.n"], dtype=np.float32).reshape(-1, 9)
+            if len(self.tri_normals) != nt:
+                raise ValueError("tris.n has %d rows for %d triangles" % (len(self.tri_normals), nt))
         nm = len(b["mats.kind"])
         self.mats = (Material * max(nm, 1))()
         for i in range(nm):

@@ -107,6 +107,9 @@ struct DevScene {
     const DevShootScene *shootScene;  // materials of the triangles (device copy of the shooter's scene)
     // ExponentialDensity (volumes/exponential.h:43-68): density a * expf(-b * Dot(Pobj - extent.pMin, upDir)); upDir normalised on the host
     float expA, expB, expUp[3];
+    // per-vertex shading normals (pvol_set_triangle_normals, pvol_shading_dev.h): [triangles][9] in the scene's ORIGINAL triangle order,
+    // world space, not normalised; nine zeros = this triangle has none.  0 = the scene has none.
+    const float *triN;
 };
 
 // One lookup li_group_kernel hands to li_fixup_kernel (pvol_group_dev.h)

@@ -141,6 +141,8 @@ struct pvol_ctx {
     // triangle hierarchy of a scene with more than PVOL_MAX_TRIS triangles (pvol_bvh.hip), else empty
     DevPtr<float4> dBvhNodes, dBvhTris;
     std::vector<int32_t> triMatHost;   // material of every triangle of the scene (host copy, any size)
+    uint32_t nSceneTris = 0;           // triangles of the scene set last
+    DevPtr<float> dTriN;               // pvol_set_triangle_normals: [nSceneTris][9] in the scene's order (hs.triN), else empty
     double bvhBuildMs = 0.0;
     // photon map
     DevPtr<float> dRawP, dRawWi, dRawAlpha;  // upload order (kept for pvol_download_photons)
@@ -291,6 +293,8 @@ size_t pvol_render_plan_flat(const pvol_camera *camera, const pvol_film *film, c
                              const uint32_t *taskIds, uint32_t nTaskIds, const int32_t *flags, int64_t tileBatchRays, uint64_t *out, size_t cap);
 // the status pvol_set_scene gives the scene on a working device, reachable without one for the tests (pvol_scene_host.hip)
 int pvol_check_scene(const pvol_params *params, const pvol_scene *s);
+// pvol_set_triangle_normals' argument checks against the scene `s`, reachable without a device for the tests (pvol_scene_host.hip)
+int pvol_check_triangle_normals(const pvol_scene *s, const float *n, uint32_t nTriangles);
 // pvol_set_scene's check of an exponential medium's arguments (PVOL_OK or PVOL_E_INVALID), reachable without a device for the tests;
 // up3 (optional) gets the normalised updir
 int pvol_check_exponential(const pvol_volume *v, float *up3);

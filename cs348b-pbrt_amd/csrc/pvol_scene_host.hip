@@ -138,6 +138,19 @@ int pvol_check_scene(const pvol_params *params, const pvol_scene *s) {
     return pvol_scene_image(params, s, &img);
 }
 
+// Arguments of pvol_set_triangle_normals against a scene of sceneTris triangles, checked without a device: NULL with count 0 (clear)
+// is fine; otherwise one row of nine finite floats per triangle of the scene.
+static int check_triangle_normals(uint32_t sceneTris, const float *n, uint32_t nTriangles) {
+    if (!n) return nTriangles == 0 ? PVOL_OK : PVOL_E_INVALID;
+    if (nTriangles != sceneTris) return PVOL_E_INVALID;
+    for (size_t i = 0, m = (size_t)nTriangles * 9; i < m; ++i) if (!finite_f(n[i])) return PVOL_E_INVALID;
+    return PVOL_OK;
+}
+int pvol_check_triangle_normals(const pvol_scene *s, const float *n, uint32_t nTriangles) {
+    if (!s) return PVOL_E_INVALID;
+    return check_triangle_normals(s->n_triangles, n, nTriangles);
+}
+
 }  // extern "C"
 
 // The order of the checks is part of the behaviour (a scene with several faults answers with the first): volume kind, counts,
@@ -322,8 +335,35 @@ extern "C" int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
     c->triMatHost.swap(img.primMat);
     c->maxDensity = img.maxDensity;
     pvol_free_caustic_map(c);
+    c->dTriN.reset();   // vertex normals belong to the scene they were set on (h.triN is zero)
+    c->nSceneTris = s->n_triangles;
     c->hs = h;
     c->hsh = img.shoot;
     c->haveScene = true;
+    return PVOL_OK;
+}
+
+// Per-vertex shading normals of the scene's triangles (Triangle::GetShadingGeometry, shapes/trianglemesh.cpp:293-368): a side array
+// in the scene's triangle order, which both closest-hit routines index by the hit's original triangle number (pvol_shading_dev.h).
+extern "C" int pvol_set_triangle_normals(pvol_ctx *c, const float *n, uint32_t nTriangles) {
+    if (!c) return PVOL_E_INVALID;
+    std::lock_guard<std::recursive_mutex> api(c->apiMu);
+    if (!c->haveScene) return PVOL_E_NO_SCENE;
+    int rc = check_triangle_normals(c->nSceneTris, n, nTriangles);
+    if (rc != PVOL_OK) return rc;
+    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
+    DevPtr<float> dn;
+    if (n && nTriangles) {
+        if (!dn.alloc((size_t)nTriangles * 9)) return PVOL_E_NO_MEMORY;
+        if (!ok(hipMemcpy(dn.get(), n, sizeof(float) * 9 * (size_t)nTriangles, hipMemcpyHostToDevice))) return PVOL_E_NO_DEVICE;
+    }
+    // commit: kernels of earlier batches may still read the old array.  Every check and the upload come first, so a rejected call
+    // changes nothing; only a device copy that fails here is put back best effort (a second failure would leave the device copy of
+    // the scene behind the host's, as in pvol_set_scene).
+    if (!ok(hipDeviceSynchronize())) return PVOL_E_NO_DEVICE;
+    const float *old = c->hs.triN;
+    c->hs.triN = dn.get();
+    if ((rc = pvol_push_scene(c)) != PVOL_OK) { c->hs.triN = old; pvol_push_scene(c); return rc; }
+    c->dTriN = std::move(dn);
     return PVOL_OK;
 }

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include "pvol_rng_dev.h"
 #include "pvol_shoot_args.h"
+#include "pvol_shading_dev.h"
 
 #define SH_MAX_DEPTH 24   // frames; deeper recursion aborts the path and is counted
 #define NBIN 30
@@ -47,16 +48,18 @@ __device__ __forceinline__ int sp_lambda(float a, bool binLane) {   // extractLa
 
 // ------------------------------------------------------------------------------------------ scene queries
 struct Hit {
-    int tri, mat;
+    int tri, mat;     // tri: where the triangle's vertices lie -- scene index (linear scan) or hierarchy slot; -1 - i: sphere i
     float t, rayEps;
-    V3 p, dpdu, nn;
+    V3 p, dpdu, nn;   // nn, dpdu: the SHADING geometry where the triangle carries vertex normals (pvol_shading_dev.h), else the geometric one
 };
+// photonIsect.dg.nn, the geometric normal (BSDF::f's side test, the radiance photon's normal): the hit's nn unless the scene has vertex normals
+__device__ __forceinline__ V3 hit_ng(const DevScene &S, const Hit &h) { return (S.triN && h.tri >= 0) ? geometric_normal(S, h.tri) : h.nn; }
 // Scene::Intersect (core/scene.h:50-56): closest hit.  The serial scan tightens maxt with `t > maxt` rejections, so of
 // several triangles at the same t the LATER one wins: one triangle per lane, minimum over the wave, highest lane of the tie.
-__device__ bool scene_closest(const DevScene &S, const DevShootScene &H, V3 o, V3 d, float mint, float *maxt, Hit *hit, int lane) {
+__device__ __forceinline__ bool scene_closest(const DevScene &S, const DevShootScene &H, V3 o, V3 d, float mint, float *maxt, Hit *hit, int lane) {
     float tk = INFINITY;
     bool any = false;
-    int best = -1;
+    int best = -1, where = -1;
     V3 p1, p2, p3;
     bool flip;
     if (S.bvhNodes) {   // large scene: every lane walks the hierarchy with the same ray (pvol_bvh_dev.h)
@@ -67,6 +70,7 @@ __device__ bool scene_closest(const DevScene &S, const DevShootScene &H, V3 o, V
         const float4 q1 = S.bvhTris[3 * slot], q2 = S.bvhTris[3 * slot + 1], q3 = S.bvhTris[3 * slot + 2];
         p1 = v3(q1.x, q1.y, q1.z); p2 = v3(q2.x, q2.y, q2.z); p3 = v3(q3.x, q3.y, q3.z);
         best = __float_as_int(q1.w);
+        where = slot;
         hit->mat = __float_as_int(q2.w);
         flip = __float_as_int(q3.w) != 0;
         }
@@ -88,6 +92,7 @@ __device__ bool scene_closest(const DevScene &S, const DevShootScene &H, V3 o, V
             p1 = v3(tr.p1[0], tr.p1[1], tr.p1[2]); p2 = v3(tr.p2[0], tr.p2[1], tr.p2[2]); p3 = v3(tr.p3[0], tr.p3[1], tr.p3[2]);
             hit->mat = H.triMat[best];
             flip = H.triFlip[best] != 0;
+            where = best;
         }
     }
     if (S.nSpheres) {   // Shape "sphere" (pvol_sphere_dev.h), tested after the triangles with the ray shortened to their hit
@@ -113,18 +118,24 @@ __device__ bool scene_closest(const DevScene &S, const DevShootScene &H, V3 o, V
     float invdet = 1.f / determinant;
     hit->dpdu = (dp1 * dv2 - dp2 * dv1) * invdet;
     V3 dpdv = (dp1 * (-du2) + dp2 * du1) * invdet;
-    hit->tri = best;
+    hit->tri = where;
     hit->t = tk;
     hit->p = o + d * tk;
     hit->rayEps = 1e-3f * tk;
     hit->nn = normalize(cross(hit->dpdu, dpdv));   // core/diffgeom.cpp:46-54
     if (flip) hit->nn = hit->nn * -1.f;
+    if (S.triN) {   // Triangle::GetShadingGeometry for a mesh with "normal N" (triN is in the scene's original order)
+        const ShadingFrame f = shading_geometry(S.triN + (size_t)best * 9, p1, p2, p3, o, d, hit->dpdu, flip);
+        if (f.any) { hit->dpdu = f.dpdu; hit->nn = f.nn; }
+    }
     return true;
 }
 
 // PhotonVolumeIntegrator::Transmittance with sample == NULL (photonvolume.cpp:15-30): one draw, Exp(-tau), one bin per lane.
 // sigTl = sigma_a + sigma_s of the lane's bin (0 on the pad lanes, which therefore return 1).
-__device__ float transmittance_bins(const DevScene &S, V3 o, V3 d, float mint, float maxt, Rng &rng, float sigTl, int lane) {
+// (every function of the shooting path is forced inline: shoot_kernel is ONE body, as the inliner used to make it on its own until the
+// path grew by the shading-normal branch -- out of line, `Rng &` sends the generator's state through memory on every call)
+__device__ __forceinline__ float transmittance_bins(const DevScene &S, V3 o, V3 d, float mint, float maxt, Rng &rng, float sigTl, int lane) {
     const float step = 4.f * S.stepSize;
     const float offset = rng_float<true>(rng, lane);
     if (S.volKind == PVOL_VOLUME_NONE) return 1.f;
@@ -198,14 +209,15 @@ __device__ __forceinline__ void concentric_disk(float u0, float u1, float *dx, f
 //          1: f_b = (fFac * Kr_b) / fDiv (specular reflection, fFac = F, fDiv = |cos wi|)
 //          2: f_b = (fFac * Kt_b) / fDiv (specular transmission, fFac = 1 - F)
 //         -1: black
-__device__ void bsdf_sample(const DevMaterial &m, V3 dpdu, V3 nn, V3 woW, float u0, float u1, float ucomp, int lambda,
+__device__ __forceinline__ void bsdf_sample(const DevScene &S, const DevMaterial &m, const Hit &h, V3 woW, float u0, float u1, float ucomp, int lambda,
                             V3 *wiW, float *pdf, int *sampledType, int *fWhich, float *fFac, float *fDiv) {
     *pdf = 0.f; *sampledType = 0; *fWhich = -1; *fFac = 0.f; *fDiv = 1.f;
     int matching = num_components(m, BSDF_ALL);
     if (matching == 0) return;
     int which = min((int)floorf(ucomp * matching), matching - 1);
     int type = m.bxdfType[which];
-    V3 sn = normalize(dpdu);
+    const V3 nn = h.nn;
+    V3 sn = normalize(h.dpdu);
     V3 tn = cross(nn, sn);
     V3 wo = v3(dot(woW, sn), dot(woW, tn), dot(woW, nn));
     V3 wi = v3(0.f, 0.f, 0.f);
@@ -251,7 +263,8 @@ __device__ void bsdf_sample(const DevMaterial &m, V3 dpdu, V3 nn, V3 woW, float 
         // reflection.cpp:583-592: f re-evaluated over the components on the sampled side; only the
         // Lambertian has a non-zero f()
         int fl = BSDF_ALL;
-        if (dot(*wiW, nn) * dot(woW, nn) > 0.f) fl &= ~BSDF_TRANSMISSION; else fl &= ~BSDF_REFLECTION;
+        const V3 ng = hit_ng(S, h);
+        if (dot(*wiW, ng) * dot(woW, ng) > 0.f) fl &= ~BSDF_TRANSMISSION; else fl &= ~BSDF_REFLECTION;   // the GEOMETRIC normal (reflection.cpp:586)
         bool lamb = false;
         for (int i = 0; i < m.nBxdf; ++i)
             if ((m.bxdfType[i] & fl) == m.bxdfType[i] && m.bxdfType[i] == (BSDF_REFLECTION | BSDF_DIFFUSE)) lamb = true;
@@ -260,7 +273,7 @@ __device__ void bsdf_sample(const DevMaterial &m, V3 dpdu, V3 nn, V3 woW, float 
 }
 
 // Light::Sample_L(scene, ls, u1, u2, time, &ray, &Ns, &pdf): spot.cpp:106-114, point.cpp:80-88, distant.cpp:82-102
-__device__ float light_emit(const DevScene &S, const DevShootScene &H, int ln, float u0, float u1, V3 *o, V3 *d, float *pdf) {
+__device__ __forceinline__ float light_emit(const DevScene &S, const DevShootScene &H, int ln, float u0, float u1, V3 *o, V3 *d, float *pdf) {
     const DevLight &l = S.lights[ln];
     if (l.kind == PVOL_LIGHT_SPOT) {
         float costheta = (1.f - u0) + u0 * l.cosTotalWidth;   // UniformSampleCone, montecarlo.cpp:405-410
@@ -341,7 +354,7 @@ struct Frame {
     bool split, spec;
 };
 #define SH_FRAME_WORDS 32
-__device__ void frame_push(float *fs, float *fa, int sp, const Frame &F, float alpha, int lane) {
+__device__ __forceinline__ void frame_push(float *fs, float *fa, int sp, const Frame &F, float alpha, int lane) {
     float *w = fs + sp * SH_FRAME_WORDS;
     if (lane == 0) {
         w[0] = F.rayO.x; w[1] = F.rayO.y; w[2] = F.rayO.z; w[3] = F.rayD.x; w[4] = F.rayD.y; w[5] = F.rayD.z;
@@ -357,7 +370,7 @@ __device__ void frame_push(float *fs, float *fa, int sp, const Frame &F, float a
     if (lane < 32) fa[sp * 32 + lane] = alpha;
     __syncthreads();
 }
-__device__ void frame_pop(const float *fs, const float *fa, int sp, Frame &F, float &alpha, int lane) {
+__device__ __forceinline__ void frame_pop(const float *fs, const float *fa, int sp, Frame &F, float &alpha, int lane) {
     const float *w = fs + sp * SH_FRAME_WORDS;
     F.rayO = v3(w[0], w[1], w[2]); F.rayD = v3(w[3], w[4], w[5]);
     F.rayMint = w[6]; F.rayMaxt = w[7];
@@ -391,7 +404,7 @@ struct PathCtx {
 // The transmittance march of photonshooter.cpp:71-80 for an ANALYTIC medium: `while (t0 < t1) { Tr = Transmittance(ray(t_i .. t0));
 // if (xi > Tr.y()) break; t0 += stepSize; }`, 64 iterations at a time, one per lane.  Every iteration draws once (the
 // offset inside Transmittance, unused by the analytic tau).  Returns true at an interaction; *t0io = the loop variable there.
-__device__ bool march_analytic(PathCtx &C, V3 rayO, V3 dn, float t_i, float *t0io, float t1, float xi, int lane) {
+__device__ __forceinline__ bool march_analytic(PathCtx &C, V3 rayO, V3 dn, float t_i, float *t0io, float t1, float xi, int lane) {
     const DevScene &S = *C.S;
     const float stepSize = C.H->shooterStep;
     float t0 = *t0io;
@@ -441,7 +454,7 @@ __device__ bool march_analytic(PathCtx &C, V3 rayO, V3 dn, float t_i, float *t0i
 // now 64 wide), then tau_b = (sum_k sigma_t,b D_k) step for each bin, and y() in bin order.  A lane that needs more than
 // GRID_KMAX densities makes the trip fall back to the serial form (returns -1).
 #define GRID_KMAX 48
-__device__ int march_grid(PathCtx &C, V3 rayO, V3 dn, float t_i, float *t0io, float t1, float xi, int lane) {
+__device__ __forceinline__ int march_grid(PathCtx &C, V3 rayO, V3 dn, float t_i, float *t0io, float t1, float xi, int lane) {
     const DevScene &S = *C.S;
     const float stepSize = C.H->shooterStep;
     const float step = 4.f * S.stepSize;   // PhotonVolumeIntegrator::Transmittance with sample == NULL (photonvolume.cpp:24-27)
@@ -503,7 +516,7 @@ __device__ int march_grid(PathCtx &C, V3 rayO, V3 dn, float t_i, float *t0io, fl
     return 0;
 }
 
-__device__ void follow_photon(PathCtx &C, V3 rayO, V3 rayD, float rayMint, float alpha, float tag, int lane) {
+__device__ __forceinline__ void follow_photon(PathCtx &C, V3 rayO, V3 rayD, float rayMint, float alpha, float tag, int lane) {
     const DevScene &S = *C.S;
     const DevShootScene &H = *C.H;
     const bool binLane = lane < NBIN;
@@ -626,7 +639,8 @@ __device__ void follow_photon(PathCtx &C, V3 rayO, V3 rayD, float rayMint, float
                     rng_skip<true>(C.rng, 288ull, lane);   // 2 x BSDF::rho (reflection.cpp:647-658)
                     if (C.outRad) {   // RadiancePhoton(p, Faceforward(nn, -photonRay.d)), photonshooter.cpp:182-189
                         if (C.nRad < C.capR) {
-                            const V3 nf = dot(F.hit.nn, F.wo) < 0.f ? F.hit.nn * -1.f : F.hit.nn;
+                            const V3 ng = hit_ng(S, F.hit);   // photonIsect.dg.nn: the geometric normal
+                            const V3 nf = dot(ng, F.wo) < 0.f ? ng * -1.f : ng;
                             float *o = C.outRad + (size_t)C.nRad * 8;
                             if (lane < 8) o[lane] = lane == 0 ? F.hit.p.x : lane == 1 ? F.hit.p.y : lane == 2 ? F.hit.p.z : lane == 3 ? nf.x : lane == 4 ? nf.y :
                                                     lane == 5 ? nf.z : lane == 6 ? __int_as_float(F.hit.mat) : 0.f;
@@ -661,7 +675,7 @@ __device__ void follow_photon(PathCtx &C, V3 rayO, V3 rayD, float rayMint, float
                 V3 wi;
                 float pdf, fFac, fDiv;
                 int flags, fWhich;
-                bsdf_sample(m, F.hit.dpdu, F.hit.nn, F.wo, ud0, ud1, uc, sp_lambda(a, binLane), &wi, &pdf, &flags, &fWhich, &fFac, &fDiv);
+                bsdf_sample(S, m, F.hit, F.wo, ud0, ud1, uc, sp_lambda(a, binLane), &wi, &pdf, &flags, &fWhich, &fFac, &fDiv);
                 if (fWhich < 0 || pdf == 0.f) continue;
                 const float *K = fWhich == 0 ? m.kd : (fWhich == 1 ? m.kr : m.kt);
                 const float Kl = binLane ? K[lane] : 0.f;

@@ -204,6 +204,11 @@ class Transform:
         m = self.m
         return np.array([F(F(m[i, 0] * x) + F(m[i, 1] * y)) + F(m[i, 2] * z) for i in range(3)], F)
 
+    def normal(self, n):     # core/transform.h:232-237: the transposed inverse, not normalised
+        x, y, z = (F(c) for c in n)
+        mi = self.minv
+        return np.array([F(F(mi[0, i] * x) + F(mi[1, i] * y)) + F(mi[2, i] * z) for i in range(3)], F)
+
     def swaps_handedness(self):   # core/transform.cpp:293-302
         m = self.m
         det = F(F(m[0, 0] * F(F(m[1, 1] * m[2, 2]) - F(m[1, 2] * m[2, 1]))) - F(m[0, 1] * F(F(m[1, 0] * m[2, 2]) - F(m[1, 2] * m[2, 0])))) + \
@@ -426,6 +431,7 @@ class _Builder:
         self.vol = ("photonvolume", _Params())
         self.camera = None
         self.lights, self.tris, self.tri_mat, self.tri_flip, self.mats, self.mat_keys = [], [], [], [], [], []
+        self.tri_n, self.have_n = [], False   # per triangle its three vertex normals (nine zeros: none); any mesh with "normal N"
         self.spheres = []
         self.volume = None
         self.in_world = False
@@ -467,8 +473,17 @@ class _Builder:
         mi = self._material_index()
         world = np.array([self.ctm.point(p) for p in P], F)   # TriangleMesh ctor: vertices go to world space (trianglemesh.cpp:73-75)
         flip = int(self.reverse ^ bool(self.ctm.swaps_handedness()))
+        # "normal N": dropped unless there is one per vertex (CreateTriangleMeshShape, trianglemesh.cpp:397-401).  The reference keeps N in
+        # object space and transforms the interpolated normal (trianglemesh.cpp:322-324); here every vertex normal goes to world space
+        # first (the map is linear, the two differ by rounding).  "vector S" and "float uv" stay unread.
+        nv = ps.one("N", ("normal",), [])
+        N = np.array(nv if len(nv) % 3 == 0 else [], F).reshape(-1, 3)
+        wn = np.array([self.ctm.normal(n) for n in N], F) if len(N) and len(N) == len(P) else None
+        self.have_n = self.have_n or wn is not None
         for t in range(len(idx) // 3):
-            self.tris.append(world[[idx[3 * t], idx[3 * t + 1], idx[3 * t + 2]]].reshape(-1))
+            v = [idx[3 * t], idx[3 * t + 1], idx[3 * t + 2]]
+            self.tris.append(world[v].reshape(-1))
+            self.tri_n.append(wn[v].reshape(-1) if wn is not None else np.zeros(9, F))
             self.tri_mat.append(mi)
             self.tri_flip.append(flip)
 
@@ -671,6 +686,8 @@ def load(path):
     d["tris.p"] = np.concatenate(b.tris).astype(F) if b.tris else np.zeros(0, F)
     d["tris.material"] = np.array(b.tri_mat, np.int32)
     d["tris.flip"] = np.array(b.tri_flip, np.int32)
+    if b.have_n:   # optional key (abi.SceneHolder): [n_triangles, 9], nine zeros for a triangle of a mesh without "normal N"
+        d["tris.n"] = np.array(b.tri_n, F).reshape(-1, 9)
     if b.spheres:   # optional keys (abi.SceneHolder): absent for scenes without spheres
         d["spheres.o2w"] = np.concatenate([_mat16(x["o2w"].m) for x in b.spheres])
         d["spheres.w2o"] = np.concatenate([_mat16(x["o2w"].minv) for x in b.spheres])

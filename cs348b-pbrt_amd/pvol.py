@@ -69,6 +69,8 @@ def lib():
         L.pvol_destroy.argtypes = [C.c_void_p]
         L.pvol_destroy.restype = None
         L.pvol_set_scene.argtypes = [C.c_void_p, C.POINTER(abi.Scene)]
+        L.pvol_set_triangle_normals.argtypes = [C.c_void_p, _f32p, C.c_uint32]
+        L.pvol_check_triangle_normals.argtypes = [C.POINTER(abi.Scene), _f32p, C.c_uint32]
         L.pvol_upload_photons.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_preprocess.argtypes = [C.c_void_p, C.c_uint32]
         L.pvol_preprocess_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
@@ -146,7 +148,7 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_get_li_coalescing_stats", "pvol_preprocess_group", "pvol_render_frame_group",
            "pvol_film_window_from_crop", "pvol_film_sample_extent", "pvol_render_tasks_window_device",
            "pvol_film_add_samples_window_device", "pvol_film_resolve_window_device", "pvol_render_frame_ranks_window",
-           "pvol_render_frame_group_window", "pvol_tile_kernel_name"]
+           "pvol_render_frame_group_window", "pvol_tile_kernel_name", "pvol_set_triangle_normals"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -218,6 +220,17 @@ class PhotonVolume:
     def set_scene(self, holder):
         self._scene = holder  # keeps the ctypes arrays alive
         _check(lib().pvol_set_scene(self._h, C.byref(holder.scene)), "pvol_set_scene")
+        if getattr(holder, "tri_normals", None) is not None:
+            self.set_triangle_normals(holder.tri_normals)
+
+    def set_triangle_normals(self, n):
+        """pvol_set_triangle_normals: n[n_triangles, 9], the world-space vertex normals of every triangle of the scene set last (nine
+        zeros: none for that triangle); None clears them.  set_scene() does this itself for a holder whose dictionary has "tris.n"."""
+        if n is None:
+            _check(lib().pvol_set_triangle_normals(self._h, None, 0), "pvol_set_triangle_normals")
+            return
+        n = np.ascontiguousarray(n, np.float32).reshape(-1, 9)
+        _check(lib().pvol_set_triangle_normals(self._h, n.ctypes.data_as(_f32p), len(n)), "pvol_set_triangle_normals")
 
     def upload_photons(self, p, wi, alpha):
         p = np.ascontiguousarray(p, np.float32).reshape(-1)

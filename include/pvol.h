@@ -296,6 +296,15 @@ void pvol_destroy(pvol_ctx *ctx);
  * range, a non-finite vertex, a sphere radius <= 0. */
 int pvol_set_scene(pvol_ctx *ctx, const pvol_scene *scene);
 
+/* Per-vertex shading normals of the scene's triangles (`"normal N"` of a trianglemesh; Triangle::GetShadingGeometry,
+ * shapes/trianglemesh.cpp:293-368, with the default uvs): n holds 9 * n_triangles floats, the three vertex normals of every triangle
+ * in the scene's triangle order and in the triangle's vertex order, in WORLD space (Transform::operator()(const Normal&) of the mesh's
+ * ObjectToWorld applied to each, not normalised).  A triangle whose nine values are all zero has no shading normals.  Call it after
+ * pvol_set_scene; NULL with n_triangles 0 clears the normals, and pvol_set_scene clears them too (as it disables the surface
+ * integrator).  PVOL_E_NO_SCENE without a scene; PVOL_E_INVALID for a count that differs from the scene's or a non-finite value; a
+ * rejected call changes nothing.  Sphere hits are untouched. */
+int pvol_set_triangle_normals(pvol_ctx *ctx, const float *n, uint32_t n_triangles);
+
 /* Installs a volume photon map computed elsewhere (e.g. by the reference's own
  * PhotonShooter) and builds the device search structure; replaces
  * `volumeMap = new KdTree<Photon>(volumePhotons)` (photonshooter.cpp:502-503).

@@ -30,6 +30,9 @@ struct HipFlatScene {
     std::vector<pvol_triangle> tris;
     std::vector<pvol_sphere> spheres;
     std::vector<pvol_material> mats;
+    // per-vertex shading normals for pvol_set_triangle_normals: nine floats per triangle of `tris` (world space, nine zeros for a
+    // triangle of a mesh without "N"); EMPTY when no mesh of the scene carries normals
+    std::vector<float> triN;
 };
 
 namespace hipflat {
@@ -130,7 +133,8 @@ inline const char *flattenMaterial(const Material *m, pvol_material *o) {
 // Fills *out from the live scene; returns NULL, or a static message naming what the path does not cover.
 inline const char *HipFlattenScene(const Scene *scene, HipFlatScene *out) {
     using namespace hipflat;
-    out->lights.clear(); out->tris.clear(); out->spheres.clear(); out->mats.clear();
+    out->lights.clear(); out->tris.clear(); out->spheres.clear(); out->mats.clear(); out->triN.clear();
+    bool anyN = false;
     pvol_scene &s = out->scene;
     memset(&s, 0, sizeof(s));
     const char *err = flattenVolume(scene->volumeRegion, &s.volume);
@@ -182,7 +186,15 @@ inline const char *HipFlattenScene(const Scene *scene, HipFlatScene *out) {
         t.material = matIndex[m];
         t.flip_normal = (tri->ReverseOrientation ^ tri->TransformSwapsHandedness) ? 1 : 0;
         out->tris.push_back(t);
+        // mesh->n stays in object space (shapes/trianglemesh.cpp:76-79); the library takes it in world space, each vertex normal through
+        // Transform::operator()(const Normal&) of the mesh's ObjectToWorld (GetShadingGeometry transforms the interpolated sum, :322-324)
+        for (int k = 0; k < 3; ++k) {
+            Normal wn(0, 0, 0);
+            if (tri->mesh->n) { wn = (*tri->mesh->ObjectToWorld)(tri->mesh->n[tri->v[k]]); anyN = true; }
+            out->triN.push_back(wn.x); out->triN.push_back(wn.y); out->triN.push_back(wn.z);
+        }
     }
+    if (!anyN) out->triN.clear();
     s.n_lights = (uint32_t)out->lights.size(); s.lights = out->lights.empty() ? NULL : &out->lights[0];
     s.n_triangles = (uint32_t)out->tris.size(); s.triangles = out->tris.empty() ? NULL : &out->tris[0];
     s.n_materials = (uint32_t)out->mats.size(); s.materials = out->mats.empty() ? NULL : &out->mats[0];

@@ -111,6 +111,10 @@ public:
         if (why) Severe("photonvolume_hip: %s", why);
         int rc = pvol_set_scene(ctx, &flat.scene);
         if (rc != PVOL_OK) Severe("photonvolume_hip: pvol_set_scene: %s", pvol_strerror(rc));
+        if (!flat.triN.empty()) {   // meshes with "normal N": the shading frame of Triangle::GetShadingGeometry
+            rc = pvol_set_triangle_normals(ctx, &flat.triN[0], flat.scene.n_triangles);
+            if (rc != PVOL_OK) Severe("photonvolume_hip: pvol_set_triangle_normals: %s", pvol_strerror(rc));
+        }
     }
 
     // The shoot half of Preprocess shared by the ranks of a multi-GPU render (pvol_preprocess_ranks): rank `rank` of `nRanks`
