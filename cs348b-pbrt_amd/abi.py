@@ -281,6 +281,10 @@ class SurfaceParams(C.Structure):   # pvol_surface_params
                 ("reserved", C.c_uint32 * 1)]
 
 
+class PhotonArray(C.Structure):   # pvol_photon_array: one surface map handed to pvol_compute_radiance_arrays
+    _fields_ = [("p", C.POINTER(C.c_float)), ("wi", C.POINTER(C.c_float)), ("alpha", C.POINTER(C.c_float)), ("n", C.c_uint32), ("n_paths", C.c_uint32)]
+
+
 def make_camera(raster_to_camera, camera_to_world, shutter_open=0.0, shutter_close=1.0, lens_radius=0.0, focal_distance=1e30):
     c = Camera()
     for i, v in enumerate(np.asarray(raster_to_camera, np.float32).reshape(16)):

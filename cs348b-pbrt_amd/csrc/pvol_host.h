@@ -6,6 +6,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <vector>
 #include "pvol_dev.h"
@@ -132,6 +133,23 @@ struct PVOL_LOCAL PhotonGrid {
     size_t cells() const { return (size_t)gdim[0] * gdim[1] * gdim[2]; }
 };
 
+// The Inside() test a photon must pass to count (pvol_grid.hip); PVOL_VOLUME_GRID with a zero extent passes every photon.
+struct MapFilter { int32_t volKind; float extLo[3], extHi[3], w2v[16]; };
+// One map from its raw device arrays raw = {p[n][3], wi[n][3], alpha[n][30]} (n > 0) and the host copy of the positions: cells of
+// firstCell(volume of the photons' box), grown until the grid has at most 2^24 of them; every extent of the box at least minExt
+// (pvol_map_host.hip).
+PVOL_LOCAL int build_photon_grid(PhotonGrid &G, const float *const raw[3], const float *hostP, uint32_t n, double minExt,
+                                 const std::function<double(double)> &firstCell, const MapFilter &f);
+
+// What pvol_compute_radiance leaves (pvol_radiance.hip): the radiance photons in input order with their Lo, and the radiance map
+// over them -- a PhotonGrid whose wi4 holds the normal and whose 32-float rows hold Lo.
+struct PVOL_LOCAL RadianceResult {
+    bool have = false;         // a compute succeeded since the last shoot (n may be 0)
+    uint32_t n = 0;
+    DevPtr<float> p, nrm, lo;  // [n][3], [n][3], [n][30]
+    PhotonGrid map;
+};
+
 struct pvol_ctx {
     pvol_params params = {};
     bool haveScene = false;
@@ -185,6 +203,7 @@ struct pvol_ctx {
     bool surfKept = false;   // the last pvol_preprocess ran with keep_surface_photons and left its stores here
     DevPtr<float> dRad;    // radiance photons: [n][8] = p(3) n(3) material index, pad
     uint32_t nRad = 0;
+    RadianceResult rad;    // pvol_compute_radiance*: dropped by every shoot and by pvol_free_surface_stores
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     PhotonGrid causticMap;
     // specular recursion of the surface integrator (pvol_spec_dev.h): segments of the camera samples that meet glass
@@ -298,6 +317,11 @@ int pvol_check_triangle_normals(const pvol_scene *s, const float *n, uint32_t nT
 // pvol_set_scene's check of an exponential medium's arguments (PVOL_OK or PVOL_E_INVALID), reachable without a device for the tests;
 // up3 (optional) gets the normalised updir
 int pvol_check_exponential(const pvol_volume *v, float *up3);
+// the argument checks of pvol_compute_radiance (what 0), pvol_compute_radiance_arrays (1) and pvol_radiance_lookup* (2), reachable
+// without a device for the tests (pvol_radiance.hip).  haveState: the stores are kept (0) / a compute has succeeded (2); a, b: the
+// radiance photons' p and n (1) or the queries' (2); hostPointers: a, b and the maps can be read (their values must be finite)
+int pvol_check_radiance(int what, int haveCtx, int haveState, int32_t nLookup, float maxDist, const pvol_photon_array *const *maps, const float *a,
+                        const float *b, const float *rhoR, const float *rhoT, uint32_t count, const void *outLo, const void *outFound, int hostPointers);
 // the largest density of a checked exponential medium over its extent (feeds roulette_possible like a VolumeGrid's maximum); up3: the normalised updir
 float pvol_exponential_max_density(const pvol_volume *v, const float *up3);
 }

@@ -1,6 +1,6 @@
 // pvol_map_host.hip -- the two photon maps of a context: the volume map (pvol_upload_photons, or pvol_finish_map behind the
 // shooter) and the surface integrator's caustic map (pvol_set_surface_integrator).  Both are a PhotonGrid (pvol_host.h) built by
-// build_photon_grid; what differs -- the first cell size, the volume map's second level -- stays with its caller.  Host code only:
+// build_photon_grid, as are the maps of pvol_compute_radiance (pvol_radiance.hip); what differs -- the first cell size, the volume map's second level -- stays with its caller.  Host code only:
 // this unit defines no kernel (the build's kernels are in pvol_grid.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -15,9 +15,6 @@
 
 static bool ok(hipError_t e) { return e == hipSuccess; }
 
-// The Inside() test a photon must pass to count (pvol_grid.hip); PVOL_VOLUME_GRID with a zero extent passes every photon.
-struct MapFilter { int32_t volKind; float extLo[3], extHi[3], w2v[16]; };
-
 static GridBuildArgs grid_args(const PhotonGrid &G, const float *const raw[3], const MapFilter &f, int sub) {
     GridBuildArgs g;
     memset(&g, 0, sizeof(g));
@@ -30,9 +27,8 @@ static GridBuildArgs grid_args(const PhotonGrid &G, const float *const raw[3], c
     return g;
 }
 
-// One map from its raw device arrays raw = {p[n][3], wi[n][3], alpha[n][30]} (n > 0) and the host copy of the positions: cells of
-// firstCell(volume of the photons' box), grown until the grid has at most 2^24 of them; every extent of the box at least minExt.
-static int build_photon_grid(PhotonGrid &G, const float *const raw[3], const float *hostP, uint32_t n, double minExt,
+// One map from its raw device arrays (pvol_host.h)
+int build_photon_grid(PhotonGrid &G, const float *const raw[3], const float *hostP, uint32_t n, double minExt,
                              const std::function<double(double)> &firstCell, const MapFilter &f) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (uint32_t i = 0; i < n; ++i)

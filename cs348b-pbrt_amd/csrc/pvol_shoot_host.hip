@@ -48,6 +48,7 @@ extern "C" void pvol_free_surface_stores(pvol_ctx *c) {
     for (int k = 0; k < 3; ++k) c->surf[k] = pvol_ctx::SurfStore();
     c->dRad.reset(); c->nRad = 0;
     c->surfKept = false;
+    c->rad = RadianceResult();   // what pvol_compute_radiance made of them
 }
 
 extern "C" int pvol_surface_photon_count(pvol_ctx *c, int kind, uint32_t *n, uint32_t *nPaths) {

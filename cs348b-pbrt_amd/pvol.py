@@ -98,6 +98,15 @@ def lib():
         L.pvol_download_surface_photons.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_radiance_photon_count.argtypes = [C.c_void_p, _u32p]
         L.pvol_download_radiance_photons.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p, C.c_uint32]
+        L.pvol_compute_radiance.argtypes = [C.c_void_p, C.c_int32, C.c_float]
+        L.pvol_compute_radiance_arrays.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.POINTER(C.POINTER(abi.PhotonArray)), _f32p, _f32p, _f32p, _f32p,
+                                                   C.c_uint32]
+        L.pvol_radiance_lo_count.argtypes = [C.c_void_p, _u32p]
+        L.pvol_download_radiance_lo.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_uint32]
+        L.pvol_radiance_lookup.argtypes = [C.c_void_p, _f32p, _f32p, C.c_uint32, _f32p, _u32p]
+        L.pvol_radiance_lookup_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pvol_check_radiance.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int32, C.c_float, C.POINTER(C.POINTER(abi.PhotonArray)), _f32p, _f32p, _f32p,
+                                          _f32p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_march_kernel_name.restype = C.c_char_p
         L.pvol_tile_kernel_name.argtypes = [C.c_void_p]
@@ -148,7 +157,9 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_get_li_coalescing_stats", "pvol_preprocess_group", "pvol_render_frame_group",
            "pvol_film_window_from_crop", "pvol_film_sample_extent", "pvol_render_tasks_window_device",
            "pvol_film_add_samples_window_device", "pvol_film_resolve_window_device", "pvol_render_frame_ranks_window",
-           "pvol_render_frame_group_window", "pvol_tile_kernel_name", "pvol_set_triangle_normals"]
+           "pvol_render_frame_group_window", "pvol_tile_kernel_name", "pvol_set_triangle_normals",
+           "pvol_compute_radiance", "pvol_compute_radiance_arrays", "pvol_radiance_lo_count", "pvol_download_radiance_lo",
+           "pvol_radiance_lookup", "pvol_radiance_lookup_device"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -193,6 +204,26 @@ def render_frame_group(pvs, cam, film, smp, d_pixels, d_rgb, hip_streams=None, w
 def _check(rc, where):
     if rc != abi.PVOL_OK:
         raise PvolError(rc, where)
+
+
+def photon_arrays(maps):
+    """maps: three entries in the `kind` order (caustic, direct, indirect), each None or (p[n,3], wi[n,3], alpha[n,30], n_paths).
+    Returns (the pvol_photon_array *[3] for pvol_compute_radiance_arrays, what keeps its arrays alive)."""
+    if len(maps) != 3:
+        raise ValueError("three maps (caustic, direct, indirect), got %d" % len(maps))
+    ptrs = (C.POINTER(abi.PhotonArray) * 3)()
+    keep = []
+    for i, m in enumerate(maps):
+        if m is None:
+            continue
+        p, w, a = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in m[:3])
+        n = p.size // 3
+        if w.size != 3 * n or a.size != 30 * n:
+            raise ValueError("photon arrays disagree: %d positions, %d directions, %d weights" % (n, w.size // 3, a.size // 30))
+        pa = abi.PhotonArray(p.ctypes.data_as(_f32p), w.ctypes.data_as(_f32p), a.ctypes.data_as(_f32p), n, int(m[3]))
+        keep.append((pa, p, w, a))
+        ptrs[i] = C.pointer(pa)
+    return ptrs, keep
 
 
 class PhotonVolume:
@@ -315,6 +346,53 @@ class PhotonVolume:
         _check(lib().pvol_download_radiance_photons(self._h, p.ctypes.data_as(_f32p), nn.ctypes.data_as(_f32p), rr.ctypes.data_as(_f32p),
                                                     rt.ctypes.data_as(_f32p), n.value), "pvol_download_radiance_photons")
         return p, nn, rr, rt
+
+    def compute_radiance(self, n_lookup, max_dist, maps=None, radiance=None):
+        """ComputeRadianceTask on the device (photonshooter.cpp:359-395).  Without arguments: over the stores the last preprocess()
+        kept (pvol_compute_radiance).  Otherwise maps = [caustic, direct, indirect], each None or (p, wi, alpha, n_paths), and
+        radiance = (p[n,3], n[n,3], rho_r[n,30], rho_t[n,30]) (pvol_compute_radiance_arrays)."""
+        if maps is None and radiance is None:
+            _check(lib().pvol_compute_radiance(self._h, int(n_lookup), float(max_dist)), "pvol_compute_radiance")
+            return
+        if maps is None or radiance is None:
+            raise ValueError("compute_radiance: maps and radiance go together")
+        ptrs, keep = photon_arrays(maps)
+        p, nn, rr, rt = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in radiance)
+        n = p.size // 3
+        if nn.size != 3 * n or rr.size != 30 * n or rt.size != 30 * n:
+            raise ValueError("radiance photon arrays disagree on their count")
+        _check(lib().pvol_compute_radiance_arrays(self._h, int(n_lookup), float(max_dist), ptrs, p.ctypes.data_as(_f32p), nn.ctypes.data_as(_f32p),
+                                                  rr.ctypes.data_as(_f32p), rt.ctypes.data_as(_f32p), n), "pvol_compute_radiance_arrays")
+        del keep
+
+    def radiance_lo_count(self):
+        n = C.c_uint32()
+        _check(lib().pvol_radiance_lo_count(self._h, C.byref(n)), "pvol_radiance_lo_count")
+        return n.value
+
+    def radiance_lo(self):
+        """(p[n,3], n[n,3], lo[n,30]) of the last compute_radiance(), in input order."""
+        n = self.radiance_lo_count()
+        p, nn, lo = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 30), np.float32)
+        _check(lib().pvol_download_radiance_lo(self._h, p.ctypes.data_as(_f32p), nn.ctypes.data_as(_f32p), lo.ctypes.data_as(_f32p), n),
+               "pvol_download_radiance_lo")
+        return p, nn, lo
+
+    def radiance_lookup(self, p, n):
+        """The radiance map's nearest photon facing n at every point p (RadiancePhotonProcess): (lo[count,30], found[count])."""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1)
+        n = np.ascontiguousarray(n, np.float32).reshape(-1)
+        count = p.size // 3
+        if n.size != 3 * count:
+            raise ValueError("radiance_lookup: %d points, %d normals" % (count, n.size // 3))
+        lo, found = np.zeros((count, 30), np.float32), np.zeros(count, np.uint32)
+        _check(lib().pvol_radiance_lookup(self._h, p.ctypes.data_as(_f32p), n.ctypes.data_as(_f32p), count, lo.ctypes.data_as(_f32p),
+                                          found.ctypes.data_as(_u32p)), "pvol_radiance_lookup")
+        return lo, found
+
+    def radiance_lookup_device(self, d_p, d_n, count, d_lo, d_found, hip_stream=0):
+        """Device-pointer variant (integers): enqueue only, no synchronisation."""
+        _check(lib().pvol_radiance_lookup_device(self._h, d_p, d_n, count, d_lo, d_found, hip_stream), "pvol_radiance_lookup_device")
 
     def check_errors(self):
         """Raises PvolError(PVOL_E_LIMIT) if a batch enqueued through a device entry point hit a kernel limit."""

@@ -387,6 +387,42 @@ int pvol_download_surface_photons(pvol_ctx *ctx, int kind, float *p, float *wo, 
 int pvol_radiance_photon_count(pvol_ctx *ctx, uint32_t *n);
 int pvol_download_radiance_photons(pvol_ctx *ctx, float *p, float *n, float *rho_r, float *rho_t, uint32_t capacity);
 
+/* ---- radiance photons: the tail of PhotonShooter::Preprocess with `finalgather` (photonshooter.cpp:505-524) ----
+ * ComputeRadianceTask::Run (photonshooter.cpp:359-395) gives every radiance photon Lo = INV_PI rho_r E(n) + INV_PI rho_t E(-n), E the
+ * sum of three k-NN irradiance estimates EPhoton (:17-35; PhotonProcess, photonshooter.h:186-203; the visit test of
+ * core/kdtree.h:180) over the direct, indirect and caustic maps, and the photons become radianceMap, which the final gather asks for
+ * the nearest photon facing a point (RadiancePhotonProcess, photonshooter.h:63-78; integrators/photonmap.cpp:226-230).  Nothing
+ * else calls these: pvol_preprocess* does not compute radiance and pvol_set_surface_integrator still refuses an indirect map. */
+typedef struct pvol_photon_array {   /* host arrays: p, wi 3 floats, alpha 30 floats per photon */
+    const float *p, *wi, *alpha; uint32_t n; uint32_t n_paths;
+} pvol_photon_array;
+
+/* ComputeRadianceTask over the stores the last pvol_preprocess* kept (keep_surface_photons):
+   direct + indirect + caustic maps, the kept radiance photons, rho_r = Kd of the photon's matte material,
+   rho_t = 0 (as pvol_download_radiance_photons reports them).  n_lookup / max_dist are the SURFACE
+   integrator's "nused" / "maxdist" (CreatePhotonShooter, photonshooter.cpp:534,543).
+   PVOL_E_INVALID: NULL ctx, n_lookup < 1, max_dist not > 0 or not finite, no kept stores; PVOL_E_UNSUPPORTED: n_lookup > 576.
+   Zero radiance photons is PVOL_OK with count 0.  A rejected call changes nothing; a second compute replaces the first; every
+   new shoot drops the result. */
+int pvol_compute_radiance(pvol_ctx *ctx, int32_t n_lookup, float max_dist);
+
+/* The same from the caller's arrays (maps computed elsewhere, as pvol_upload_photons allows for the volume map).
+   maps[0] caustic, maps[1] direct, maps[2] indirect (the `kind` order of pvol_surface_photon_count);
+   a NULL entry or n == 0 is EPhoton's `if (!map) return 0`.  Needs no scene.  rp_p, rp_n: 3 floats, rho_r, rho_t: 30 floats per
+   radiance photon.  Also PVOL_E_INVALID: a NULL array with a count > 0, a map with n > 0 and n_paths == 0, a non-finite value. */
+int pvol_compute_radiance_arrays(pvol_ctx *ctx, int32_t n_lookup, float max_dist, const pvol_photon_array *const maps[3],
+                                 const float *rp_p, const float *rp_n, const float *rho_r, const float *rho_t, uint32_t n_rp);
+
+int pvol_radiance_lo_count(pvol_ctx *ctx, uint32_t *n);            /* 0 until one of the two above succeeded */
+int pvol_download_radiance_lo(pvol_ctx *ctx, float *p, float *n, float *lo, uint32_t capacity);  /* input order; lo 30 floats */
+
+/* radianceMap->Lookup(p, RadiancePhotonProcess(n), INFINITY): the nearest radiance photon with Dot(rp.n, n) > 0, no radius
+   limit.  lo: 30 floats per query (that photon's Lo; zeros when none), found: 1 / 0.  PVOL_E_INVALID before any compute.  The
+   device form takes DEVICE pointers and is enqueued on `hip_stream` without synchronising. */
+int pvol_radiance_lookup(pvol_ctx *ctx, const float *p, const float *n, uint32_t count, float *lo, uint32_t *found);
+int pvol_radiance_lookup_device(pvol_ctx *ctx, const float *d_p, const float *d_n, uint32_t count, float *d_lo,
+                                uint32_t *d_found, void *hip_stream);
+
 /* Number of photons in the current volume map. */
 int pvol_photon_count(pvol_ctx *ctx, uint32_t *n);
 /* Copies the current map back (same layout as pvol_upload_photons); capacity in photons. */
