@@ -38,13 +38,21 @@ __device__ __forceinline__ bool tri_closest_v(V3 p1, V3 p2, V3 p3, V3 o, V3 d, f
     return true;
 }
 
-// entry distance of the ray into a box, +inf when it misses [mint, maxt]; fminf/fmaxf drop the NaN of 0 * inf
+// entry distance of the ray into a box, +inf when it misses [mint, maxt]; fminf/fmaxf drop the NaN of 0 * inf.
+// The box's own interval is widened by 4 to 8 ulps of its ends before [mint, maxt] clips it: the build-time pad is a fixed length,
+// while the rounding of (lo - o) * inv grows with |o| -- from a few hundred scene diagonals out it exceeds the pad, and a box
+// would be left out whose triangle the scan hits.  +-inf and 0 keep their values.
+#define PVOL_BVH_SLAB_WIDEN 4.76837158203125e-7f   /* 2^-21 */
 __device__ __forceinline__ float bvh_slab(const float4 lo, const float4 hi, V3 o, V3 inv, float mint, float maxt) {
     const float ax = (lo.x - o.x) * inv.x, bx = (hi.x - o.x) * inv.x;
     const float ay = (lo.y - o.y) * inv.y, by = (hi.y - o.y) * inv.y;
     const float az = (lo.z - o.z) * inv.z, bz = (hi.z - o.z) * inv.z;
-    const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), mint));
-    const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), maxt));
+    float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+    float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+    tn *= 1.f - copysignf(PVOL_BVH_SLAB_WIDEN, tn);
+    tf *= 1.f + copysignf(PVOL_BVH_SLAB_WIDEN, tf);
+    tn = fmaxf(tn, mint);
+    tf = fminf(tf, maxt);
     return tn <= tf ? tn : INFINITY;
 }
 

@@ -1,4 +1,4 @@
-// pvol_host.h -- host-side internals shared by the host units (pvol_api.hip, pvol_scene_host.hip, pvol_map_host.hip, pvol_shoot_host.hip,
+// pvol_host.h -- host-side internals shared by the host units (pvol_api.hip, pvol_scene_host.hip, pvol_map_host.hip, pvol_shoot_host.hip, pvol_probe.hip,
 // pvol_render_host.hip)
 #ifndef PVOL_HOST_H
 #define PVOL_HOST_H
@@ -322,6 +322,11 @@ int pvol_check_exponential(const pvol_volume *v, float *up3);
 // radiance photons' p and n (1) or the queries' (2); hostPointers: a, b and the maps can be read (their values must be finite)
 int pvol_check_radiance(int what, int haveCtx, int haveState, int32_t nLookup, float maxDist, const pvol_photon_array *const *maps, const float *a,
                         const float *b, const float *rhoR, const float *rhoT, uint32_t count, const void *outLo, const void *outFound, int hostPointers);
+// the ray probe of the tests (pvol_probe.hip): n host rays through the device's own hit routines on the uploaded scene -- mode 0
+// surf_closest, 1 lane_occluded, 2 scene_occluded (one ray per wave); per ray out gets t, rayEps, p, nn, dpdu (11 floats) and outi the
+// hit flag, the primitive (triangle index in upload order, -1 - i for sphere i) and its material.  Synchronous; PVOL_E_INVALID for a
+// null pointer, no scene, n == 0 or an unknown mode
+int pvol_probe_hits(pvol_ctx *c, const pvol_ray *rays, uint32_t n, int mode, float *out, int32_t *outi);
 // the largest density of a checked exponential medium over its extent (feeds roulette_possible like a VolumeGrid's maximum); up3: the normalised updir
 float pvol_exponential_max_density(const pvol_volume *v, const float *up3);
 }

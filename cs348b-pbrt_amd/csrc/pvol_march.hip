@@ -673,20 +673,14 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
     return true;
 }
 
+#include "pvol_closest_dev.h"   // lane_occluded
+
 // ---- blocked march for the two ray-parallel modes over an analytic (homogeneous / rainbow) medium.
 // Everything about a march step that is SCALAR -- sample point, inside test, segment length, light
 // geometry, shadow-ray occlusion, exit distance of the shadow ray -- is evaluated for 64 steps at once,
 // one step per lane; the serial loop that follows only does the spectral arithmetic and the gather, reading
 // each step's scalars back with wave-uniform lane reads.  Returns 0 = done, 1 = the ray needs the roulette
 // (MODE_PAR: redo sequentially), 2 = not applicable (the caller runs march_ray).
-__device__ __forceinline__ bool lane_occluded(const DevScene &S, const RayD &vis) {
-    if (S.nSpheres && spheres_occluded(S, vis.o, vis.d, vis.mint, vis.maxt)) return true;
-    if (S.bvhNodes) return bvh_occluded(S, vis.o, vis.d, vis.mint, vis.maxt);
-    bool hit = false;
-    for (int t = 0; t < S.nTris && !hit; ++t) hit = tri_hit(S.tris[t], vis);
-    return hit;
-}
-
 template <bool STATS, int MODE, int NREG>
 __device__ int march_ray_blocked(const DevScene &S, const LiArgs &A, const pvol_ray &pr, Rng &rng, MarchLds &M, int lane,
                                  WaveCounters &wc, f4 *LvOut, f4 *TrOut, RayRec rec, TauRec *tauRec = nullptr) {

@@ -107,6 +107,7 @@ def lib():
         L.pvol_radiance_lookup_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pvol_check_radiance.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int32, C.c_float, C.POINTER(C.POINTER(abi.PhotonArray)), _f32p, _f32p, _f32p,
                                           _f32p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
+        L.pvol_probe_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _f32p, C.POINTER(C.c_int32)]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_march_kernel_name.restype = C.c_char_p
         L.pvol_tile_kernel_name.argtypes = [C.c_void_p]
@@ -327,6 +328,18 @@ class PhotonVolume:
         v = (C.c_double * 2)()
         _check(lib().pvol_get_accel_info(self._h, v), "pvol_get_accel_info")
         return int(v[0]), float(v[1])
+
+    def probe_hits(self, rays, mode):
+        """The tests' ray probe (csrc/pvol_probe.hip, not part of the ABI): rays (RAY_DTYPE) through the device's own hit routines on
+        the uploaded scene -- mode 0 surf_closest, 1 lane_occluded, 2 scene_occluded (one ray per wave).  Returns (f, i): f[n, 11] =
+        t, rayEps, p, nn, dpdu; i[n, 3] = hit flag, primitive (triangle index in upload order, -1 - k for sphere k), material."""
+        assert rays.dtype == abi.RAY_DTYPE
+        rays = np.ascontiguousarray(rays)
+        f = np.zeros((len(rays), 11), np.float32)
+        i = np.zeros((len(rays), 3), np.int32)
+        _check(lib().pvol_probe_hits(self._h, rays.ctypes.data, len(rays), mode, f.ctypes.data_as(_f32p), i.ctypes.data_as(C.POINTER(C.c_int32))),
+               "pvol_probe_hits")
+        return f, i
 
     def surface_photons(self, kind):
         """(p, wo, alpha, n_paths) of the caustic (0) / direct (1) / indirect (2) store kept by the last preprocess()."""

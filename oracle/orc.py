@@ -74,6 +74,8 @@ def lib():
         L.orc_light_sample.argtypes = [C.c_void_p, C.c_uint32, _f32p, _f32p]
         L.orc_intersect.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float, C.c_float, _f32p]
         L.orc_intersect_p.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float, C.c_float]
+        L.orc_hits_batch.argtypes = [C.c_void_p, _f32p, C.c_uint32, _f32p, C.POINTER(C.c_int32)]
+        L.orc_hits_batch.restype = None
         L.orc_bsdf_sample.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, C.c_float, C.c_float, C.c_float, _f32p, _f32p, _f32p]
         L.orc_volume_query.argtypes = [C.c_void_p, _f32p, _f32p]
         L.orc_rainbow.argtypes = [_f32p, _f32p, _f32p, _f32p]
@@ -197,6 +199,20 @@ class Oracle:
         p, nn, rr, rt = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 30), np.float32), np.zeros((n, 30), np.float32)
         lib().orc_get_radiance_photons(self._h, _p(p, _f32p), _p(nn, _f32p), _p(rr, _f32p), _p(rt, _f32p), n)
         return p, nn, rr, rt
+
+    def hits(self, o, d, mint, maxt):
+        """Scene::IntersectP and Scene::Intersect of n rays (orc_intersect_p / orc_intersect with the whole record) -> (f, i):
+        f[n, 14] = both flags, t, p, nn, dpdu, rayEpsilon; i[n, 2] = primitive (triangle index, -1 - k for sphere k), material."""
+        n = len(mint)
+        rays = np.empty((n, 8), np.float32)
+        rays[:, 0:3] = np.asarray(o, np.float32).reshape(n, 3)
+        rays[:, 3:6] = np.asarray(d, np.float32).reshape(n, 3)
+        rays[:, 6] = mint
+        rays[:, 7] = maxt
+        f = np.zeros((n, 14), np.float32)
+        i = np.zeros((n, 2), np.int32)
+        lib().orc_hits_batch(self._h, _p(rays, _f32p), n, _p(f, _f32p), _p(i, C.POINTER(C.c_int32)))
+        return f, i
 
     def shoot_stats(self):
         v = np.zeros(12, np.uint64)

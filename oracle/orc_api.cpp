@@ -298,6 +298,32 @@ int orc_intersect_p(orc_ctx *c, const float *o, const float *d, float mint, floa
     Ray r = make_ray(v3(o[0], o[1], o[2]), v3(d[0], d[1], d[2]), mint, maxt, 0.f);
     return scene_intersect_p(c->scene, r) ? 1 : 0;
 }
+// orc_intersect_p and orc_intersect for n rays at once, with the whole record: rays = o(3) d(3) mint maxt per ray; outf = the
+// IntersectP flag, the Intersect flag, t, p, nn, dpdu, rayEpsilon (14 floats, zero behind the flags on a miss); outi = the primitive
+// (triangle index, -1 - i for sphere i) and its material (0 0 on a miss)
+static void hits_range(const orc_ctx *c, const float *rays, uint32_t i0, uint32_t i1, float *outf, int32_t *outi) {
+    for (uint32_t i = i0; i < i1; ++i) {
+        const float *q = rays + 8 * (size_t)i;
+        float *f = outf + 14 * (size_t)i;
+        int32_t *k = outi + 2 * (size_t)i;
+        for (int j = 0; j < 14; ++j) f[j] = 0.f;
+        k[0] = k[1] = 0;
+        Ray r = make_ray(v3(q[0], q[1], q[2]), v3(q[3], q[4], q[5]), q[6], q[7], 0.f);
+        f[0] = scene_intersect_p(c->scene, r) ? 1.f : 0.f;
+        Hit h;
+        if (!scene_intersect(c->scene, &r, &h)) continue;
+        f[1] = 1.f; f[2] = h.t; f[3] = h.p.x; f[4] = h.p.y; f[5] = h.p.z; f[6] = h.nn.x; f[7] = h.nn.y; f[8] = h.nn.z;
+        f[9] = h.dpdu.x; f[10] = h.dpdu.y; f[11] = h.dpdu.z; f[12] = h.rayEpsilon;
+        k[0] = h.tri; k[1] = prim_material(c->scene, h.tri);
+    }
+}
+void orc_hits_batch(orc_ctx *c, const float *rays, uint32_t n, float *outf, int32_t *outi) {
+    const uint32_t nt = n >= 1024 ? 8 : 1;   // rays are independent
+    std::vector<std::thread> th;
+    for (uint32_t t = 1; t < nt; ++t) th.emplace_back(hits_range, c, rays, (uint32_t)((uint64_t)n * t / nt), (uint32_t)((uint64_t)n * (t + 1) / nt), outf, outi);
+    hits_range(c, rays, 0, (uint32_t)((uint64_t)n / nt), outf, outi);
+    for (size_t t = 0; t < th.size(); ++t) th[t].join();
+}
 // BSDF::Sample_f at a surface hit (see orc_shooter.h): out = wi(3) pdf flags f(30)
 int orc_bsdf_sample(orc_ctx *c, int tri, const float *wo, const float *alpha30, float u0, float u1, float ucomp,
                     const float *dpdu, const float *nn, float *out) {

@@ -781,16 +781,100 @@ static int cmdUnits(const std::string &name, const char *outPath) {
     }
     return out.save(outPath) ? 0 : 1;
 }
+// Scene::IntersectP / Scene::Intersect for chosen rays.  rays blob: rays.o rays.d [3n], rays.mint rays.maxt [n].  Per ray 14 floats --
+// the IntersectP flag, the Intersect flag, ray.maxt, dg.p, dg.nn, dg.dpdu, isect.rayEpsilon -- and 2 ints: the primitive hit (the
+// triangle's index in the order flatten() writes them, -1 - i for sphere i) and its material: "hit.f", "hit.i".
+// "scan.f", "scan.i": the same record from a loop over the scene's leaves in that order -- the triangles, then the spheres -- with
+// the reference's own GeometricPrimitive::Intersect / IntersectP and no hierarchy: the ray is shortened by every hit, so of two leaves
+// at the same t the later one stays.  "ties": how many leaves return the scan's t for this ray on their own (2 or more: an exact tie,
+// which the reference's tree decides by its order of visits).
+static void hitRecord(bool hitP, bool hit, const RayDifferential &ray, const Intersection &isect, std::map<const Primitive *, int> &primIndex,
+                      std::map<const Material *, int> &matIndex, float *f, int32_t *k) {
+    f[0] = hitP ? 1.f : 0.f; f[1] = hit ? 1.f : 0.f;
+    if (!hit) return;
+    f[2] = ray.maxt; f[3] = isect.dg.p.x; f[4] = isect.dg.p.y; f[5] = isect.dg.p.z;
+    f[6] = isect.dg.nn.x; f[7] = isect.dg.nn.y; f[8] = isect.dg.nn.z;
+    f[9] = isect.dg.dpdu.x; f[10] = isect.dg.dpdu.y; f[11] = isect.dg.dpdu.z;
+    f[12] = isect.rayEpsilon;
+    const GeometricPrimitive *gp = static_cast<const GeometricPrimitive *>(isect.primitive);
+    k[0] = primIndex.count(gp) ? primIndex[gp] : 0x7fffffff;
+    k[1] = matIndex.count(gp->material.GetPtr()) ? matIndex[gp->material.GetPtr()] : -1;
+}
+
+static int cmdHits(const std::string &name, const char *rayPath, const char *outPath) {
+    BuiltScene B;
+    memset(&B.nx, 0, sizeof(int) * 3);
+    if (!buildByName(B, name)) { fprintf(stderr, "unknown scene %s\n", name.c_str()); return 1; }
+    Blob rb;
+    if (!rb.load(rayPath)) { fprintf(stderr, "cannot read %s\n", rayPath); return 1; }
+    const size_t n = rb.get("rays.mint").count();
+    const float *ro = rb.get("rays.o").f32(), *rd = rb.get("rays.d").f32(), *rmin = rb.get("rays.mint").f32(), *rmax = rb.get("rays.maxt").f32();
+    std::vector<Reference<Primitive> > leaves, order;
+    const char *why = hipflat::collectLeaves(B.scene->aggregate, leaves);
+    if (why) { fprintf(stderr, "%s\n", why); return 3; }
+    std::stable_sort(leaves.begin(), leaves.end(), hipflat::ByShapeId());   // creation order: the order of flatten()'s lists
+    std::map<const Primitive *, int> primIndex;
+    int nt = 0, ns = 0;
+    for (int pass = 0; pass < 2; ++pass)   // the triangles, then the spheres
+        for (size_t i = 0; i < leaves.size(); ++i) {
+            const GeometricPrimitive *gp = static_cast<const GeometricPrimitive *>(leaves[i].GetPtr());
+            const bool sphere = dynamic_cast<const Sphere *>(gp->shape.GetPtr()) != NULL;
+            if (sphere != (pass == 1)) continue;
+            primIndex[gp] = sphere ? -1 - ns++ : nt++;
+            order.push_back(leaves[i]);
+        }
+    std::map<const Material *, int> matIndex;
+    for (size_t i = 0; i < B.matRefs.size(); ++i) matIndex[B.matRefs[i].GetPtr()] = (int)i;
+    std::vector<float> of(14 * n, 0.f), sf(14 * n, 0.f);
+    std::vector<int32_t> oi(2 * n, 0), si(2 * n, 0), ties(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const Point o(ro[3 * i], ro[3 * i + 1], ro[3 * i + 2]);
+        const Vector d(rd[3 * i], rd[3 * i + 1], rd[3 * i + 2]);
+        {
+            RayDifferential ray(o, d, rmin[i], rmax[i], 0.f);
+            Intersection isect;
+            const bool hitP = B.scene->IntersectP(ray);
+            const bool hit = B.scene->Intersect(ray, &isect);
+            hitRecord(hitP, hit, ray, isect, primIndex, matIndex, &of[14 * i], &oi[2 * i]);
+        }
+        RayDifferential ray(o, d, rmin[i], rmax[i], 0.f);
+        Intersection isect;
+        bool hitP = false, hit = false;
+        for (size_t k = 0; k < order.size(); ++k) {
+            if (order[k]->IntersectP(ray)) hitP = true;   // before this leaf shortens the ray: IntersectP sees the caller's maxt
+            ray.maxt = rmax[i];
+        }
+        for (size_t k = 0; k < order.size(); ++k) {
+            Intersection i2;
+            if (order[k]->Intersect(ray, &i2)) { isect = i2; hit = true; }
+        }
+        hitRecord(hitP, hit, ray, isect, primIndex, matIndex, &sf[14 * i], &si[2 * i]);
+        if (!hit) continue;
+        for (size_t k = 0; k < order.size(); ++k) {
+            RayDifferential r2(o, d, rmin[i], rmax[i], 0.f);
+            Intersection i2;
+            if (order[k]->Intersect(r2, &i2) && r2.maxt == ray.maxt) ++ties[i];
+        }
+    }
+    Blob out;
+    out.putf("hit.f", of);
+    out.put("hit.i", blob::I32, oi.data(), oi.size());
+    out.putf("scan.f", sf);
+    out.put("scan.i", blob::I32, si.data(), si.size());
+    out.put("ties", blob::I32, ties.data(), ties.size());
+    return out.save(outPath) ? 0 : 1;
+}
 
 int main(int argc, char **argv) {
     SampledSpectrum::Init();  // pbrtInit (core/api.cpp) does this
     if (argc >= 3 && !strcmp(argv[1], "tables")) return cmdTables(argv[2]);
     if (argc >= 4 && !strcmp(argv[1], "scene")) return cmdScene(argv[2], argv[3]);
     if (argc >= 4 && !strcmp(argv[1], "shimscene")) return cmdShimScene(argv[2], argv[3]);
+    if (argc >= 5 && !strcmp(argv[1], "hits")) return cmdHits(argv[2], argv[3], argv[4]);
     if (argc >= 4 && !strcmp(argv[1], "units")) return cmdUnits(argv[2], argv[3]);
     if (argc >= 5 && !strcmp(argv[1], "render")) return cmdRender(argv[2], argv[3], argv[4], argc - 5, argv + 5);
     if (argc >= 6 && !strcmp(argv[1], "li")) return cmdLi(argv[2], argv[3], argv[4], argv[5], argc - 6, argv + 6);
     fprintf(stderr,
-            "usage: ref_capture tables OUT | scene NAME OUT | shimscene NAME OUT | units NAME OUT | li NAME PHOTONS|- RAYS OUT [stepsize v] [nused v] [maxdist v]\n");
+            "usage: ref_capture tables OUT | scene NAME OUT | shimscene NAME OUT | units NAME OUT | hits NAME RAYS OUT | li NAME PHOTONS|- RAYS OUT [stepsize v] [nused v] [maxdist v]\n");
     return 64;
 }

@@ -143,37 +143,39 @@ static int addGlass(BuiltScene &B, float ior, float vn, const float kr[3], const
     return (int)B.mats.size() - 1;
 }
 
-static void addMesh(BuiltScene &B, const Transform &ctm, const float *P, int nverts, const int *idx, int nidx, int material) {
+static void addMesh(BuiltScene &B, const Transform &ctm, const float *P, int nverts, const int *idx, int nidx, int material,
+                    bool reverseOrientation = false) {
     ParamSet ps;
     std::vector<Point> pts(nverts);
     for (int i = 0; i < nverts; ++i) pts[i] = Point(P[3 * i], P[3 * i + 1], P[3 * i + 2]);
     ps.AddPoint("P", &pts[0], nverts);
     ps.AddInt("indices", idx, nidx);
     Transform *o2w = keep(ctm), *w2o = keep(Inverse(ctm));
-    TriangleMesh *mesh = CreateTriangleMeshShape(o2w, w2o, false, ps, NULL);
+    TriangleMesh *mesh = CreateTriangleMeshShape(o2w, w2o, reverseOrientation, ps, NULL);
     B.meshes.push_back(mesh);
     B.meshMaterial.push_back(material);
     Reference<Shape> shape(mesh);
     B.prims.push_back(new GeometricPrimitive(shape, B.matRefs[material], NULL));
 }
 
-static void addSphere(BuiltScene &B, const Transform &ctm, float radius, float zmin, float zmax, float phimax, int material) {
+static void addSphere(BuiltScene &B, const Transform &ctm, float radius, float zmin, float zmax, float phimax, int material,
+                      bool reverseOrientation = false) {
     ParamSet ps;
     ps.AddFloat("radius", &radius, 1);
     ps.AddFloat("zmin", &zmin, 1);
     ps.AddFloat("zmax", &zmax, 1);
     ps.AddFloat("phimax", &phimax, 1);
     Transform *o2w = keep(ctm), *w2o = keep(Inverse(ctm));
-    Sphere *sph = CreateSphereShape(o2w, w2o, false, ps);
+    Sphere *sph = CreateSphereShape(o2w, w2o, reverseOrientation, ps);
     B.spheres.push_back(sph);
     B.sphereMaterial.push_back(material);
     Reference<Shape> shape(sph);
     B.prims.push_back(new GeometricPrimitive(shape, B.matRefs[material], NULL));
 }
 
-static void addQuad(BuiltScene &B, const Transform &ctm, const float P[12], int material) {
+static void addQuad(BuiltScene &B, const Transform &ctm, const float P[12], int material, bool reverseOrientation = false) {
     static const int idx[6] = {0, 1, 2, 2, 3, 0};
-    addMesh(B, ctm, P, 4, idx, 6, material);
+    addMesh(B, ctm, P, 4, idx, 6, material, reverseOrientation);
 }
 
 static void finish(BuiltScene &B) {
@@ -385,6 +387,98 @@ static void buildSphereScene(BuiltScene &B, bool extra) {
     finish(B);
 }
 
+// ---- the hit zoos (tests/test_hit_records.py, tests/test_gpu_hit_probe.py): scenes made to be probed ray by ray where
+// Sphere::Intersect and Triangle::Intersect branch.  A small homogeneous medium and one point light keep them shootable and renderable.
+static void zooCommon(BuiltScene &B, const float p0[3], const float p1[3], const float lightAt[3], float I) {
+    B.stepSize = .25f; B.nUsed = 50; B.maxDist = 0.5f; B.nVolumePhotons = 2000;
+    B.shooterStep = 0.25f; B.maxPhotonDepth = 5; B.nCaustic = 0; B.nIndirect = 0; B.finalGather = 0;
+    B.xres = 32; B.yres = 20; B.spp = 2; B.fov = 70.f;
+    B.volume = makeVolume(B, Transform(), "homogeneous", p0, p1, .05f, .1f);
+    addPoint(B, Transform(), lightAt, I);
+}
+
+// Eight spheres (the ABI's limit; the ten properties asked of them are shared out), three matte walls, one triangle tangent to the
+// unit sphere at its +z pole.  Spheres 0 and 1 are concentric at the origin under the identity: rays along z reach the unit sphere
+// through the caps cut out of sphere 1, and every intermediate of such a ray is exact.
+static void buildSphereZoo(BuiltScene &B) {
+    const float p0[3] = {-9, -7, -9}, p1[3] = {9, 9, 9}, lightAt[3] = {3, 7, -4};
+    zooCommon(B, p0, p1, lightAt, 200.f);
+    B.camToWorld = Translate(Vector(0, 0, -14));
+    int m[8];
+    for (int i = 0; i < 7; ++i) m[i] = addMatte(B, .3f + .1f * i, .8f - .1f * i, .5f);
+    addSphere(B, Transform(), 1.f, -1.f, 1.f, 360.f, m[0]);                                           // 0 full, identity
+    addSphere(B, Transform(), 2.f, -1.f, 1.f, 360.f, m[1]);                                           // 1 clipped in z, identity
+    addSphere(B, Translate(Vector(5, 0, 0)), 1.f, -1.f, 1.f, 180.f, m[2]);                            // 2 phimax 180
+    addSphere(B, Translate(Vector(-5, 0, 0)), 1.f, -1.f, 1.f, 270.f, m[3], true);                     // 3 phimax 270, ReverseOrientation
+    addSphere(B, Translate(Vector(0, 5, 0)) * Scale(-1, 1, 1), 1.5f, -.5f, 1.f, 270.f, m[4]);         // 4 z and phi, mirrored (TransformSwapsHandedness)
+    addSphere(B, Translate(Vector(0, -4, 0)) * Scale(1, -1, 1), 1.f, -1.f, .5f, 360.f, m[5], true);   // 5 mirrored and reversed: the flips cancel
+    addSphere(B, Translate(Vector(100, 0, 0)), 1e-3f, -1e-3f, 1e-3f, 360.f, m[6]);                    // 6 radius 1e-3, 100 units out: C = o.o - r^2 cancels
+    addSphere(B, Translate(Vector(0, 0, 6)) * Rotate(30, Vector(1, 1, 0)) * Scale(1.f, 0.7f, 1.2f), 1.f, -.6f, .8f, 300.f, m[6]);   // 7 rotation + non-uniform scale
+    const float floorQ[12] = {-12, -8, -12, 12, -8, -12, 12, -8, 12, -12, -8, 12};
+    const float backQ[12] = {-12, -8, 10, 12, -8, 10, 12, 10, 10, -12, 10, 10};
+    const float sideQ[12] = {-12, -8, 10, -12, -8, -12, -12, 10, -12, -12, 10, 10};
+    const int wall = addMatte(B, .6f, .6f, .6f);
+    addQuad(B, Transform(), floorQ, wall);
+    addQuad(B, Transform(), backQ, wall);
+    addQuad(B, Transform(), sideQ, wall);
+    const float tangent[9] = {-.25f, -.25f, 1, .25f, -.25f, 1, 0, .25f, 1};   // touches sphere 0 at (0, 0, 1): an exact tie in t
+    const int one[3] = {0, 1, 2};
+    addMesh(B, Transform(), tangent, 3, one, 3, wall);
+    finish(B);
+}
+
+// 55 triangles (the linear scan on the device); `filler` adds 16 small far-away ones behind them, in the same order, so that the
+// device builds its hierarchy over the very same triangles.
+static void buildTriZoo(BuiltScene &B, bool filler) {
+    const float p0[3] = {-6, -4, -3}, p1[3] = {10, 8, 8}, lightAt[3] = {2, 2, 1.5f};   // between the grid and the pair: most photons meet a surface
+    zooCommon(B, p0, p1, lightAt, 100.f);
+    B.camToWorld = Translate(Vector(2, 2, 9)) * Scale(1, 1, -1);
+    int m[7];
+    for (int i = 0; i < 7; ++i) m[i] = addMatte(B, .2f + .1f * i, .5f, .9f - .1f * i);
+    {   // 4 x 4 quads on integer vertices in the plane z = 0: shared edges, shared vertices, exact arithmetic
+        float P[75];
+        int idx[96], k = 0;
+        for (int j = 0; j <= 4; ++j) for (int i = 0; i <= 4; ++i) { P[3 * (5 * j + i)] = (float)i; P[3 * (5 * j + i) + 1] = (float)j; P[3 * (5 * j + i) + 2] = 0.f; }
+        for (int j = 0; j < 4; ++j) for (int i = 0; i < 4; ++i) {
+            const int a = 5 * j + i, b = a + 1, c = a + 6, d = a + 5;
+            idx[k++] = a; idx[k++] = b; idx[k++] = c; idx[k++] = a; idx[k++] = c; idx[k++] = d;
+        }
+        addMesh(B, Transform(), P, 25, idx, 96, m[0]);
+    }
+    const int one[3] = {0, 1, 2};
+    const float pairA[9] = {0, 0, 2, 2, 0, 2, 0, 2, 2}, pairB[9] = {0, 0, 2, 0, 2, 2, 2, 0, 2};   // coincident, the second reversed
+    addMesh(B, Transform(), pairA, 3, one, 3, m[1]);
+    addMesh(B, Transform(), pairB, 3, one, 3, m[1]);
+    {   // a sliver, a collinear triangle, a point, a repeated vertex
+        const float P[36] = {5, 0, 0, 9, 0, 0, 7, 1e-4f, 0,   5, 2, 0, 6, 2, 0, 7, 2, 0,   5, 3, 0, 5, 3, 0, 5, 3, 0,   5, 4, 0, 5, 4, 0, 7, 4, 1};
+        const int idx[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+        addMesh(B, Transform(), P, 12, idx, 12, m[2]);
+    }
+    {   // an axis-aligned thin plate
+        const float z0 = 1.f, z1 = 1.001f;
+        const float P[24] = {-3, 0, z0, -1, 0, z0, -1, 2, z0, -3, 2, z0, -3, 0, z1, -1, 0, z1, -1, 2, z1, -3, 2, z1};
+        const int idx[36] = {0, 1, 2, 2, 3, 0, 4, 6, 5, 6, 4, 7, 0, 4, 5, 5, 1, 0, 1, 5, 6, 6, 2, 1, 2, 6, 7, 7, 3, 2, 3, 7, 4, 4, 0, 3};
+        addMesh(B, Transform(), P, 8, idx, 36, m[3]);
+    }
+    const float revQ[12] = {0, -1, 0, 4, -1, 0, 4, -1, 3, 0, -1, 3};
+    addQuad(B, Transform(), revQ, m[4], true);                         // ReverseOrientation
+    const float mirQ[12] = {5, 0, .5f, 7, 0, .5f, 7, 2, .5f, 5, 2, .5f};
+    addQuad(B, Scale(-1, 1, 1), mirQ, m[5]);                           // a mirroring transform
+    const float tiny[9] = {2.5f, 2.5f, 1, 2.501f, 2.5f, 1, 2.5f, 2.501f, 1};
+    addMesh(B, Transform(), tiny, 3, one, 3, m[6]);
+    if (filler) {
+        float P[16 * 9];
+        int idx[16 * 3];
+        for (int k = 0; k < 16; ++k) {
+            const float x = 60.f + k, f[9] = {x, 60, 60, x + .01f, 60, 60, x, 60.01f, 60};
+            memcpy(P + 9 * k, f, sizeof(f));
+            idx[3 * k] = 3 * k; idx[3 * k + 1] = 3 * k + 1; idx[3 * k + 2] = 3 * k + 2;
+        }
+        addMesh(B, Transform(), P, 48, idx, 48, m[0]);
+    }
+    finish(B);
+}
+
 static bool buildByName(BuiltScene &B, const std::string &name) {
     if (name == "volumescene_h") buildVolumeScene(B, "homogeneous", 0);
     else if (name == "volumescene_hg") buildVolumeScene(B, "homogeneous", 0, 0.6f);   // anisotropic phase function (row a16)
@@ -397,6 +491,9 @@ static bool buildByName(BuiltScene &B, const std::string &name) {
     else if (name == "spherescene") buildSphereScene(B, false);
     else if (name == "sphereroom") buildSphereScene(B, true);
     else if (name == "meshroom_big") buildMeshRoom(B, 256, 128);
+    else if (name == "spherezoo") buildSphereZoo(B);
+    else if (name == "trizoo") buildTriZoo(B, false);
+    else if (name == "trizoo_h") buildTriZoo(B, true);
     else return false;
     return true;
 }
