@@ -281,7 +281,7 @@ class SurfaceParams(C.Structure):   # pvol_surface_params
                 ("reserved", C.c_uint32 * 1)]
 
 
-class PhotonArray(C.Structure):   # pvol_photon_array: one surface map handed to pvol_compute_radiance_arrays
+class PhotonArray(C.Structure):   # pvol_photon_array: one surface map handed to pvol_compute_radiance_arrays / pvol_set_surface_integrator_maps
     _fields_ = [("p", C.POINTER(C.c_float)), ("wi", C.POINTER(C.c_float)), ("alpha", C.POINTER(C.c_float)), ("n", C.c_uint32), ("n_paths", C.c_uint32)]
 
 

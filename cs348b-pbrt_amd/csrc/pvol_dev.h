@@ -49,17 +49,25 @@ struct DevTri {
     float p1[3], p2[3], p3[3];
 };
 
-// PhotonIntegrator (integrators/photonmap.cpp), matte subset: parameters + the caustic photon map (same grid layout as the
-// volume map; alpha rows are the photons' raw weights, divided by nCausticPaths at lookup as photonmap.cpp:89 does)
-struct DevSurface {
-    int32_t enabled, nLookup, maxSpecularDepth, nCausticPaths;
-    float maxDistSq;
+// One photon map LPhoton reads (photonmap.cpp:62-108): same grid layout as the volume map; alpha rows are the photons' raw
+// weights, divided by nPaths (nCausticPaths / nIndirectPaths) at lookup as photonmap.cpp:89 does.  nPhotons 0: no such map.
+struct DevSurfMap {
     uint32_t nPhotons;
+    int32_t nPaths;
     float gridLo[3];
     float cellSize, invCell;
     int32_t gdim[3];
     const uint32_t *cellStart;
     const float4 *pos4, *alpha4, *wi4;
+};
+#define SURF_MAP_CAUSTIC 0
+#define SURF_MAP_INDIRECT 1
+// PhotonIntegrator (integrators/photonmap.cpp), matte subset: parameters + the two maps of its LPhoton calls (:179-180 caustic,
+// :307-309 indirect without the final gather)
+struct DevSurface {
+    int32_t enabled, nLookup, maxSpecularDepth;
+    float maxDistSq;
+    DevSurfMap map[2];
 };
 struct DevShootScene;
 

@@ -206,6 +206,8 @@ struct pvol_ctx {
     RadianceResult rad;    // pvol_compute_radiance*: dropped by every shoot and by pvol_free_surface_stores
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     PhotonGrid causticMap;
+    // ... and its indirect map (pvol_set_surface_integrator_maps: LPhoton(indirectMap) without the final gather), built by the same builder
+    PhotonGrid indirectMap;
     // specular recursion of the surface integrator (pvol_spec_dev.h): segments of the camera samples that meet glass
     bool specOn = false;            // the scene holds a specular material and the surface integrator is on
     pvol_stream hSegStream = {};    // the segment pool seen as one stream of a ray batch (host copy of PVOL_BUF_SEG_STREAM)
@@ -294,7 +296,7 @@ void pvol_phase_mark(pvol_ctx *c, hipStream_t stream, int id);
 int pvol_finish_map(pvol_ctx *c, uint32_t n, const float *hostPositions);
 void pvol_free_photons(pvol_ctx *c);          // empties the volume map, in the context and in its host scene
 void pvol_free_surface_stores(pvol_ctx *c);
-void pvol_free_caustic_map(pvol_ctx *c);      // empties the caustic map and switches the surface integrator off
+void pvol_free_caustic_map(pvol_ctx *c);      // empties the caustic and the indirect map and switches the surface integrator off
 int pvol_push_scene(pvol_ctx *c);
 // pvol_li without the coalescer (pvol_api.hip) and through it (pvol_li_coalesce.hip); arguments already validated
 int pvol_li_lone(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T);
@@ -322,6 +324,11 @@ int pvol_check_exponential(const pvol_volume *v, float *up3);
 // radiance photons' p and n (1) or the queries' (2); hostPointers: a, b and the maps can be read (their values must be finite)
 int pvol_check_radiance(int what, int haveCtx, int haveState, int32_t nLookup, float maxDist, const pvol_photon_array *const *maps, const float *a,
                         const float *b, const float *rhoR, const float *rhoT, uint32_t count, const void *outLo, const void *outFound, int hostPointers);
+// every status of pvol_set_surface_integrator_maps in its one order, reachable without a device for the tests (pvol_map_host.hip).
+// materials: 0 the scene's surfaces are matte, 1 glass among them, 2 a kind the surface integrator does not cover; storesKept and
+// storeN / storePaths ([0] caustic, [1] indirect): what the last pvol_preprocess* kept; hostPointers: the arrays can be read
+int pvol_check_surface_maps(const pvol_surface_params *sp, int haveScene, int materials, int storesKept, const uint32_t *storeN,
+                            const uint32_t *storePaths, const pvol_photon_array *caustic, const pvol_photon_array *indirect, int hostPointers);
 // the ray probe of the tests (pvol_probe.hip): n host rays through the device's own hit routines on the uploaded scene -- mode 0
 // surf_closest, 1 lane_occluded, 2 scene_occluded (one ray per wave); per ray out gets t, rayEps, p, nn, dpdu (11 floats) and outi the
 // hit flag, the primitive (triangle index in upload order, -1 - i for sphere i) and its material.  Synchronous; PVOL_E_INVALID for a

@@ -59,10 +59,40 @@ void pvol_map_to_scene(const PhotonGrid &G, DevScene &h) {
     for (int a = 0; a < 3; ++a) { h.gridLo[a] = G.gridLo[a]; h.gdim[a] = G.gdim[a]; }
     h.cellStart = G.cellStart.get(); h.subStart = G.subStart.get(); h.pos4 = G.pos4.get(); h.alpha4 = G.alpha4.get(); h.wi4 = G.wi4.get();
 }
-static void map_to_surface(const PhotonGrid &G, DevSurface &sf) {
-    sf.nPhotons = G.n; sf.cellSize = G.cellSize; sf.invCell = G.invCell;
+static void map_to_surface(const PhotonGrid &G, uint32_t nPaths, DevSurfMap &sf) {
+    sf.nPhotons = G.n; sf.nPaths = (int32_t)nPaths; sf.cellSize = G.cellSize; sf.invCell = G.invCell;
     for (int a = 0; a < 3; ++a) { sf.gridLo[a] = G.gridLo[a]; sf.gdim[a] = G.gdim[a]; }
     sf.cellStart = G.cellStart.get(); sf.pos4 = G.pos4.get(); sf.alpha4 = G.alpha4.get(); sf.wi4 = G.wi4.get();
+}
+
+// A map of the surface integrator from its raw device arrays: cells of maxdist / 2 (a lookup gathers everything within maxdist,
+// never fewer), no Inside() filter -- surface photons count wherever they lie
+static int build_surface_grid(PhotonGrid &G, const float *const raw[3], const float *hostP, uint32_t n, float maxDist) {
+    MapFilter all;
+    memset(&all, 0, sizeof(all));
+    all.volKind = PVOL_VOLUME_GRID;
+    const double first = 0.5 * maxDist;
+    return build_photon_grid(G, raw, hostP, n, 1e-3 * maxDist, [first](double) { return first; }, all);
+}
+
+static bool all_finite(const float *v, size_t n) {
+    for (size_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false;
+    return true;
+}
+// materials: what the scene's surfaces allow -- 0 matte only, 1 glass among them, 2 a kind the surface integrator does not cover
+static int scene_materials(const pvol_ctx *c) {
+    int m = 0;
+    for (size_t i = 0; i < c->triMatHost.size(); ++i) {
+        const int kind = c->hsh.mats[c->triMatHost[i]].kind;
+        if (kind == PVOL_MATERIAL_GLASS) m = std::max(m, 1);
+        else if (kind != PVOL_MATERIAL_MATTE) return 2;
+    }
+    for (int i = 0; i < c->hs.nSpheres; ++i) {
+        const int kind = c->hsh.mats[c->hs.spheres[i].mat].kind;
+        if (kind == PVOL_MATERIAL_GLASS) m = std::max(m, 1);
+        else if (kind != PVOL_MATERIAL_MATTE) return 2;
+    }
+    return m;
 }
 
 extern "C" {
@@ -75,6 +105,7 @@ void pvol_free_photons(pvol_ctx *c) {
 
 void pvol_free_caustic_map(pvol_ctx *c) {
     c->causticMap = PhotonGrid();
+    c->indirectMap = PhotonGrid();
     memset(&c->hs.surf, 0, sizeof(c->hs.surf));
     c->specOn = false;
 }
@@ -154,22 +185,14 @@ int pvol_set_surface_integrator(pvol_ctx *c, const pvol_surface_params *sp, cons
     if (sp->n_used < 1 || !(sp->max_dist > 0.f) || sp->max_specular_depth < 0) return PVOL_E_INVALID;
     // matte and glass: a specular BSDF brings the recursion of SpecularReflect / SpecularTransmit (core/integrator.cpp:177-262,
     // pvol_spec_dev.h), walked for "maxspeculardepth" up to SPEC_MAX_DEPTH (the reference's default)
-    bool anySpecular = false;
-    for (size_t i = 0; i < c->triMatHost.size(); ++i) {
-        const int kind = c->hsh.mats[c->triMatHost[i]].kind;
-        if (kind == PVOL_MATERIAL_GLASS) anySpecular = true;
-        else if (kind != PVOL_MATERIAL_MATTE) return PVOL_E_UNSUPPORTED;
-    }
-    for (int i = 0; i < c->hs.nSpheres; ++i) {
-        const int kind = c->hsh.mats[c->hs.spheres[i].mat].kind;
-        if (kind == PVOL_MATERIAL_GLASS) anySpecular = true;
-        else if (kind != PVOL_MATERIAL_MATTE) return PVOL_E_UNSUPPORTED;
-    }
+    const int materials = scene_materials(c);
+    if (materials == 2) return PVOL_E_UNSUPPORTED;
+    const bool anySpecular = materials == 1;
     if (anySpecular && sp->max_specular_depth > SPEC_MAX_DEPTH) return PVOL_E_UNSUPPORTED;
     // an indirect map makes PhotonIntegrator::Li gather: the final gather, or LPhoton(indirectMap) with 144 more rho draws
-    // (photonmap.cpp:183-309).  None of that radiance and none of those draws exist here yet, so such an integrator is
-    // refused by name rather than rendered wrong -- whether the map is the caller's (n_indirect_photons) or the store of
-    // the last pvol_preprocess.
+    // (photonmap.cpp:183-309).  This entry point takes the caustic map alone, so such an integrator is refused by name rather
+    // than rendered wrong -- whether the map is the caller's (n_indirect_photons) or the store of the last pvol_preprocess;
+    // pvol_set_surface_integrator_maps takes both maps (without the final gather).
     if (sp->n_indirect_photons > 0) return PVOL_E_UNSUPPORTED;
     if (sp->use_preprocess_store) {
         if (!c->surfKept) return PVOL_E_INVALID;   // nothing was kept: params.keep_surface_photons was 0, or no pvol_preprocess yet
@@ -200,18 +223,100 @@ int pvol_set_surface_integrator(pvol_ctx *c, const pvol_surface_params *sp, cons
     hipDeviceSynchronize();
     pvol_free_caustic_map(c);
     if (n) {
-        MapFilter all;   // no Inside() filter: surface photons count wherever they lie
-        memset(&all, 0, sizeof(all));
-        all.volKind = PVOL_VOLUME_GRID;
-        const double first = 0.5 * sp->max_dist;
-        int rc = build_photon_grid(c->causticMap, raw, p, n, 1e-3 * sp->max_dist, [first](double) { return first; }, all);
+        int rc = build_surface_grid(c->causticMap, raw, p, n, sp->max_dist);
         if (rc != PVOL_OK) { pvol_free_caustic_map(c); pvol_push_scene(c); return rc; }
     }
     DevSurface &sf = c->hs.surf;
-    sf.enabled = 1; sf.nLookup = sp->n_used; sf.maxSpecularDepth = sp->max_specular_depth; sf.nCausticPaths = (int32_t)nPaths;
+    sf.enabled = 1; sf.nLookup = sp->n_used; sf.maxSpecularDepth = sp->max_specular_depth;
     c->specOn = anySpecular && sp->max_specular_depth > 1;
     sf.maxDistSq = sp->max_dist * sp->max_dist;   // photonmap.cpp:345-346
-    map_to_surface(c->causticMap, sf);
+    map_to_surface(c->causticMap, nPaths, sf.map[SURF_MAP_CAUSTIC]);
+    return pvol_push_scene(c);
+}
+
+// Every status of pvol_set_surface_integrator_maps (include/pvol.h) in its one order, a pure function of its arguments: no context, no
+// HIP call.  materials: scene_materials() above; storesKept, storeN / storePaths [0] caustic [1] indirect: what the last
+// pvol_preprocess* kept; hostPointers: the arrays can be read (their values must be finite).
+int pvol_check_surface_maps(const pvol_surface_params *sp, int haveScene, int materials, int storesKept, const uint32_t *storeN,
+                            const uint32_t *storePaths, const pvol_photon_array *caustic, const pvol_photon_array *indirect, int hostPointers) {
+    if (!sp) return PVOL_E_INVALID;
+    if (sp->n_used < 1 || !(sp->max_dist > 0.f) || sp->max_specular_depth < 0) return PVOL_E_INVALID;
+    if (materials == 2) return PVOL_E_UNSUPPORTED;
+    if (materials == 1 && sp->max_specular_depth > SPEC_MAX_DEPTH) return PVOL_E_UNSUPPORTED;
+    if (!haveScene) return PVOL_E_NO_SCENE;
+    uint32_t nIndirect = 0;
+    if (sp->use_preprocess_store) {
+        if (caustic || indirect || !storesKept || !storeN || !storePaths) return PVOL_E_INVALID;
+        for (int m = 0; m < 2; ++m) if (storeN[m] > 0 && storePaths[m] == 0) return PVOL_E_INVALID;
+        nIndirect = storeN[1];
+    } else {
+        const pvol_photon_array *maps[2] = {caustic, indirect};
+        for (int m = 0; m < 2; ++m) {
+            const pvol_photon_array *M = maps[m];
+            if (!M || !M->n) continue;
+            if (!M->p || !M->wi || !M->alpha || !M->n_paths) return PVOL_E_INVALID;
+            if (hostPointers && (!all_finite(M->p, 3 * (size_t)M->n) || !all_finite(M->wi, 3 * (size_t)M->n) || !all_finite(M->alpha, 30 * (size_t)M->n)))
+                return PVOL_E_INVALID;
+        }
+        nIndirect = indirect ? indirect->n : 0u;
+    }
+    // LPhoton(indirectMap) is the branch WITHOUT the final gather (photonmap.cpp:183, :307-309); the gather itself is not built
+    if (sp->final_gather != 0 && nIndirect > 0) return PVOL_E_UNSUPPORTED;
+    return PVOL_OK;
+}
+
+// PhotonIntegrator with both maps of its LPhoton calls (include/pvol.h).  Both grids are built aside and committed last: a
+// rejected call leaves the integrator as it was.
+int pvol_set_surface_integrator_maps(pvol_ctx *c, const pvol_surface_params *sp, const pvol_photon_array *caustic, const pvol_photon_array *indirect) {
+    if (!c) return PVOL_E_INVALID;
+    std::lock_guard<std::recursive_mutex> api(c->apiMu);
+    const uint32_t storeN[2] = {c->surf[0].n, c->surf[2].n}, storePaths[2] = {c->surf[0].nPaths, c->surf[2].nPaths};
+    int rc = pvol_check_surface_maps(sp, c->haveScene, scene_materials(c), c->surfKept, storeN, storePaths, caustic, indirect, 1);
+    if (rc != PVOL_OK) return rc;
+    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
+    const pvol_photon_array *arrays[2] = {caustic, indirect};
+    const int storeKind[2] = {0, 2};
+    PhotonGrid grid[2];
+    uint32_t nPaths[2] = {0, 0};
+    for (int m = 0; m < 2; ++m) {
+        std::vector<float> hp;
+        const float *raw[3] = {0, 0, 0}, *hostP = 0;
+        DevPtr<float> up[3];
+        uint32_t n = 0;
+        if (sp->use_preprocess_store) {   // device to device; the positions come back once for the grid bounds
+            const pvol_ctx::SurfStore &st = c->surf[storeKind[m]];
+            n = st.n; nPaths[m] = st.nPaths;
+            raw[0] = st.p.get(); raw[1] = st.wo.get(); raw[2] = st.alpha.get();
+            hp.resize(3 * (size_t)n);
+            if (n && !ok(hipMemcpy(hp.data(), raw[0], sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
+            hostP = hp.data();
+        } else if (arrays[m] && arrays[m]->n) {
+            n = arrays[m]->n; nPaths[m] = arrays[m]->n_paths;
+            const size_t width[3] = {3, 3, 30};
+            const float *src[3] = {arrays[m]->p, arrays[m]->wi, arrays[m]->alpha};
+            for (int i = 0; i < 3; ++i) {
+                if (!up[i].alloc(width[i] * (size_t)n)) return PVOL_E_NO_MEMORY;
+                if (!ok(hipMemcpy(up[i].get(), src[i], sizeof(float) * width[i] * (size_t)n, hipMemcpyHostToDevice))) return PVOL_E_NO_DEVICE;
+                raw[i] = up[i].get();
+            }
+            hostP = arrays[m]->p;
+        }
+        if (!n) continue;
+        rc = build_surface_grid(grid[m], raw, hostP, n, sp->max_dist);
+        if (rc != PVOL_OK) return rc;
+        if (!ok(hipDeviceSynchronize())) return PVOL_E_NO_DEVICE;   // the build has read `up` and the stores
+    }
+    hipDeviceSynchronize();   // an earlier batch may still read the maps replaced here
+    const int materials = scene_materials(c);
+    c->causticMap = std::move(grid[0]);
+    c->indirectMap = std::move(grid[1]);
+    DevSurface &sf = c->hs.surf;
+    memset(&sf, 0, sizeof(sf));
+    sf.enabled = 1; sf.nLookup = sp->n_used; sf.maxSpecularDepth = sp->max_specular_depth;
+    c->specOn = materials == 1 && sp->max_specular_depth > 1;
+    sf.maxDistSq = sp->max_dist * sp->max_dist;   // photonmap.cpp:345-346
+    map_to_surface(c->causticMap, nPaths[0], sf.map[SURF_MAP_CAUSTIC]);
+    map_to_surface(c->indirectMap, nPaths[1], sf.map[SURF_MAP_INDIRECT]);
     return pvol_push_scene(c);
 }
 

@@ -2,6 +2,7 @@
 // photonmap.cpp:154-319) that the BASELINE scenes' camera rays need on their matte walls:
 //   L = UniformSampleAllLights (core/integrator.cpp:47-79 -> EstimateDirect :117-174, delta lights)
 //     + LPhoton(causticMap)     (photonmap.cpp:62-108, diffuse branch: kernel-weighted k-NN estimate)
+//     + LPhoton(indirectMap)    (photonmap.cpp:307-309: the same routine over the indirect map, when there is one and no final gather)
 // (`indirectphotons 0` in both scenes leaves the final gather and the indirect estimate without a map), plus every RNG
 // draw of the rest of that Li(): 2 x 72 of BSDF::rho inside LPhoton, 2 x 3 of the BSDFSample(rng) that SpecularReflect /
 // SpecularTransmit construct, one per unoccluded light sample (visibility.Transmittance(..., NULL, rng)).  None of the drawn
@@ -9,7 +10,7 @@
 // (they precede the sample's volume Li() in the task's stream) and the radiance is added by surface_kernel afterwards:
 //   sample = T * Lsurface + Lvi        (SamplerRenderer::Li, renderers/samplerrenderer.cpp:238-250)
 // Not covered (the host refuses such scenes when the surface integrator is on): specular BSDFs (the recursion of
-// SpecularReflect/Transmit), an indirect map / final gather, VolumeGrid media (the shadow-ray tau() offset is a drawn value).
+// SpecularReflect/Transmit), the final gather over an indirect map, VolumeGrid media (the shadow-ray tau() offset is a drawn value).
 #include "pvol_closest_dev.h"   // SurfHit, surf_closest, lane_occluded
 #define SRF_AIM 1.6f    // the search ball is re-aimed at this multiple of nused photons for the sparsest sample of a cluster
 #define SRF_CAP 1024   // caustic bucket capacity (photons within the search ball + spread of a group's hit points).  Measured on the C2 frame with the
@@ -64,7 +65,8 @@ __device__ uint32_t surf_count_draws(const DevScene &S, const SurfHit &h, V3 d, 
         const V3 ng = surf_ng(S, h);
         for (int ln = 0; ln < S.nLights; ++ln) n += surf_light(S, ln, h.p, h.rayEps, ng, wo, lambert, blackMask).take ? 1u : 0u;
     }
-    if (S.surf.nPhotons > 0u && lambert) n += 144u;     // LPhoton(causticMap): two BSDF::rho(wo, rng)
+    if (S.surf.map[SURF_MAP_CAUSTIC].nPhotons > 0u && lambert) n += 144u;    // LPhoton(causticMap): two BSDF::rho(wo, rng)
+    if (S.surf.map[SURF_MAP_INDIRECT].nPhotons > 0u && lambert) n += 144u;   // LPhoton(indirectMap), photonmap.cpp:307-309: the same again
     if (depth + 1 < S.surf.maxSpecularDepth) n += 6u;   // SpecularReflect + SpecularTransmit: BSDFSample(rng) each
     return n;
 }
@@ -76,8 +78,7 @@ __device__ __forceinline__ V3 lane_v3(V3 v, int l) { return v3(lane_f(v.x, l), l
 // smallest distance^2 by bisection over the fp32 bit pattern (one pass per step, as the bucket form does over LDS); then the flux
 // sum over the members (ties at the nused-th distance in photon order).  Every lane returns the wave's sums in acc[0..29]:
 // Lr = sum kernel / (nPaths r^2) alpha over the members on the wo side (photonmap.cpp:62-108).
-__device__ __attribute__((noinline)) void caustic_stream(const DevScene &S, const GridView &cg, V3 P, V3 Nf, int k, int lane, float *acc) {
-    const float maxD2 = S.surf.maxDistSq;
+__device__ __attribute__((noinline)) void caustic_stream(const DevSurfMap &M, float maxD2, const GridView &cg, V3 P, V3 Nf, int k, int lane, float *acc) {
     const GridRows R = grid_rows<false>(cg, P, sqrtf(maxD2), 0);
     // pass 0: count inside; pass 1..: bisection steps; each pass visits every photon of the rows once
     uint32_t lo = 0u, hi = __float_as_uint(maxD2), kth = 0xffffffffu;
@@ -128,7 +129,7 @@ __device__ __attribute__((noinline)) void caustic_stream(const DevScene &S, cons
     float a[32];
 #pragma unroll
     for (int b = 0; b < 32; ++b) a[b] = 0.f;
-    const float norm = 1.f / ((float)S.surf.nCausticPaths * r2);
+    const float norm = 1.f / ((float)M.nPaths * r2);
     int tiesSeen = 0;
     for (int r = 0; r < R.nrows; ++r) {
         uint32_t start, rlen;
@@ -151,11 +152,11 @@ __device__ __attribute__((noinline)) void caustic_stream(const DevScene &S, cons
             }
             tiesSeen += __popcll(tb);
             if (mem) {
-                const f4 wi4 = S.surf.wi4[start + i];
+                const f4 wi4 = M.wi4[start + i];
                 if (Nf.x * wi4.x + Nf.y * wi4.y + Nf.z * wi4.z > 0.f) {
                     const float sW = 1.f - d2 / r2;
                     const float wgt = (3.f * 0.31830988618379067154f * sW * sW) * norm;
-                    const float4 *row = S.surf.alpha4 + (size_t)(start + i) * 8;
+                    const float4 *row = M.alpha4 + (size_t)(start + i) * 8;
 #pragma unroll
                     for (int qq = 0; qq < 8; ++qq) {
                         const float4 rr = row[qq];
@@ -188,15 +189,12 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
     const float *bX = bucket, *bY = bucket + PITCH, *bZ = bucket + 2 * PITCH, *bI = bucket + 3 * PITCH;
     unsigned blackMask = 0u;
     { const int q = lane & 7; for (int l = 0; l < S.nLights; ++l) if (spec_is_black(ld4(S.lights[l].intensity, q))) blackMask |= 1u << l; }
-    GridView cg;
-    cg.cellSize = S.surf.cellSize; cg.invCell = S.surf.invCell;
-    for (int i = 0; i < 3; ++i) { cg.gridLo[i] = S.surf.gridLo[i]; cg.gdim[i] = S.surf.gdim[i]; }
-    cg.cellStart = S.surf.cellStart; cg.subStart = 0; cg.pos4 = S.surf.pos4;
     const int k = S.surf.nLookup;
     // groups of 64 samples in runs of sixteen (four 256-spp pixels) per wave: the search radius that served one group is the first
     // guess for the next (the caustic density changes slowly along a wall)
-    const float maxDist = sqrtf(S.surf.maxDistSq);
-    float Rtry = maxDist;   // wave-uniform
+    const float maxDistSq = S.surf.maxDistSq;
+    const float maxDist = sqrtf(maxDistSq);
+    float RtryMap[2] = {maxDist, maxDist};   // wave-uniform, one per map: the two differ in density
     const unsigned long long nGroups = (A.nRays + LANES - 1) / LANES;
     for (unsigned long long gi = (unsigned long long)blockIdx.x * 16ull; gi < nGroups; gi = ((gi & 15ull) == 15ull) ? gi + 1ull + ((unsigned long long)gridDim.x - 1ull) * 16ull : gi + 1ull) {
         const unsigned long long g0 = gi * LANES;
@@ -235,11 +233,20 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                 }
             }
         }
-        // ---- caustic estimate (photonmap.cpp:62-108), shared buckets: the samples still waiting are served cluster by cluster
+        // ---- LPhoton (photonmap.cpp:62-108) over the caustic map, then over the indirect one (:179-180, :307-309): the same estimate
+        // with the map's own photons and path count; the hit and the direct term above serve both.  Shared buckets: the samples still waiting are served cluster by cluster
         // -- all of them at once when they lie within maxdist of their common centre (one pixel's samples on one wall), else
         // those within maxdist of the first waiting sample's hit point, and that sample alone if even this bucket overflows.
-        const bool needAny = lambert && S.surf.nPhotons > 0u;
-        unsigned long long pending = __ballot(needAny);
+#pragma unroll 1
+        for (int mi = 0; mi < 2; ++mi) {   // wave-uniform
+        const DevSurfMap &M = S.surf.map[mi];
+        if (M.nPhotons == 0u) continue;
+        GridView cg;
+        cg.cellSize = M.cellSize; cg.invCell = M.invCell;
+        for (int i = 0; i < 3; ++i) { cg.gridLo[i] = M.gridLo[i]; cg.gdim[i] = M.gdim[i]; }
+        cg.cellStart = M.cellStart; cg.subStart = 0; cg.pos4 = M.pos4;
+        float Rtry = mi ? RtryMap[1] : RtryMap[0];
+        unsigned long long pending = __ballot(lambert);
         bool alone = false;
         // Where more photons lie within maxdist of the samples than the bucket holds (a caustic's focus; the beam's footprint on a wall),
         // the nused nearest lie far inside maxdist: the cluster is then searched with a SMALLER radius -- halved area per overflow,
@@ -280,13 +287,13 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                 else Rtry = Rlo > 0.f ? sqrtf(Rlo * Rhi) : 0.70710678f * Rq;
                 continue;
             }
-            const float T2 = (alone || !(Rq < maxDist)) ? S.surf.maxDistSq : Rq * Rq;   // the searched ball's radius^2
+            const float T2 = (alone || !(Rq < maxDist)) ? maxDistSq : Rq * Rq;   // the searched ball's radius^2
             const bool wasAlone = alone;
             alone = false;
             if (Mb < 0) {   // more photons within maxdist of ONE point than the bucket holds: streamed from the grid for that point
                 pending &= ~__ballot(need);
                 float sa[32];
-                caustic_stream(S, cg, c, dot(lane_v3(h.nn, pivLane), lane_v3(wo, pivLane)) < 0.f ? lane_v3(h.nn, pivLane) * -1.f : lane_v3(h.nn, pivLane), k, lane, sa);
+                caustic_stream(M, maxDistSq, cg, c, dot(lane_v3(h.nn, pivLane), lane_v3(wo, pivLane)) < 0.f ? lane_v3(h.nn, pivLane) * -1.f : lane_v3(h.nn, pivLane), k, lane, sa);
                 if (need) {
 #pragma unroll
                     for (int b = 0; b < 30; ++b) Ls[b] += sa[b] * mat.kd[b] * 0.31830988618379067154f;
@@ -394,7 +401,7 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                     }
                 }
                 // a sample is served when its nused nearest lie inside the searched ball, or the ball is the full one
-                const bool served = need && (nIn >= k || !(T2 < S.surf.maxDistSq));
+                const bool served = need && (nIn >= k || !(T2 < maxDistSq));
                 pending &= ~__ballot(served);
                 if (!wasAlone) {
                     // photons on a surface: the count grows with the radius squared.  The next ball aims at 1.6 nused photons for the
@@ -412,7 +419,7 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                 }
                 // pass B: Lr = sum over members on the wo side of  kernel / (nPaths r^2) * alpha   (the -wo side carries rho_t == 0)
                 const V3 Nf = dot(h.nn, wo) < 0.f ? h.nn * -1.f : h.nn;
-                const float norm = 1.f / ((float)S.surf.nCausticPaths * r2);
+                const float norm = 1.f / ((float)M.nPaths * r2);
                 // acc[sample][bin] += weight[sample][photon] * alpha[photon][bin] on the matrix pipe (v_mfma_f32_32x32x2_f32 is bit for
                 // bit the fmaf chain the per-lane loop made, bucket order kept): A = two flux rows (lane l: bin l & 31 of the photon of
                 // its half-wave, one coalesced 128-B row per half-wave), B = the two photons' weights for sample l & 31 -- ONE
@@ -425,8 +432,8 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                 const int half = lane >> 5, binL = lane & 31;
                 typedef const __attribute__((address_space(1))) float gfloat;
                 typedef const __attribute__((address_space(1))) nf4 gfloat4;
-                gfloat *alphaF = (gfloat *)(S.surf.alpha4);
-                gfloat4 *wiG = (gfloat4 *)(S.surf.wi4);
+                gfloat *alphaF = (gfloat *)(M.alpha4);
+                gfloat4 *wiG = (gfloat4 *)(M.wi4);
                 for (int i0 = 0; i0 < Mb; i0 += 8) {   // four photon pairs per trip: their rows are requested before the first is used
                     float av[4], w0[4], w1[4];
 #pragma unroll
@@ -478,6 +485,8 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                 for (int b = 0; b < 30; ++b) Ls[b] += acc[b] * mat.kd[b] * 0.31830988618379067154f;   // Lr * rho(wo) * INV_PI, rho == Kd
             }
         }
+        if (mi) RtryMap[1] = Rtry; else RtryMap[0] = Rtry;
+        }   // the next map
         // ---- compose: sample = T * Lsurface + Lvi
         if (hit && A.spectral) {   // a segment of the specular recursion: its T is in the record, the sum stays spectral
             float *op = A.out + ri * 60;

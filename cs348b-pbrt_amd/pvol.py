@@ -109,6 +109,9 @@ def lib():
                                           _f32p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
         L.pvol_probe_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _f32p, C.POINTER(C.c_int32)]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
+        L.pvol_set_surface_integrator_maps.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), C.POINTER(abi.PhotonArray), C.POINTER(abi.PhotonArray)]
+        L.pvol_check_surface_maps.argtypes = [C.POINTER(abi.SurfaceParams), C.c_int, C.c_int, C.c_int, _u32p, _u32p, C.POINTER(abi.PhotonArray),
+                                              C.POINTER(abi.PhotonArray), C.c_int]
         L.pvol_march_kernel_name.restype = C.c_char_p
         L.pvol_tile_kernel_name.argtypes = [C.c_void_p]
         L.pvol_tile_kernel_name.restype = C.c_char_p
@@ -160,7 +163,7 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_film_add_samples_window_device", "pvol_film_resolve_window_device", "pvol_render_frame_ranks_window",
            "pvol_render_frame_group_window", "pvol_tile_kernel_name", "pvol_set_triangle_normals",
            "pvol_compute_radiance", "pvol_compute_radiance_arrays", "pvol_radiance_lo_count", "pvol_download_radiance_lo",
-           "pvol_radiance_lookup", "pvol_radiance_lookup_device"]
+           "pvol_radiance_lookup", "pvol_radiance_lookup_device", "pvol_set_surface_integrator_maps"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -205,6 +208,17 @@ def render_frame_group(pvs, cam, film, smp, d_pixels, d_rgb, hip_streams=None, w
 def _check(rc, where):
     if rc != abi.PVOL_OK:
         raise PvolError(rc, where)
+
+
+def photon_array(m):
+    """One map (p[n,3], wi[n,3], alpha[n,30], n_paths) as (a pvol_photon_array, what keeps its arrays alive); None stays None."""
+    if m is None:
+        return None, None
+    p, w, a = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in m[:3])
+    n = p.size // 3
+    if w.size != 3 * n or a.size != 30 * n:
+        raise ValueError("photon arrays disagree: %d positions, %d directions, %d weights" % (n, w.size // 3, a.size // 30))
+    return abi.PhotonArray(p.ctypes.data_as(_f32p), w.ctypes.data_as(_f32p), a.ctypes.data_as(_f32p), n, int(m[3])), (p, w, a)
 
 
 def photon_arrays(maps):
@@ -500,6 +514,21 @@ class PhotonVolume:
         assert w.size == 3 * n and a.size == 30 * n
         _check(lib().pvol_set_surface_integrator(self._h, C.byref(sp), p.ctypes.data_as(_f32p), w.ctypes.data_as(_f32p), a.ctypes.data_as(_f32p), n),
                "pvol_set_surface_integrator")
+
+    def set_surface_integrator_maps(self, n_used=50, max_dist=0.1, max_specular_depth=5, final_gather=False, caustic=None, indirect=None,
+                                    from_preprocess=False):
+        """PhotonIntegrator with both maps of its LPhoton calls (pvol_set_surface_integrator_maps): the caustic estimate and,
+        without the final gather, the same estimate over the indirect map.  Each map is None or (p[n,3], wi[n,3], alpha[n,30],
+        n_paths); from_preprocess=True takes the caustic and the indirect store the last preprocess() kept instead.
+        final_gather=True with a non-empty indirect map raises PVOL_E_UNSUPPORTED: the final gather is not built."""
+        sp = abi.SurfaceParams()
+        sp.n_used, sp.max_dist, sp.max_specular_depth, sp.final_gather = int(n_used), float(max_dist), int(max_specular_depth), int(bool(final_gather))
+        sp.use_preprocess_store = int(bool(from_preprocess))
+        ca, keep_c = photon_array(caustic)
+        ia, keep_i = photon_array(indirect)
+        _check(lib().pvol_set_surface_integrator_maps(self._h, C.byref(sp), C.byref(ca) if ca is not None else None,
+                                                      C.byref(ia) if ia is not None else None), "pvol_set_surface_integrator_maps")
+        del keep_c, keep_i
 
     def film_add_samples(self, film, d_image_xy, d_xyz, stride, n, d_pixels, hip_stream=0, window=None):
         if window is not None:

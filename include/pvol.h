@@ -255,8 +255,9 @@ typedef struct pvol_render_debug {   /* optional DEVICE buffers that receive the
 
 /* Surface integrator in front of the volume term: PhotonIntegrator::Li
  * (integrators/photonmap.cpp:154-319) for camera rays that end on MATTE surfaces, without an indirect
- * map (`indirectphotons 0`, both BASELINE scenes): UniformSampleAllLights over delta lights
- * (core/integrator.cpp:47-79, :117-174), the caustic estimate LPhoton (photonmap.cpp:62-108) and the
+ * map (`indirectphotons 0`, both BASELINE scenes) or with one and `finalgather false`
+ * (pvol_set_surface_integrator_maps): UniformSampleAllLights over delta lights
+ * (core/integrator.cpp:47-79, :117-174), the estimate LPhoton (photonmap.cpp:62-108) over each map and the
  * RNG traffic of the rest of that Li() (2 x BSDF::rho, 2 x BSDFSample, one draw per unoccluded light). */
 typedef struct pvol_surface_params {
     int32_t n_used;              /* "nused" (photonmap.cpp:340), lookup size of the caustic estimate */
@@ -267,7 +268,9 @@ typedef struct pvol_surface_params {
     int32_t use_preprocess_store;/* 1: take the caustic photons (and path count) the last pvol_preprocess kept
                                     (params.keep_surface_photons) instead of the arrays passed        */
     uint32_t n_indirect_photons; /* photons in the integrator's INDIRECT map (0 with `indirectphotons 0`, both BASELINE
-                                    scenes).  > 0 makes Li() gather (photonmap.cpp:183-309): PVOL_E_UNSUPPORTED            */
+                                    scenes).  > 0 makes Li() gather (photonmap.cpp:183-309): pvol_set_surface_integrator,
+                                    which takes the caustic map alone, answers PVOL_E_UNSUPPORTED.
+                                    pvol_set_surface_integrator_maps takes the indirect map itself and does not read this */
     uint32_t reserved[1];
 } pvol_surface_params;
 
@@ -392,7 +395,8 @@ int pvol_download_radiance_photons(pvol_ctx *ctx, float *p, float *n, float *rho
  * sum of three k-NN irradiance estimates EPhoton (:17-35; PhotonProcess, photonshooter.h:186-203; the visit test of
  * core/kdtree.h:180) over the direct, indirect and caustic maps, and the photons become radianceMap, which the final gather asks for
  * the nearest photon facing a point (RadiancePhotonProcess, photonshooter.h:63-78; integrators/photonmap.cpp:226-230).  Nothing
- * else calls these: pvol_preprocess* does not compute radiance and pvol_set_surface_integrator still refuses an indirect map. */
+ * else calls these: pvol_preprocess* does not compute radiance and the final gather that would ask radianceMap is not built
+ * (pvol_set_surface_integrator_maps refuses `finalgather` with an indirect map). */
 typedef struct pvol_photon_array {   /* host arrays: p, wi 3 floats, alpha 30 floats per photon */
     const float *p, *wi, *alpha; uint32_t n; uint32_t n_paths;
 } pvol_photon_array;
@@ -548,9 +552,25 @@ int pvol_render_tasks_device(pvol_ctx *ctx, const pvol_camera *camera, const pvo
  * indirect photons) (here); a VolumeGrid medium, whose T is a product of stepped taus with drawn offsets, or glass in a
  * medium dense enough for the roulette (from pvol_render_tasks_device).  PVOL_E_INVALID:
  * use_preprocess_store without a pvol_preprocess that ran with params.keep_surface_photons.  pvol_set_scene disables the
- * surface integrator again. */
+ * surface integrator again.  This entry point describes an integrator WITHOUT an indirect map: it drops one that
+ * pvol_set_surface_integrator_maps set, whether it enables or disables. */
 int pvol_set_surface_integrator(pvol_ctx *ctx, const pvol_surface_params *sp, const float *p, const float *wo,
                                 const float *alpha, uint32_t n);
+
+/* PhotonIntegrator with both maps LPhoton reads (photonmap.cpp:179-180, :307-309): the caustic estimate and, WITHOUT the final
+ * gather, the same estimate over the indirect map with nIndirectPaths in its norm and 2 x 72 more BSDF::rho draws per
+ * Lambertian hit.  pvol_photon_array::wi is Photon::wi (the `wo` of pvol_set_surface_integrator).  A NULL array or n == 0:
+ * no such map (LPhoton's `if (map && ...)`).  sp->use_preprocess_store = 1: both arrays must be NULL; the caustic map is store 0
+ * and the indirect map store 2 of the last pvol_preprocess*, each with its own path count, copied device to device.
+ * sp->n_caustic_paths and sp->n_indirect_photons are not read: the arrays or stores carry them.
+ * Statuses, the first that applies: PVOL_E_INVALID a NULL ctx or sp, n_used < 1, max_dist not > 0, max_specular_depth < 0;
+ * PVOL_E_UNSUPPORTED a material other than matte or glass, maxspeculardepth > 5 with glass; PVOL_E_NO_SCENE;
+ * PVOL_E_INVALID an array with n > 0 and a NULL pointer or n_paths == 0, a non-finite value, use_preprocess_store together
+ * with an array or without kept stores; PVOL_E_UNSUPPORTED sp->final_gather != 0 with a non-empty indirect map (the final
+ * gather, photonmap.cpp:183-306, is not built).  With an empty indirect map final_gather changes nothing and the call equals
+ * pvol_set_surface_integrator.  A rejected call changes nothing; a successful one replaces both maps; pvol_set_scene drops them. */
+int pvol_set_surface_integrator_maps(pvol_ctx *ctx, const pvol_surface_params *sp, const pvol_photon_array *caustic,
+                                     const pvol_photon_array *indirect);
 
 /* ---- multi-GPU frame (north_star: pixel tiles partitioned over the GPUs of a node, one RCCL reduce of the film) ----
  * Rank `rank` of `n_ranks` renders the tasks rank, rank + n_ranks, ... of SamplerRenderer::Render's task loop

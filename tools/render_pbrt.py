@@ -12,7 +12,8 @@ window's size, info["window"] says where it lies; the sampler then covers the wi
 random streams are those of the reference's crop render, not a cut-out of the full frame's.  The surface integrator (direct lighting +
 caustic estimate on matte surfaces) is switched on when the scene asks for "photonmap" and the device path
 covers it (matte and glass surfaces -- the specular recursion included --, a homogeneous or rainbow medium at any nused and
-phase function, or no medium; no indirect map); otherwise (a VolumeGrid or exponential medium, an indirect map) Ls = 0 and the image holds the
+phase function, or no medium; an indirect map only with `finalgather false`, where it adds its own LPhoton estimate); otherwise (a
+VolumeGrid or exponential medium, the final gather over an indirect map) Ls = 0 and the image holds the
 volume term alone -- the tool says which.  info["render_s"]: wall seconds of the frame's render_tasks (shoot excluded)."""
 import argparse
 import importlib
@@ -27,7 +28,7 @@ sys.path.insert(0, ROOT)
 
 
 def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_tasks=2048, surface=True, log=print, caustic_photons=None,
-                      devices=None, cropwindow=None, phases=False):
+                      devices=None, cropwindow=None, phases=False, indirect_photons=None):
     """cropwindow: (x0, x1, y0, y1) overrides the file's; None keeps it (the whole frame when the file names none).
     phases: info["phase_ms"] gets the first context's device milliseconds per phase of the frame (tile pre-pass, march + gather,
     surface, film) from HIP events, which serialise the phases a little: not for the frame's own timing.
@@ -47,6 +48,8 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
         over["n_volume_photons"] = int(photons)
     if caustic_photons is not None:
         over["n_caustic_photons"] = int(caustic_photons)
+    if indirect_photons is not None:
+        over["n_indirect_photons"] = int(indirect_photons)
     params = abi.params_from_blob(scene, **over)
     group = devices is not None
     if group:
@@ -72,13 +75,19 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
             else:
                 pv.preprocess(shoot_tasks)
         st = pv.shoot_stats()
-        log("photon map: %d volume, %d caustic photons from %d paths" % (st["stored_volume"], st["stored_caustic"], st["paths"]))
+        log("photon map: %d volume, %d caustic, %d indirect photons from %d paths" % (st["stored_volume"], st["stored_caustic"], st["stored_indirect"],
+                                                                                        st["paths"]))
         used_surface = False
         if surface and scene["surf.name"] == "photonmap":
+            # `finalgather false` with indirect photons: LPhoton over both stores (set_surface_integrator_maps).  Everything else takes
+            # the caustic-only entry point, which refuses an indirect map by name -- `finalgather true` with one is the final gather
+            final_gather = bool(scene["surf.params.i"][2])
+            both_maps = not final_gather and st["stored_indirect"] > 0
             try:
                 for q in pvs:
-                    q.set_surface_integrator(int(scene["surf.params.i"][0]), float(scene["surf.params.f"][0]), int(scene["surf.params.i"][1]),
-                                             bool(scene["surf.params.i"][2]), from_preprocess=True)
+                    setter = q.set_surface_integrator_maps if both_maps else q.set_surface_integrator
+                    setter(int(scene["surf.params.i"][0]), float(scene["surf.params.f"][0]), int(scene["surf.params.i"][1]), final_gather,
+                           from_preprocess=True)
                 used_surface = True
             except pvol.PvolError as e:
                 log("surface integrator not applied (%s): the image holds the volume term only" % e)
@@ -134,7 +143,7 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
         for q in pvs:
             q.check_errors()
         info = {"xres": xres, "yres": yres, "spp": spp, "surface_integrator": used_surface, "kernel": pv.march_kernel_name(),
-                "photons": int(st["stored_volume"]), "caustic_photons": int(st["stored_caustic"]), "render_s": render_s}
+                "photons": int(st["stored_volume"]), "caustic_photons": int(st["stored_caustic"]), "indirect_photons": int(st["stored_indirect"]), "render_s": render_s}
         if group:
             info["devices"] = devices
         if phases:
