@@ -150,6 +150,16 @@ struct PVOL_LOCAL RadianceResult {
     PhotonGrid map;
 };
 
+// What pvol_build_gather_map* leaves (pvol_gather.hip): the indirect map as the reference's kd-tree, node by node
+// (GatherNode, pvol_gather_tree.h: two float4 a node), and the photons' Photon::wi in the store's order.
+struct PVOL_LOCAL GatherMap {
+    bool have = false;
+    uint32_t n = 0;
+    int depth = 0;             // nodes on the longest root-to-leaf path: bounds the lookup's stack
+    DevPtr<float4> nodes4;     // [n][2]
+    DevPtr<float> wi;          // [n][3]
+};
+
 struct pvol_ctx {
     pvol_params params = {};
     bool haveScene = false;
@@ -204,6 +214,7 @@ struct pvol_ctx {
     DevPtr<float> dRad;    // radiance photons: [n][8] = p(3) n(3) material index, pad
     uint32_t nRad = 0;
     RadianceResult rad;    // pvol_compute_radiance*: dropped by every shoot and by pvol_free_surface_stores
+    GatherMap gather;      // pvol_build_gather_map*: dropped wherever `rad` is
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     PhotonGrid causticMap;
     // ... and its indirect map (pvol_set_surface_integrator_maps: LPhoton(indirectMap) without the final gather), built by the same builder
@@ -307,6 +318,21 @@ int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream);
 void *pvol_rccl_symbol(const char *name);
 // plan_size(plan_path(in)) for the tests; like pvol_rccl_symbol not part of include/pvol.h
 void pvol_plan_batch(const PlanIn *in, BatchPlan *out);
+// the gather map's kd-tree (gather_tree_build, pvol_gather_tree.h) over n host positions p[n][3], for the tests (pvol_gather.hip):
+// nodes gets n GatherNode (32 bytes each), *depth the tree's depth.  No HIP call.  PVOL_E_INVALID: a NULL pointer or a non-finite
+// position; PVOL_E_UNSUPPORTED: n == 0 or n > 2^24
+int pvol_gather_tree_build(const float *p, uint32_t n, void *nodes, int32_t *depth);
+// every status of the gather entry points in their one order (include/pvol.h), reachable without a device for the tests
+// (pvol_gather.hip).  what: 0 pvol_build_gather_map, 1 pvol_build_gather_map_arrays, 2 pvol_gather_photons*, 3 pvol_gather_directions*;
+// haveState: the stores are kept (0) / a map is built (2, 3); storeN: photons of the kept indirect store (0); args: the call's
+// pointers as GatherCheck lists them; hostPointers: the arrays can be read
+struct GatherCheck {
+    const pvol_photon_array *indirect;                         // what 1
+    const float *p; uint32_t count; float maxDist;             // what 2, 3
+    const void *outIndex, *outD2, *outFound, *outRounds;       // what 2
+    const float *frames, *wo, *uBsdf, *uPhoton; int32_t nSamples; float cosGatherAngle; const void *outBsdf, *outPhoton;   // what 3
+};
+int pvol_check_gather(int what, int haveCtx, int haveState, uint32_t storeN, const GatherCheck *args, int hostPointers);
 // the shoot's merge (ShootMerge, pvol_shoot_merge.h) replayed over recorded count tables, for the tests (pvol_shoot_host.hip)
 size_t pvol_shoot_merge_replay(const uint32_t *cfg, const uint32_t *tables, uint32_t nTables, uint64_t *out, size_t cap);
 // the plan of a render call (RenderPlan below) flattened for the tests (pvol_render_host.hip)

@@ -49,6 +49,7 @@ extern "C" void pvol_free_surface_stores(pvol_ctx *c) {
     c->dRad.reset(); c->nRad = 0;
     c->surfKept = false;
     c->rad = RadianceResult();   // what pvol_compute_radiance made of them
+    c->gather = GatherMap();     // ... and pvol_build_gather_map
 }
 
 extern "C" int pvol_surface_photon_count(pvol_ctx *c, int kind, uint32_t *n, uint32_t *nPaths) {

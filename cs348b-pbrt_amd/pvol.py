@@ -31,6 +31,40 @@ class ShootComm(C.Structure):
     _fields_ = [("nccl_comm", C.c_void_p), ("allgather", ALLGATHER_FN), ("user", C.c_void_p)]
 
 
+# ---- final gather, sampling half (include/pvol.h: pvol_gather_*)
+GATHER_K = 50   # nIndirSamplePhotons (integrators/photonmap.cpp:190)
+# pvol_gather_sample
+GATHER_SAMPLE_DTYPE = np.dtype([("wi", "<f4", 3), ("weight", "<f4"), ("bsdf_pdf", "<f4"), ("photon_pdf", "<f4"), ("photon_index", "<u4"), ("valid", "<u4")])
+# GatherNode (csrc/pvol_gather_tree.h), what the test hook pvol_gather_tree_build fills
+GATHER_NODE_DTYPE = np.dtype([("p", "<f4", 3), ("split_pos", "<f4"), ("split_axis", "<u4"), ("has_left_child", "<u4"), ("right_child", "<u4"),
+                              ("index", "<u4")])
+assert GATHER_SAMPLE_DTYPE.itemsize == 32 and GATHER_NODE_DTYPE.itemsize == 32
+
+
+class GatherCheck(C.Structure):   # the arguments pvol_check_gather judges (csrc/pvol_host.h)
+    _fields_ = [("indirect", C.POINTER(abi.PhotonArray)), ("p", _f32p), ("count", C.c_uint32), ("max_dist", C.c_float),
+                ("out_index", C.c_void_p), ("out_d2", C.c_void_p), ("out_found", C.c_void_p), ("out_rounds", C.c_void_p),
+                ("frames", _f32p), ("wo", _f32p), ("u_bsdf", _f32p), ("u_photon", _f32p), ("n_samples", C.c_int32), ("cos_gather_angle", C.c_float),
+                ("out_bsdf", C.c_void_p), ("out_photon", C.c_void_p)]
+
+
+def gather_cos_angle(gather_angle):
+    """PhotonShooter's cosGatherAngle for a "gatherangle" in degrees (core/photonshooter.cpp:413): Radians() in fp32, cos in double,
+    the result stored as a float."""
+    rad = np.float32(np.float32(np.float32(3.14159265358979323846) / np.float32(180.0)) * np.float32(gather_angle))
+    return float(np.float32(np.cos(np.float64(rad))))
+
+
+def gather_tree(p):
+    """The gather map's kd-tree over p[n,3] as the host builds it (pvol_gather_tree_build; no GPU): (nodes, depth), nodes a
+    GATHER_NODE_DTYPE array in the reference's node numbering."""
+    p = np.ascontiguousarray(p, np.float32).reshape(-1)
+    n = p.size // 3
+    nodes, depth = np.zeros(n, GATHER_NODE_DTYPE), C.c_int32()
+    _check(lib().pvol_gather_tree_build(p.ctypes.data_as(_f32p), n, nodes.ctypes.data, C.byref(depth)), "pvol_gather_tree_build")
+    return nodes, depth.value
+
+
 def gloo_allgather(group=None):
     """A host all-gather for PhotonVolume.preprocess_ranks over torch.distributed (gloo: CPU tensors): bytes -> list of bytes,
     one entry per rank in rank order."""
@@ -107,7 +141,18 @@ def lib():
         L.pvol_radiance_lookup_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pvol_check_radiance.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int32, C.c_float, C.POINTER(C.POINTER(abi.PhotonArray)), _f32p, _f32p, _f32p,
                                           _f32p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
-        L.pvol_probe_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _f32p, C.POINTER(C.c_int32)]
+        L.pvol_build_gather_map.argtypes = [C.c_void_p]
+        L.pvol_build_gather_map_arrays.argtypes = [C.c_void_p, C.POINTER(abi.PhotonArray)]
+        L.pvol_gather_map_count.argtypes = [C.c_void_p, _u32p]
+        L.pvol_gather_photons.argtypes = [C.c_void_p, _f32p, C.c_uint32, C.c_float, _u32p, _f32p, _u32p, _u32p]
+        L.pvol_gather_photons_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pvol_gather_directions.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_uint32, C.c_float, C.c_int32, C.c_float, _f32p, _f32p, C.c_void_p,
+                                             C.c_void_p]
+        L.pvol_gather_directions_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_int32, C.c_float,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pvol_gather_tree_build.argtypes = [_f32p, C.c_uint32, C.c_void_p, C.POINTER(C.c_int32)]
+        L.pvol_check_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(GatherCheck), C.c_int]
+        L.pvol_probe_hits.argtypes =[C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _f32p, C.POINTER(C.c_int32)]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_set_surface_integrator_maps.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), C.POINTER(abi.PhotonArray), C.POINTER(abi.PhotonArray)]
         L.pvol_check_surface_maps.argtypes = [C.POINTER(abi.SurfaceParams), C.c_int, C.c_int, C.c_int, _u32p, _u32p, C.POINTER(abi.PhotonArray),
@@ -163,7 +208,9 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_film_add_samples_window_device", "pvol_film_resolve_window_device", "pvol_render_frame_ranks_window",
            "pvol_render_frame_group_window", "pvol_tile_kernel_name", "pvol_set_triangle_normals",
            "pvol_compute_radiance", "pvol_compute_radiance_arrays", "pvol_radiance_lo_count", "pvol_download_radiance_lo",
-           "pvol_radiance_lookup", "pvol_radiance_lookup_device", "pvol_set_surface_integrator_maps"]
+           "pvol_radiance_lookup", "pvol_radiance_lookup_device", "pvol_set_surface_integrator_maps",
+           "pvol_build_gather_map", "pvol_build_gather_map_arrays", "pvol_gather_map_count", "pvol_gather_photons",
+           "pvol_gather_photons_device", "pvol_gather_directions", "pvol_gather_directions_device"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -420,6 +467,64 @@ class PhotonVolume:
     def radiance_lookup_device(self, d_p, d_n, count, d_lo, d_found, hip_stream=0):
         """Device-pointer variant (integers): enqueue only, no synchronisation."""
         _check(lib().pvol_radiance_lookup_device(self._h, d_p, d_n, count, d_lo, d_found, hip_stream), "pvol_radiance_lookup_device")
+
+    def build_gather_map(self, indirect=None):
+        """The gather map (the indirect map as the reference's kd-tree): from the indirect store the last preprocess() kept
+        (pvol_build_gather_map), or from indirect = (p[n,3], wi[n,3]) (pvol_build_gather_map_arrays).  Returns its photon count."""
+        if indirect is None:
+            _check(lib().pvol_build_gather_map(self._h), "pvol_build_gather_map")
+        else:
+            p, w = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in indirect[:2])
+            if w.size != p.size:
+                raise ValueError("build_gather_map: %d positions, %d directions" % (p.size // 3, w.size // 3))
+            pa = abi.PhotonArray(p.ctypes.data_as(_f32p), w.ctypes.data_as(_f32p), None, p.size // 3, 0)
+            _check(lib().pvol_build_gather_map_arrays(self._h, C.byref(pa)), "pvol_build_gather_map_arrays")
+        return self.gather_map_count()
+
+    def gather_map_count(self):
+        n = C.c_uint32()
+        _check(lib().pvol_gather_map_count(self._h, C.byref(n)), "pvol_gather_map_count")
+        return n.value
+
+    def gather_photons(self, p, max_dist):
+        """The 50 indirect photons of the final gather at every point p, in the order of PhotonProcess' heap
+        (photonmap.cpp:189-199): (index[count,50] in the store's order, d2[count,50], found[count], rounds[count])."""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1)
+        count = p.size // 3
+        index, d2 = np.zeros((count, GATHER_K), np.uint32), np.zeros((count, GATHER_K), np.float32)
+        found, rounds = np.zeros(count, np.uint32), np.zeros(count, np.uint32)
+        _check(lib().pvol_gather_photons(self._h, p.ctypes.data_as(_f32p), count, float(max_dist), index.ctypes.data_as(_u32p),
+                                         d2.ctypes.data_as(_f32p), found.ctypes.data_as(_u32p), rounds.ctypes.data_as(_u32p)), "pvol_gather_photons")
+        return index, d2, found, rounds
+
+    def gather_photons_device(self, d_p, count, max_dist, d_index, d_d2, d_found, d_rounds, hip_stream=0):
+        """Device-pointer variant (integers): enqueue only, no synchronisation."""
+        _check(lib().pvol_gather_photons_device(self._h, d_p, count, float(max_dist), d_index, d_d2, d_found, d_rounds, hip_stream),
+               "pvol_gather_photons_device")
+
+    def gather_directions(self, p, frames, wo, max_dist, cos_gather_angle, u_bsdf, u_photon):
+        """The gather rays of both sampling loops (photonmap.cpp:208-219, :250-265) with their weights.  frames[count,9] = nn, dpdu,
+        ng; wo[count,3]; u_bsdf, u_photon[count,n_samples,3] = uComponent, uDir[0], uDir[1].  Returns two GATHER_SAMPLE_DTYPE
+        arrays [count, n_samples]: the BSDF-sampled and the photon-sampled rays."""
+        p, frames, wo = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (p, frames, wo))
+        u_bsdf, u_photon = np.ascontiguousarray(u_bsdf, np.float32), np.ascontiguousarray(u_photon, np.float32)
+        count = p.size // 3
+        if u_bsdf.ndim != 3 or u_bsdf.shape != u_photon.shape or u_bsdf.shape[0] != count or u_bsdf.shape[2] != 3:
+            raise ValueError("gather_directions: u_bsdf and u_photon are [count, n_samples, 3]")
+        if frames.size != 9 * count or wo.size != 3 * count:
+            raise ValueError("gather_directions: %d points, %d frames, %d wo" % (count, frames.size // 9, wo.size // 3))
+        ns = u_bsdf.shape[1]
+        ob, op = np.zeros((count, ns), GATHER_SAMPLE_DTYPE), np.zeros((count, ns), GATHER_SAMPLE_DTYPE)
+        _check(lib().pvol_gather_directions(self._h, p.ctypes.data_as(_f32p), frames.ctypes.data_as(_f32p), wo.ctypes.data_as(_f32p), count,
+                                            float(max_dist), ns, float(cos_gather_angle), u_bsdf.ctypes.data_as(_f32p), u_photon.ctypes.data_as(_f32p),
+                                            ob.ctypes.data, op.ctypes.data), "pvol_gather_directions")
+        return ob, op
+
+    def gather_directions_device(self, d_p, d_frames, d_wo, count, max_dist, n_samples, cos_gather_angle, d_u_bsdf, d_u_photon, d_out_bsdf,
+                                 d_out_photon, hip_stream=0):
+        """Device-pointer variant (integers): enqueue only, no synchronisation."""
+        _check(lib().pvol_gather_directions_device(self._h, d_p, d_frames, d_wo, count, float(max_dist), int(n_samples), float(cos_gather_angle),
+                                                   d_u_bsdf, d_u_photon, d_out_bsdf, d_out_photon, hip_stream), "pvol_gather_directions_device")
 
     def check_errors(self):
         """Raises PvolError(PVOL_E_LIMIT) if a batch enqueued through a device entry point hit a kernel limit."""

@@ -395,8 +395,9 @@ int pvol_download_radiance_photons(pvol_ctx *ctx, float *p, float *n, float *rho
  * sum of three k-NN irradiance estimates EPhoton (:17-35; PhotonProcess, photonshooter.h:186-203; the visit test of
  * core/kdtree.h:180) over the direct, indirect and caustic maps, and the photons become radianceMap, which the final gather asks for
  * the nearest photon facing a point (RadiancePhotonProcess, photonshooter.h:63-78; integrators/photonmap.cpp:226-230).  Nothing
- * else calls these: pvol_preprocess* does not compute radiance and the final gather that would ask radianceMap is not built
- * (pvol_set_surface_integrator_maps refuses `finalgather` with an indirect map). */
+ * else calls these: pvol_preprocess* does not compute radiance, and of the final gather that would ask radianceMap only the
+ * sampling half exists (pvol_gather_* below: the 50 photons and the gather rays' directions and weights; the rays are not traced,
+ * so pvol_set_surface_integrator_maps still refuses `finalgather` with an indirect map). */
 typedef struct pvol_photon_array {   /* host arrays: p, wi 3 floats, alpha 30 floats per photon */
     const float *p, *wi, *alpha; uint32_t n; uint32_t n_paths;
 } pvol_photon_array;
@@ -426,6 +427,68 @@ int pvol_download_radiance_lo(pvol_ctx *ctx, float *p, float *n, float *lo, uint
 int pvol_radiance_lookup(pvol_ctx *ctx, const float *p, const float *n, uint32_t count, float *lo, uint32_t *found);
 int pvol_radiance_lookup_device(pvol_ctx *ctx, const float *d_p, const float *d_n, uint32_t count, float *d_lo,
                                 uint32_t *d_found, void *hip_stream);
+
+/* ---- final gather, sampling half: what PhotonIntegrator::Li does between `if (finalGather && indirectMap != NULL)` and the moment a
+ * gather ray is traced (integrators/photonmap.cpp:183-219, :248-265), and the weight each ray carries (:233-243, :280-291) ----
+ * The gather map is the indirect map as the reference's own kd-tree (KdTree<Photon>::KdTree, core/kdtree.h:99-147), because the
+ * photon-sampled loop picks photonDirs[j] by its PLACE in the heap PhotonProcess leaves (core/photonshooter.h:186-203), and that
+ * place depends on the tree's visiting order (kdtree.h:157-183).  Results are exact, ties included: CompareNode breaks a
+ * coordinate tie by the photon's index in the store, ClosePhoton::operator< a distance tie by the node number, and the heap
+ * routines leave libstdc++'s layout.
+ *
+ * Statuses, decided in this one order (pvol_check_gather):
+ *   1. PVOL_E_INVALID      NULL ctx
+ *   builds:
+ *   2. PVOL_E_INVALID      pvol_build_gather_map without kept stores; _arrays: NULL `indirect`, NULL p or wi with n > 0, a
+ *                          non-finite p or wi (a non-finite position in the kept store is answered the same way, once the
+ *                          store has been read back)
+ *   3. PVOL_E_UNSUPPORTED  fewer than 50 photons (photonmap.cpp:194-199 does not terminate on such a map) or more than 2^24
+ *   lookups:
+ *   2. PVOL_E_INVALID      max_dist not > 0, not finite, or so small that max_dist^2 is 0 in fp32 (the doubling would never leave
+ *                          it); n_samples outside 1..256; cos_gather_angle not inside (-1, 1); a NULL array with count > 0
+ *   3. PVOL_E_INVALID      no gather map built
+ *   then PVOL_E_NO_DEVICE / PVOL_E_NO_MEMORY from the device, as everywhere.
+ * A rejected call changes nothing; a second build replaces the first; whatever drops the radiance result above (a new shoot,
+ * freeing the kept stores) drops the map too. */
+
+/* Replaces `new KdTree<Photon>(indirectPhotons)` (photonshooter.cpp:502) for the gather: from the indirect store (kind 2) the last
+   pvol_preprocess* kept. */
+int pvol_build_gather_map(pvol_ctx *ctx);
+/* The same from the caller's host arrays (p and wi are read, alpha and n_paths are not); needs no scene. */
+int pvol_build_gather_map_arrays(pvol_ctx *ctx, const pvol_photon_array *indirect);
+int pvol_gather_map_count(pvol_ctx *ctx, uint32_t *n);   /* 0 until a build succeeded */
+
+/* Replaces photonmap.cpp:189-199: per query point p (3 floats) the loop `md2 = searchDist2; nFound = 0; Lookup(p, proc, md2);
+   searchDist2 *= 2` from searchDist2 = max_dist^2 until 50 photons are found.  index: 50 per query, the photons' indices in the
+   store's order, in the order of proc.photons[]; d2: their squared distances; found: 50, or fewer when even a round over the whole
+   map (md2 = +inf) did not hold 50 -- a non-finite query, a d^2 that overflows; the tail of index and d2 is then zero and the call
+   still returns PVOL_OK; rounds: Lookup calls made.  The device form takes DEVICE pointers and is enqueued on `hip_stream` without
+   synchronising. */
+int pvol_gather_photons(pvol_ctx *ctx, const float *p, uint32_t count, float max_dist, uint32_t *index, float *d2, uint32_t *found,
+                        uint32_t *rounds);
+int pvol_gather_photons_device(pvol_ctx *ctx, const float *d_p, uint32_t count, float max_dist, uint32_t *d_index, float *d_d2,
+                               uint32_t *d_found, uint32_t *d_rounds, void *hip_stream);
+
+/* One gather ray as either loop samples it.  weight: what multiplies fr * Lindir in the sum (AbsDot(wi, n) * wt / pdf; neither
+   fr = Kd INV_PI nor Lindir is multiplied in); photon_index: the store index of photonDirs[photonNum] in the photon loop,
+   0xffffffff in the BSDF loop; valid 0: the reference `continue`s (pdf == 0 or fr black), wi, weight and the pdfs are then 0. */
+typedef struct pvol_gather_sample {
+    float wi[3], weight, bsdf_pdf, photon_pdf; uint32_t photon_index, valid;
+} pvol_gather_sample;
+
+/* Replaces photonmap.cpp:189-219 and :248-265 with the weights of :233-243 and :280-291, for a BSDF of one Lambertian lobe: the
+   lookup above, then n_samples BSDF-sampled and n_samples photon-sampled gather rays per query.  frames: 9 floats per query,
+   dgShading.nn, dgShading.dpdu, ng (the frame is built as BSDF::BSDF does, core/reflection.cpp:619-627); wo: 3 floats;
+   u_bsdf, u_photon: per query and sample uComponent, uDir[0], uDir[1] in [0, 1); cos_gather_angle: PhotonShooter's
+   cosGatherAngle (photonshooter.cpp:413).  out_bsdf, out_photon: n_samples records per query.  A query whose lookup found fewer
+   than 50 gets invalid records. */
+int pvol_gather_directions(pvol_ctx *ctx, const float *p, const float *frames, const float *wo, uint32_t count, float max_dist,
+                           int32_t n_samples, float cos_gather_angle, const float *u_bsdf, const float *u_photon,
+                           pvol_gather_sample *out_bsdf, pvol_gather_sample *out_photon);
+int pvol_gather_directions_device(pvol_ctx *ctx, const float *d_p, const float *d_frames, const float *d_wo, uint32_t count,
+                                  float max_dist, int32_t n_samples, float cos_gather_angle, const float *d_u_bsdf,
+                                  const float *d_u_photon, pvol_gather_sample *d_out_bsdf, pvol_gather_sample *d_out_photon,
+                                  void *hip_stream);
 
 /* Number of photons in the current volume map. */
 int pvol_photon_count(pvol_ctx *ctx, uint32_t *n);
