@@ -118,7 +118,9 @@ enum {
     PVOL_BUF_SEG_COUNTER, PVOL_BUF_SEG_STREAM,   // ... its fill counter (16 bytes) and the pool seen as one pvol_stream
     PVOL_BUF_TILE_RAYS, PVOL_BUF_TILE_XY, PVOL_BUF_TILE_OUT, PVOL_BUF_TILE_STREAMS, PVOL_BUF_TILE_WINDOWS,   // render driver (pvol_render_host.hip)
     PVOL_BUF_LI_IN, PVOL_BUF_LI_OUT,    // device staging of the coalesced per-sample batches (pvol_li_coalesce.hip)
-    PVOL_BUF_GROUP_STAGE, PVOL_N_BUFS   // pvol_render_frame_group: the other contexts' films next to the root's
+    PVOL_BUF_GROUP_STAGE,               // pvol_render_frame_group: the other contexts' films next to the root's
+    PVOL_BUF_FG_DIRS, PVOL_BUF_FG_RAYS, // pvol_final_gather* (pvol_final_gather.hip): a slice's direction records and ray records
+    PVOL_N_BUFS
 };
 extern "C" bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream);
 
@@ -215,6 +217,7 @@ struct pvol_ctx {
     uint32_t nRad = 0;
     RadianceResult rad;    // pvol_compute_radiance*: dropped by every shoot and by pvol_free_surface_stores
     GatherMap gather;      // pvol_build_gather_map*: dropped wherever `rad` is
+    uint64_t fgScratchBound = 0;   // pvol_final_gather_set_scratch_bound (tests): bytes of scratch a slice may take, 0 = PVOL_FINAL_GATHER_SCRATCH_BYTES
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     PhotonGrid causticMap;
     // ... and its indirect map (pvol_set_surface_integrator_maps: LPhoton(indirectMap) without the final gather), built by the same builder
@@ -333,6 +336,19 @@ struct GatherCheck {
     const float *frames, *wo, *uBsdf, *uPhoton; int32_t nSamples; float cosGatherAngle; const void *outBsdf, *outPhoton;   // what 3
 };
 int pvol_check_gather(int what, int haveCtx, int haveState, uint32_t storeN, const GatherCheck *args, int hostPointers);
+// every status of pvol_final_gather* in its one order (include/pvol.h), reachable without a device for the tests
+// (pvol_final_gather.hip); no HIP call.  args: the call's pointers and numbers; volKind: the scene's medium; haveGather: a gather
+// map is built; haveRad / radN: a radiance result exists / its radiance photons
+struct FinalGatherCheck {
+    const float *p, *frames, *wo, *kd, *rayEps; uint32_t count; float maxDist; int32_t nSamples; float cosGatherAngle;
+    const float *uBsdf, *uPhoton; const void *L, *draws;
+};
+int pvol_check_final_gather(int haveCtx, const FinalGatherCheck *args, int haveScene, int volKind, int haveGather, int haveRad, uint32_t radN);
+// queries per slice of pvol_final_gather*: as many as keep a slice's scratch (64 bytes per gather ray, 2 n_samples rays per query)
+// within `bound` bytes (0 or more than PVOL_FINAL_GATHER_SCRATCH_BYTES: that), whole blocks of 64 where that many fit, never fewer than one
+uint32_t pvol_final_gather_slice(int32_t nSamples, uint64_t bound);
+// lowers (or, with 0, restores) the scratch bound of this context's pvol_final_gather* calls, for the tests
+int pvol_final_gather_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
 // the shoot's merge (ShootMerge, pvol_shoot_merge.h) replayed over recorded count tables, for the tests (pvol_shoot_host.hip)
 size_t pvol_shoot_merge_replay(const uint32_t *cfg, const uint32_t *tables, uint32_t nTables, uint64_t *out, size_t cap);
 // the plan of a render call (RenderPlan below) flattened for the tests (pvol_render_host.hip)

@@ -12,6 +12,7 @@
 
 #include "pvol_math.h"
 #include "pvol_gridrows_dev.h"
+#include "pvol_radwalk_dev.h"
 #include "pvol_host.h"
 
 #define RAD_MAX_LOOKUP 576   // the project's nused bound
@@ -35,10 +36,8 @@ struct RadLoArgs {
     float *lo;       // [nRp][30]
 };
 struct RadNearestArgs {
-    GridView g;
-    const float4 *nrm4, *lo4;   // the radiance map's wi4 (normals) and 32-float rows (Lo)
-    uint32_t n;
-    float eps;                  // slack of a shell's distance bound
+    RadWalk w;                  // the radiance map's grid and normals (pvol_radwalk_dev.h)
+    const float4 *lo4;          // its 32-float rows (Lo)
     const float *qp, *qn;
     uint32_t count;
     float *lo;
@@ -164,66 +163,13 @@ __global__ __launch_bounds__(256) void radiance_lo_kernel(const RadLoArgs *__res
     }
 }
 
-// radianceMap->Lookup(p, RadiancePhotonProcess(n), INFINITY): one query per lane.  Cube shells of cells outward from the query's
-// (clamped) cell; a shell's cells lie beyond one of the six faces of the cube of shells before it, so the nearest of those faces
-// that still has cells behind it bounds the shell's distance from below.
+// radianceMap->Lookup(p, RadiancePhotonProcess(n), INFINITY): one query per lane; the walk itself is radiance_nearest
+// (pvol_radwalk_dev.h), shared with the final gather.
 __global__ __launch_bounds__(256) void radiance_nearest_kernel(RadNearestArgs A) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.count) return;
-    float best = INFINITY;
-    int64_t bestIdx = -1;
-    if (A.n) {
-        const float q[3] = {A.qp[3 * (size_t)i], A.qp[3 * (size_t)i + 1], A.qp[3 * (size_t)i + 2]};
-        const float nx = A.qn[3 * (size_t)i], ny = A.qn[3 * (size_t)i + 1], nz = A.qn[3 * (size_t)i + 2];
-        const GridView &g = A.g;
-        int c0[3], maxS = 0;
-        for (int a = 0; a < 3; ++a) {
-            // clamped in float before the conversion: a huge (or, from the device entry point, non-finite) coordinate must not
-            // reach an int conversion outside its range; fmaxf / fminf drop a NaN
-            const float cf = fminf(fmaxf(floorf((q[a] - g.gridLo[a]) * g.invCell), 0.f), (float)(g.gdim[a] - 1));
-            c0[a] = min(max((int)cf, 0), g.gdim[a] - 1);
-            maxS = max(maxS, max(c0[a], g.gdim[a] - 1 - c0[a]));
-        }
-        for (int s = 0; s <= maxS; ++s) {
-            if (s > 0) {
-                float face = INFINITY;
-                for (int a = 0; a < 3; ++a) {
-                    if (c0[a] + s <= g.gdim[a] - 1) face = fminf(face, (g.gridLo[a] + (float)(c0[a] + s) * g.cellSize) - q[a]);
-                    if (c0[a] - s >= 0) face = fminf(face, q[a] - (g.gridLo[a] + (float)(c0[a] - s + 1) * g.cellSize));
-                }
-                const float d = fmaxf(0.f, face - A.eps);
-                if (best < INFINITY && d * d >= best) break;   // with nothing found yet (or every d2 so far overflowed) the walk goes on
-            }
-            const int z0 = max(0, c0[2] - s), z1 = min(g.gdim[2] - 1, c0[2] + s);
-            const int y0 = max(0, c0[1] - s), y1 = min(g.gdim[1] - 1, c0[1] + s);
-            for (int z = z0; z <= z1; ++z)
-                for (int y = y0; y <= y1; ++y) {
-                    const bool wholeRow = abs(z - c0[2]) == s || abs(y - c0[1]) == s;
-                    const size_t base = ((size_t)z * g.gdim[1] + y) * g.gdim[0];
-                    // the row's cells of this shell: all of c0x - s .. c0x + s on a face, else the two ends
-                    for (int part = 0; part < 2; ++part) {
-                        int x0, x1;
-                        if (wholeRow) {
-                            if (part) break;
-                            x0 = max(0, c0[0] - s); x1 = min(g.gdim[0] - 1, c0[0] + s);
-                        } else {
-                            x0 = x1 = part ? c0[0] + s : c0[0] - s;
-                            if (x0 < 0 || x0 > g.gdim[0] - 1) continue;
-                        }
-                        const uint32_t j0 = g.cellStart[base + x0], j1 = g.cellStart[base + x1 + 1];
-                        for (uint32_t j = j0; j < j1; ++j) {
-                            const float4 pp = g.pos4[j];
-                            const float dx = pp.x - q[0], dy = pp.y - q[1], dz = pp.z - q[2];
-                            const float d2 = dx * dx + dy * dy + dz * dz;
-                            if (d2 < best) {
-                                const float4 rn = A.nrm4[j];
-                                if (rn.x * nx + rn.y * ny + rn.z * nz > 0.f) { best = d2; bestIdx = (int64_t)j; }
-                            }
-                        }
-                    }
-                }
-        }
-    }
+    const float q[3] = {A.qp[3 * (size_t)i], A.qp[3 * (size_t)i + 1], A.qp[3 * (size_t)i + 2]};
+    const int64_t bestIdx = radiance_nearest(A.w, q, A.qn[3 * (size_t)i], A.qn[3 * (size_t)i + 1], A.qn[3 * (size_t)i + 2]);
     A.found[i] = bestIdx >= 0 ? 1u : 0u;
     const float *row = bestIdx >= 0 ? (const float *)A.lo4 + (size_t)bestIdx * 32 : 0;
     for (int b = 0; b < 30; ++b) A.lo[30 * (size_t)i + b] = row ? row[b] : 0.f;
@@ -306,15 +252,23 @@ static int compute_radiance(pvol_ctx *c, int32_t k, float maxDist, const MapSour
     return PVOL_OK;
 }
 
-static hipError_t launch_nearest(const pvol_ctx *c, const float *dP, const float *dN, uint32_t count, float *dLo, uint32_t *dFound, hipStream_t stream) {
+RadWalk pvol_radiance_walk(const pvol_ctx *c) {
     const PhotonGrid &G = c->rad.map;
-    RadNearestArgs A;
-    memset(&A, 0, sizeof(A));
-    A.g = rad_map(G, 1).g;
-    A.nrm4 = G.wi4.get(); A.lo4 = G.alpha4.get(); A.n = c->rad.n ? G.n : 0u;
+    RadWalk w;
+    memset(&w, 0, sizeof(w));
+    w.g = rad_map(G, 1).g;
+    w.nrm4 = G.wi4.get(); w.n = c->rad.n ? G.n : 0u;
     // photons are put into cells by floor((x - lo) * inv) in fp32: a shell's bound gives way by 1e-4 cell plus the rounding of the
     // largest cell index
-    A.eps = G.cellSize * (1e-4f + 1e-6f * (float)std::max(G.gdim[0], std::max(G.gdim[1], G.gdim[2])));
+    w.eps = G.cellSize * (1e-4f + 1e-6f * (float)std::max(G.gdim[0], std::max(G.gdim[1], G.gdim[2])));
+    return w;
+}
+
+static hipError_t launch_nearest(const pvol_ctx *c, const float *dP, const float *dN, uint32_t count, float *dLo, uint32_t *dFound, hipStream_t stream) {
+    RadNearestArgs A;
+    memset(&A, 0, sizeof(A));
+    A.w = pvol_radiance_walk(c);
+    A.lo4 = c->rad.map.alpha4.get();
     A.qp = dP; A.qn = dN; A.count = count; A.lo = dLo; A.found = dFound;
     hipLaunchKernelGGL(radiance_nearest_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, A);
     return hipGetLastError();

@@ -38,7 +38,10 @@ GATHER_SAMPLE_DTYPE = np.dtype([("wi", "<f4", 3), ("weight", "<f4"), ("bsdf_pdf"
 # GatherNode (csrc/pvol_gather_tree.h), what the test hook pvol_gather_tree_build fills
 GATHER_NODE_DTYPE = np.dtype([("p", "<f4", 3), ("split_pos", "<f4"), ("split_axis", "<u4"), ("has_left_child", "<u4"), ("right_child", "<u4"),
                               ("index", "<u4")])
-assert GATHER_SAMPLE_DTYPE.itemsize == 32 and GATHER_NODE_DTYPE.itemsize == 32
+# pvol_gather_ray (final gather, tracing half: pvol_final_gather*)
+GATHER_RAY_DTYPE = np.dtype([("t", "<f4"), ("n_gather", "<f4", 3), ("radiance_index", "<u4"), ("prim", "<i4"), ("hit", "<u4"), ("drew", "<u4")])
+GATHER_NONE = 0xffffffff
+assert GATHER_SAMPLE_DTYPE.itemsize == 32 and GATHER_NODE_DTYPE.itemsize == 32 and GATHER_RAY_DTYPE.itemsize == 32
 
 
 class GatherCheck(C.Structure):   # the arguments pvol_check_gather judges (csrc/pvol_host.h)
@@ -46,6 +49,12 @@ class GatherCheck(C.Structure):   # the arguments pvol_check_gather judges (csrc
                 ("out_index", C.c_void_p), ("out_d2", C.c_void_p), ("out_found", C.c_void_p), ("out_rounds", C.c_void_p),
                 ("frames", _f32p), ("wo", _f32p), ("u_bsdf", _f32p), ("u_photon", _f32p), ("n_samples", C.c_int32), ("cos_gather_angle", C.c_float),
                 ("out_bsdf", C.c_void_p), ("out_photon", C.c_void_p)]
+
+
+class FinalGatherCheck(C.Structure):   # the arguments pvol_check_final_gather judges (csrc/pvol_host.h)
+    _fields_ = [("p", _f32p), ("frames", _f32p), ("wo", _f32p), ("kd", _f32p), ("ray_eps", _f32p), ("count", C.c_uint32), ("max_dist", C.c_float),
+                ("n_samples", C.c_int32), ("cos_gather_angle", C.c_float), ("u_bsdf", _f32p), ("u_photon", _f32p), ("L", C.c_void_p),
+                ("draws", C.c_void_p)]
 
 
 def gather_cos_angle(gather_angle):
@@ -152,6 +161,13 @@ def lib():
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pvol_gather_tree_build.argtypes = [_f32p, C.c_uint32, C.c_void_p, C.POINTER(C.c_int32)]
         L.pvol_check_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(GatherCheck), C.c_int]
+        L.pvol_final_gather.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_uint32, C.c_float, C.c_int32, C.c_float, _f32p, _f32p,
+                                        _f32p, _u32p, C.c_void_p, C.c_void_p]
+        L.pvol_final_gather_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_uint32, C.c_float, C.c_int32, C.c_float] + [C.c_void_p] * 7
+        L.pvol_check_final_gather.argtypes = [C.c_int, C.POINTER(FinalGatherCheck), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
+        L.pvol_final_gather_slice.argtypes = [C.c_int32, C.c_uint64]
+        L.pvol_final_gather_slice.restype = C.c_uint32
+        L.pvol_final_gather_set_scratch_bound.argtypes = [C.c_void_p, C.c_uint64]
         L.pvol_probe_hits.argtypes =[C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _f32p, C.POINTER(C.c_int32)]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_set_surface_integrator_maps.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), C.POINTER(abi.PhotonArray), C.POINTER(abi.PhotonArray)]
@@ -210,7 +226,8 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_compute_radiance", "pvol_compute_radiance_arrays", "pvol_radiance_lo_count", "pvol_download_radiance_lo",
            "pvol_radiance_lookup", "pvol_radiance_lookup_device", "pvol_set_surface_integrator_maps",
            "pvol_build_gather_map", "pvol_build_gather_map_arrays", "pvol_gather_map_count", "pvol_gather_photons",
-           "pvol_gather_photons_device", "pvol_gather_directions", "pvol_gather_directions_device"]
+           "pvol_gather_photons_device", "pvol_gather_directions", "pvol_gather_directions_device", "pvol_final_gather",
+           "pvol_final_gather_device"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -525,6 +542,41 @@ class PhotonVolume:
         """Device-pointer variant (integers): enqueue only, no synchronisation."""
         _check(lib().pvol_gather_directions_device(self._h, d_p, d_frames, d_wo, count, float(max_dist), int(n_samples), float(cos_gather_angle),
                                                    d_u_bsdf, d_u_photon, d_out_bsdf, d_out_photon, hip_stream), "pvol_gather_directions_device")
+
+    def final_gather(self, p, frames, wo, kd, ray_eps, max_dist, cos_gather_angle, u_bsdf, u_photon, rays=False):
+        """The final gather at every point p (photonmap.cpp:183-295 for a Lambertian hit): the gather rays of gather_directions()
+        traced, Lindir from the radiance map, the homogeneous medium's transmittance, and both loops' weighted sums.  kd[count,30],
+        ray_eps[count]; n_samples is u_bsdf.shape[1].  Returns (L[count,30], draws[count]) and, with rays=True, a third item
+        (rays_bsdf, rays_photon): two GATHER_RAY_DTYPE arrays [count, n_samples]."""
+        p, frames, wo, kd, ray_eps = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (p, frames, wo, kd, ray_eps))
+        u_bsdf, u_photon = np.ascontiguousarray(u_bsdf, np.float32), np.ascontiguousarray(u_photon, np.float32)
+        count = p.size // 3
+        if u_bsdf.ndim != 3 or u_bsdf.shape != u_photon.shape or u_bsdf.shape[0] != count or u_bsdf.shape[2] != 3:
+            raise ValueError("final_gather: u_bsdf and u_photon are [count, n_samples, 3]")
+        if frames.size != 9 * count or wo.size != 3 * count or kd.size != 30 * count or ray_eps.size != count:
+            raise ValueError("final_gather: %d points, %d frames, %d wo, %d kd, %d ray_eps" % (count, frames.size // 9, wo.size // 3, kd.size // 30,
+                                                                                             ray_eps.size))
+        ns = u_bsdf.shape[1]
+        L, draws = np.zeros((count, 30), np.float32), np.zeros(count, np.uint32)
+        rb = np.zeros((count, ns), GATHER_RAY_DTYPE) if rays else None
+        rp = np.zeros((count, ns), GATHER_RAY_DTYPE) if rays else None
+        _check(lib().pvol_final_gather(self._h, p.ctypes.data_as(_f32p), frames.ctypes.data_as(_f32p), wo.ctypes.data_as(_f32p),
+                                       kd.ctypes.data_as(_f32p), ray_eps.ctypes.data_as(_f32p), count, float(max_dist), ns, float(cos_gather_angle),
+                                       u_bsdf.ctypes.data_as(_f32p), u_photon.ctypes.data_as(_f32p), L.ctypes.data_as(_f32p),
+                                       draws.ctypes.data_as(_u32p), rb.ctypes.data if rays else None, rp.ctypes.data if rays else None),
+               "pvol_final_gather")
+        return (L, draws, (rb, rp)) if rays else (L, draws)
+
+    def final_gather_device(self, d_p, d_frames, d_wo, d_kd, d_ray_eps, count, max_dist, n_samples, cos_gather_angle, d_u_bsdf, d_u_photon, d_L,
+                            d_draws, d_rays_bsdf=0, d_rays_photon=0, hip_stream=0):
+        """Device-pointer variant (integers): enqueue only, no synchronisation."""
+        _check(lib().pvol_final_gather_device(self._h, d_p, d_frames, d_wo, d_kd, d_ray_eps, count, float(max_dist), int(n_samples),
+                                              float(cos_gather_angle), d_u_bsdf, d_u_photon, d_L, d_draws, d_rays_bsdf or None,
+                                              d_rays_photon or None, hip_stream), "pvol_final_gather_device")
+
+    def final_gather_set_scratch_bound(self, nbytes):
+        """Test hook: the bytes of scratch a slice of final_gather() may take (0: the header's PVOL_FINAL_GATHER_SCRATCH_BYTES)."""
+        _check(lib().pvol_final_gather_set_scratch_bound(self._h, int(nbytes)), "pvol_final_gather_set_scratch_bound")
 
     def check_errors(self):
         """Raises PvolError(PVOL_E_LIMIT) if a batch enqueued through a device entry point hit a kernel limit."""

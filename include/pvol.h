@@ -395,9 +395,9 @@ int pvol_download_radiance_photons(pvol_ctx *ctx, float *p, float *n, float *rho
  * sum of three k-NN irradiance estimates EPhoton (:17-35; PhotonProcess, photonshooter.h:186-203; the visit test of
  * core/kdtree.h:180) over the direct, indirect and caustic maps, and the photons become radianceMap, which the final gather asks for
  * the nearest photon facing a point (RadiancePhotonProcess, photonshooter.h:63-78; integrators/photonmap.cpp:226-230).  Nothing
- * else calls these: pvol_preprocess* does not compute radiance, and of the final gather that would ask radianceMap only the
- * sampling half exists (pvol_gather_* below: the 50 photons and the gather rays' directions and weights; the rays are not traced,
- * so pvol_set_surface_integrator_maps still refuses `finalgather` with an indirect map). */
+ * else calls these: pvol_preprocess* does not compute radiance, and the final gather that asks radianceMap exists as entry points
+ * of its own (pvol_gather_* and pvol_final_gather* below), not yet inside the surface integrator: pvol_set_surface_integrator_maps
+ * still refuses `finalgather` with an indirect map. */
 typedef struct pvol_photon_array {   /* host arrays: p, wi 3 floats, alpha 30 floats per photon */
     const float *p, *wi, *alpha; uint32_t n; uint32_t n_paths;
 } pvol_photon_array;
@@ -489,6 +489,57 @@ int pvol_gather_directions_device(pvol_ctx *ctx, const float *d_p, const float *
                                   float max_dist, int32_t n_samples, float cos_gather_angle, const float *d_u_bsdf,
                                   const float *d_u_photon, pvol_gather_sample *d_out_bsdf, pvol_gather_sample *d_out_photon,
                                   void *hip_stream);
+
+/* ---- final gather, tracing half: what PhotonIntegrator::Li does with every gather ray of both loops from the construction of
+ * bounceRay to `L += Li / gatherSamples` (integrators/photonmap.cpp:219-231, :243-246, :265-278, :291-295), on top of the
+ * sampling half above.  Per query point p (the dgShading.p of a Lambertian hit) and per valid sample of pvol_gather_directions:
+ * the ray (p, wi, mint = ray_eps, maxt = +inf) meets the scene (Scene::Intersect: any primitive counts, glass too; a miss
+ * contributes nothing and draws nothing); nGather = Faceforward(dg.nn, -wi) with the GEOMETRIC normal; Lindir is the Lo of
+ * radianceMap->Lookup(hit point, RadiancePhotonProcess(nGather), INFINITY) -- the walk of pvol_radiance_lookup -- or 0 when no
+ * photon faces; Lindir *= Transmittance over [ray_eps, t_hit], which draws one RandomFloat per ray that hits exactly when the scene
+ * has a volume region, and for a homogeneous medium is exp(-sigma_t |p(t0) - p(t1)|) whatever was drawn
+ * (volumes/homogeneous.h:78-82).  Then
+ *     L = sum_bsdf (Kd INV_PI) Lindir weight / n_samples + sum_photon (Kd INV_PI) Lindir weight / n_samples,
+ * each loop summed in sample order; draws counts the RandomFloat calls.  A query whose Kd is black in every bin, or whose lookup
+ * found fewer than 50 photons, gives L = 0 and zero draws with nothing traced.  Nothing is wired into the surface integrator yet:
+ * pvol_set_surface_integrator_maps still refuses `finalgather` with an indirect map.
+ *
+ * Statuses, decided in this one order (pvol_check_final_gather):
+ *   1. PVOL_E_INVALID      NULL ctx
+ *   2. PVOL_E_INVALID      the argument faults of pvol_gather_directions; a NULL kd, ray_eps, L or draws with count > 0
+ *   3. PVOL_E_NO_SCENE
+ *   4. PVOL_E_UNSUPPORTED  the scene's medium is a density region (VolumeGrid, exponential), as behind the surface integrator
+ *   5. PVOL_E_INVALID      no gather map built
+ *   6. PVOL_E_INVALID      no radiance result, or one with zero radiance photons (the reference's lookup on an empty tree is
+ *                          undefined)
+ *   then PVOL_E_NO_DEVICE / PVOL_E_NO_MEMORY from the device.  A rejected call writes nothing. */
+
+/* One traced gather ray.  All zero for an invalid sample and for every sample of a dead query; a valid ray that misses has hit 0,
+   radiance_index 0xffffffff and the rest zero. */
+typedef struct pvol_gather_ray {      /* 32 bytes; one per query, loop and sample */
+    float t, n_gather[3];             /* the hit's ray parameter; Faceforward(dg.nn, -wi) */
+    uint32_t radiance_index;          /* the radiance photon found, in the input order of the radiance photons
+                                         (pvol_download_radiance_lo); 0xffffffff: none faces */
+    int32_t prim;                     /* triangle index in upload order, -1 - i for sphere i */
+    uint32_t hit, drew;               /* 1 / 0; RandomFloat calls of this ray's Transmittance (0 or 1) */
+} pvol_gather_ray;
+
+/* Queries are walked in slices so that the per-ray scratch (a direction record and a ray record, 64 bytes) stays within this
+   bound; the scratch belongs to the context. */
+#define PVOL_FINAL_GATHER_SCRATCH_BYTES (256ull << 20)
+
+/* p, frames, wo, max_dist, cos_gather_angle, u_bsdf, u_photon: exactly as for pvol_gather_directions.  kd: 30 floats per query
+   (the Lambertian's R); ray_eps: isect.rayEpsilon per query; n_samples: gatherSamples after RequestSamples has halved and rounded
+   it.  L: 30 floats, draws: one count per query.  rays_bsdf, rays_photon: n_samples records per query, optional (NULL: not
+   reported).  The host form holds the context from upload to copy-back; the device form takes DEVICE pointers, is enqueued on
+   `hip_stream` and not synchronised. */
+int pvol_final_gather(pvol_ctx *ctx, const float *p, const float *frames, const float *wo, const float *kd, const float *ray_eps,
+                      uint32_t count, float max_dist, int32_t n_samples, float cos_gather_angle, const float *u_bsdf,
+                      const float *u_photon, float *L, uint32_t *draws, pvol_gather_ray *rays_bsdf, pvol_gather_ray *rays_photon);
+int pvol_final_gather_device(pvol_ctx *ctx, const float *d_p, const float *d_frames, const float *d_wo, const float *d_kd,
+                             const float *d_ray_eps, uint32_t count, float max_dist, int32_t n_samples, float cos_gather_angle,
+                             const float *d_u_bsdf, const float *d_u_photon, float *d_L, uint32_t *d_draws,
+                             pvol_gather_ray *d_rays_bsdf, pvol_gather_ray *d_rays_photon, void *hip_stream);
 
 /* Number of photons in the current volume map. */
 int pvol_photon_count(pvol_ctx *ctx, uint32_t *n);
