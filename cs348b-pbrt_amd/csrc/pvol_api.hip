@@ -70,6 +70,7 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     { const char *fs = getenv("PVOL_FORCE_SEQ"); c->forceSeq = fs && fs[0] == '1'; }
     { const char *ng = getenv("PVOL_NO_GROUP"); c->noGroup = ng && ng[0] == '1'; }
     { const char *nl = getenv("PVOL_NO_LITE"); c->noLite = nl && nl[0] == '1'; }
+    { const char *nm = getenv("PVOL_NO_MOMENTS"); c->noMoments = nm && nm[0] == '1'; }
     { const char *gw = getenv("PVOL_GROUP_WAVES"); if (gw) c->groupWavesPerCU = std::max(1, atoi(gw)); }
     { const char *tw = getenv("PVOL_TILE_WAVES"); if (tw) c->tileWaves = std::max(0, atoi(tw)); }
     // li_fixup_kernel / li_fixup_group_kernel waves per CU (C3, 8 spp frame: 16.3 s at 8, 13.9 s at 16)
@@ -143,6 +144,14 @@ BatchPlan plan_path(const PlanIn &in) {
     const bool bucket = !in.noGroup && in.g == 0.f && in.nPhotons > 0 && in.nUsed >= 10;
     if (par) {   // homogeneous and k <= 64; li_par_kernel (one wave per ray) otherwise
         p.groupForm = bucket && homog && in.nUsed <= 64 && in.candCap <= 4 * 64;
+        // an XYZ result of a nearly grey medium: the flux is summed as moments.  The stats launch keeps the 30 bins
+        // (a -DGRP_PHASE_DIAG build, timing only, times the form the plain launch takes)
+#ifdef GRP_PHASE_DIAG
+        const bool momStats = true;
+#else
+        const bool momStats = !in.statsOn;
+#endif
+        if (p.groupForm && in.momentTerms > 0 && in.outXYZ && !in.noMoments && momStats) p.groupForm = GRP_FORM_MOMENTS;
         p.kernel = p.groupForm ? "li_group_kernel" : "li_par_kernel";
     } else if (sliced) {
         // with a tile pre-pass in FUSED mode (several lights) the flag selects the pre-pass's own geometry + RNG-only form
@@ -221,6 +230,95 @@ void pvol_plan_batch(const PlanIn *in, BatchPlan *out) {
     if (out->rc == PVOL_OK) plan_size(*in, *out);
 }
 
+// ---- the moment form's gate and constants (pvol_host.h): pure, no HIP call, no context, no environment
+// sigma_t's midrange as the float the kernels multiply by, and the largest |sigma_t_b - it|
+static float moment_sig_bar(const float *sigA, const float *sigS, double *maxDelta) {
+    float lo = INFINITY, hi = -INFINITY;
+    for (int b = 0; b < PVOL_NBINS; ++b) { const float t = sigA[b] + sigS[b]; lo = std::min(lo, t); hi = std::max(hi, t); }
+    const float bar = (float)(0.5 * ((double)lo + (double)hi));
+    *maxDelta = std::max((double)hi - (double)bar, (double)bar - (double)lo);
+    return bar;
+}
+// smallest N in 1..maxN with x^N / N! e^x < 2^-25, x = max|delta| pathBound; 0 = none
+static int moment_terms(const float *sigA, const float *sigS, double pathBound, int maxN) {
+    double maxDelta = 0.0;
+    const float bar = moment_sig_bar(sigA, sigS, &maxDelta);
+    if (!std::isfinite(bar) || !std::isfinite(pathBound) || !(pathBound >= 0.0)) return 0;
+    const double x = maxDelta * pathBound;
+    double term = exp(x);   // x^N / N! e^x
+    for (int n = 1; n <= maxN; ++n) {
+        term *= x / n;
+        if (term < ldexp(1.0, -25)) return n;
+    }
+    return 0;
+}
+int pvol_moment_gate(const float *sigA, const float *sigS, double pathBound) {
+    if (!sigA || !sigS) return 0;
+    return moment_terms(sigA, sigS, pathBound, MOM_ORDERS);
+}
+
+// The longest main diagonal of the medium's extent in world space (the inverse of w2v's linear part applied to the box's edges): no
+// segment inside the medium is longer.  INFINITY where w2v is projective or singular.
+static double extent_world_diagonal(const DevScene &h) {
+    const float *w = h.w2v;
+    if (w[12] != 0.f || w[13] != 0.f || w[14] != 0.f || w[15] != 1.f) return INFINITY;
+    const double m[3][3] = {{w[0], w[1], w[2]}, {w[4], w[5], w[6]}, {w[8], w[9], w[10]}};
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    if (!std::isfinite(det) || det == 0.0) return INFINITY;
+    double inv[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {   // cofactor of (j, i) over det
+            const int a = (j + 1) % 3, b = (j + 2) % 3, c = (i + 1) % 3, d = (i + 2) % 3;
+            inv[i][j] = (m[a][c] * m[b][d] - m[a][d] * m[b][c]) / det;
+        }
+    const double e[3] = {(double)h.extHi[0] - h.extLo[0], (double)h.extHi[1] - h.extLo[1], (double)h.extHi[2] - h.extLo[2]};
+    double best = 0.0;
+    for (int s = 0; s < 4; ++s) {
+        const double v[3] = {e[0], (s & 1) ? -e[1] : e[1], (s & 2) ? -e[2] : e[2]};
+        double l2 = 0.0;
+        for (int i = 0; i < 3; ++i) { const double u = inv[i][0] * v[0] + inv[i][1] * v[1] + inv[i][2] * v[2]; l2 += u * u; }
+        best = std::max(best, sqrt(l2));
+    }
+    return best * (1.0 + 1e-6);   // the kernels measure lengths in fp32
+}
+
+int pvol_moment_scene(DevScene &h, MomentWeights *wts) {
+    h.momSigBar = 0.f;
+    memset(h.momEmit, 0, sizeof(h.momEmit)); memset(h.momDirect, 0, sizeof(h.momDirect));
+    if (wts) memset(wts, 0, sizeof(*wts));
+    if (h.volKind != PVOL_VOLUME_HOMOGENEOUS) return 0;
+    const double diag = extent_world_diagonal(h);
+    // flux and emission are attenuated over the view ray's rest (<= diag): MOM_ORDERS terms; the direct term over that plus the
+    // shadow ray's way out (<= 2 diag): one term more
+    const int terms = moment_terms(h.sigA, h.sigS, diag, MOM_ORDERS);
+    if (terms < 1 || moment_terms(h.sigA, h.sigS, 2.0 * diag, MOM_ORDERS + 1) < 1) return 0;
+    double maxDelta = 0.0;
+    h.momSigBar = moment_sig_bar(h.sigA, h.sigS, &maxDelta);
+    const float *cie[3] = {h.cieX, h.cieY, h.cieZ};
+    double emit[9] = {0}, direct[PVOL_MAX_LIGHTS][12] = {{0}};
+    for (int b = 0; b < PVOL_NBINS; ++b) {
+        const float sigT = h.sigA[b] + h.sigS[b];
+        const double d = 0.6931471805599453 * ((double)sigT - (double)h.momSigBar);
+        const double albedo = sigT != 0.f ? (double)h.sigS[b] / (double)sigT : 0.0;
+        double pw = 1.0;   // (ln2 delta_b)^n / n!
+        for (int n = 0; n <= MOM_ORDERS; ++n) {
+            for (int c = 0; c < 3; ++c) {
+                if (n < MOM_ORDERS) {
+                    if (wts) wts->w[4 * n + c][b] = (float)(cie[c][b] * albedo * pw);
+                    emit[3 * n + c] += (double)cie[c][b] * ((double)h.sigA[b] * (double)h.le[b]) * pw;
+                }
+                for (int l = 0; l < h.nLights && l < PVOL_MAX_LIGHTS; ++l)
+                    direct[l][3 * n + c] += (double)cie[c][b] * ((double)h.sigS[b] * (double)h.lights[l].intensity[b]) * pw;
+            }
+            pw *= d / (n + 1);
+        }
+    }
+    for (int i = 0; i < 9; ++i) h.momEmit[i] = (float)emit[i];
+    for (int l = 0; l < PVOL_MAX_LIGHTS; ++l) for (int i = 0; i < 12; ++i) h.momDirect[l][i] = (float)direct[l][i];
+    return terms;
+}
+
 LaunchKnobs pvol_read_knobs() {
     auto num = [](const char *name) { const char *v = getenv(name); return v ? (int64_t)atoll(v) : (int64_t)0; };
     auto real = [](const char *name) { const char *v = getenv(name); return v ? (float)atof(v) : 0.f; };
@@ -254,6 +352,7 @@ static PlanIn plan_input(const pvol_ctx *c, const BatchArgs &b) {
     in.nCU = c->nCU; in.groupWavesPerCU = c->groupWavesPerCU; in.fixWavesPerCU = c->fixWavesPerCU; in.tileWaves = c->tileWaves;
     in.nRays = b.nRays; in.nStreams = b.nStreams; in.maxRays = b.maxRaysPerStream; in.hasInit = b.initState != 0; in.transOnly = b.transOnly != 0; in.hasTile = b.tile != 0;
     in.spp = b.tile ? b.tile->spp : 0; in.specOn = b.tile && b.tile->specOn; in.hasTauOut = b.tauOut != 0;
+    in.momentTerms = (int16_t)(h.mom ? c->momentTerms : 0); in.outXYZ = b.outputKind == PVOL_OUT_XYZ; in.noMoments = c->noMoments;
     in.knobs = pvol_read_knobs();
     return in;
 }
@@ -446,7 +545,7 @@ int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
     a.scene = c->ds.get(); a.rays = b.rays; a.streams = b.streams; a.nStreams = b.nStreams; a.nRays = b.nRays; a.outputKind = b.outputKind;
     a.out = b.out; a.draws = b.draws; a.initState = b.initState; a.finalState = b.finalState; a.counters = c->dCounters.get();
     a.transmittanceOnly = b.transOnly; a.chunkCounter = c->dWords.get(); a.needSeq = c->dWords.get() + 1; a.gated = 0;
-    a.tauOut = b.tauOut; a.status = b.status; a.grpGuess = in.knobs.groupGuess;
+    a.tauOut = b.tauOut; a.status = b.status; a.grpGuess = in.knobs.groupGuess; a.moments = p.groupForm == GRP_FORM_MOMENTS;
     if (p.groupForm) {
         a.defer = pvol_buf<DeferRec>(c, PVOL_BUF_DEFER); a.deferCount = c->dWords.get() + 2;
         a.deferCap = (uint32_t)std::min<size_t>(c->buf[PVOL_BUF_DEFER].bytes / sizeof(DeferRec), 0xffffffffu);

@@ -118,7 +118,18 @@ struct DevScene {
     // per-vertex shading normals (pvol_set_triangle_normals, pvol_shading_dev.h): [triangles][9] in the scene's ORIGINAL triangle order,
     // world space, not normalised; nine zeros = this triangle has none.  0 = the scene has none.
     const float *triN;
+    // XYZ moments of the volume map (pvol_map_host.hip): per photon in slot order MOM_ROW floats, entry 4 n + c =
+    // sum_b cie_c[b] albedo_b (ln2 delta_b)^n / n! alpha[b] for order n < MOM_ORDERS and channel c (X, Y, Z), the rest zero; delta_b =
+    // sigma_t_b - momSigBar.  0 = the map has none.  The emission and the direct term's coefficients of the same expansion, per order
+    // and channel: momEmit[3 n + c] = sum_b cie_c[b] (sigma_a Le)_b (ln2 delta_b)^n / n!, momDirect[light][3 n + c] the same over sigma_s_b I_b
+    // (one order more: its path is the view ray's plus the shadow ray's)
+    const float *mom;
+    float momSigBar;
+    float momEmit[9];
+    float momDirect[PVOL_MAX_LIGHTS][12];
 };
+#define MOM_ROW 16
+#define MOM_ORDERS 3
 
 // One lookup li_group_kernel hands to li_fixup_kernel (pvol_group_dev.h)
 struct DeferRec {

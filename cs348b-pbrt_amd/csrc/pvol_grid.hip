@@ -100,6 +100,35 @@ extern "C" hipError_t pvol_grid_occupancy(const uint32_t *cellStart, uint32_t nc
     return e;
 }
 
+// The volume map's XYZ moments (pvol_dev.h DevScene::mom): thread 4 j + n writes entries 4 n .. 4 n + 3 of photon j's row, the three
+// channels of order n from the sorted alpha row and the weights w[4 n + c][b]; n = 3 writes the row's zero tail.
+__global__ void moment_rows_kernel(MomentWeights W, const float4 *alpha4, float4 *mom4, uint32_t n) {
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = gid >> 2, ord = gid & 3u;
+    if (j >= n) return;
+    float s[3] = {0.f, 0.f, 0.f};
+    if (ord < MOM_ORDERS) {
+        for (int q = 0; q < 8; ++q) {
+            const float4 a = alpha4[(size_t)j * 8 + q];
+            const float av[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s[c] = __builtin_fmaf(W.w[4 * ord + c][4 * q + cc], av[cc], s[c]);
+        }
+    }
+    mom4[(size_t)j * 4 + ord] = make_float4(s[0], s[1], s[2], 0.f);
+}
+extern "C" hipError_t pvol_fill_moments(const MomentWeights *w, const float4 *alpha4, float *mom, uint32_t n, hipStream_t stream) {
+    static_assert(MOM_ROW == 16 && MOM_ORDERS == 3, "four float4 per row: one per order and the zero tail");
+    if (!n) return hipSuccess;
+    const unsigned long long threads = (unsigned long long)n * 4ull;
+    hipLaunchKernelGGL(moment_rows_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, *w, alpha4, reinterpret_cast<float4 *>(mom), n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    return e;
+}
+
 // Runs the whole build on `stream`.  All output buffers are preallocated by the caller:
 // pos4[n], alpha4[8n], wi4[n], cellStart[ncells+1], and with args->sub == 4 subStart[64 ncells + 1].  Returns a hipError_t.
 extern "C" hipError_t pvol_build_grid(const GridBuildArgs *args, float4 *pos4, float4 *alpha4, float4 *wi4,

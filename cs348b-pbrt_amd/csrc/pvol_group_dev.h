@@ -302,8 +302,17 @@ __device__ __forceinline__ uint32_t nib_sum(uint32_t w) {   // sum of the eight 
     return (t * 0x01010101u) >> 24;
 }
 
-template <bool STATS, bool SPECTRAL, bool REPLAY, bool GRID>
+// OUT: what is summed over a lookup's members and what a ray's result is -- GRP_OUT_XYZ (0, `false`) 30 bins projected onto X, Y, Z step by
+// step, GRP_OUT_SPECTRAL (1, `true`) 30 bins, GRP_OUT_MOMENTS XYZ from the map's moment rows (DevScene::mom): for a
+// medium whose sigma_t is nearly grey, exp2(sigma_t_b kappa) = exp2(sigBar kappa) sum_n (ln2 delta_b kappa)^n / n! truncated below
+// rounding (pvol_moment_gate), so X = sum_b cieX_b t_b needs per photon only MOM_ORDERS x 3 sums over the bins, made once per map.
+#define GRP_OUT_XYZ 0
+#define GRP_OUT_SPECTRAL 1
+#define GRP_OUT_MOMENTS 2
+template <bool STATS, int OUT, bool REPLAY, bool GRID>
 __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
+    constexpr bool SPECTRAL = OUT == GRP_OUT_SPECTRAL, MOMENTS = OUT == GRP_OUT_MOMENTS;
+    static_assert(!MOMENTS || (!REPLAY && !GRID), "the moment form: one light's coefficients, a homogeneous medium");
     extern __shared__ __align__(16) unsigned char lds[];
     const DevScene &S = *A.scene;
     const int lane = threadIdx.x;
@@ -548,9 +557,14 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                 // fmaf chain): rows = bins, columns = rays.  Lane l holds column (ray) l & 31 of CA (rays 0..31) and of CB (rays 32..63),
                 // register i = bin 8 (i >> 2) + (i & 3) + 4 (l >> 5).  After the attempts 16 v_permlane32_swap leave every lane its OWN
                 // ray's 32 bins: CA[i] = bin 8 (i >> 2) + (i & 3), CB[i] = the same + 4.
+                // MOMENTS: four 16 x 16 accumulators (v_mfma_f32_16x16x4_f32, four slots per instruction): rows = moment entries, columns =
+                // the rays 16 g .. 16 g + 15 of CM[g].  Lane l holds column l & 15, register r = entry 4 (l >> 4) + r = order l >> 4, channel r.
                 f32x16 CA, CB;
+                nf4 CM[4];
 #pragma unroll
                 for (int b = 0; b < 16; ++b) { CA[b] = 0.f; CB[b] = 0.f; }
+#pragma unroll
+                for (int g = 0; g < 4; ++g) CM[g] = nf4{0.f, 0.f, 0.f, 0.f};
                 bool anyFlux = false;   // wave-uniform
                 float rk = 0.f;
                 int nFoundLane = k;
@@ -764,6 +778,111 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                             const int half = lane >> 5, binL = lane & 31;
                             typedef const __attribute__((address_space(1))) float gfloat;   // global_load, not flat_load
                             gfloat *alphaF = (gfloat *)(S.alpha4);
+                            if (MOMENTS) {
+                            // The same sum over the moment rows: A = rows (lane l: entry l & 15 of the slot of its quarter-wave: one 64-B row
+                            // per quarter and load), B = member bits of ray 16 g + (l & 15) for that slot (the other quarters' words of a
+                            // ray come from three swaps per 32 slots).  Four slots per instruction, rays 16 g .. 16 g + 15 into CM[g].
+                            const int qtr = lane >> 4, rowL = lane & 15;
+                            gfloat *momF = (gfloat *)(S.mom);
+                            // every lane: the value of lanes (l & 15), 16 + (l & 15), 32 + (l & 15), 48 + (l & 15)
+                            auto quarters = [](uint32_t v, uint32_t (&w)[4]) {
+                                auto h2 = __builtin_amdgcn_permlane32_swap(v, v, false, false);       // rows r0 r1 r0 r1 | r2 r3 r2 r3
+                                auto lo = __builtin_amdgcn_permlane16_swap(h2[0], h2[0], false, false);
+                                auto hi = __builtin_amdgcn_permlane16_swap(h2[1], h2[1], false, false);
+                                w[0] = lo[0]; w[1] = lo[1]; w[2] = hi[0]; w[3] = hi[1];
+                            };
+                            if (GRP_CORE_MIN < GRP_CAP) {
+                                const bool anyOk = __ballot(ok) != 0ull;
+                                int nCore = 0;
+                                uint32_t coreW[GRP_NW];
+#pragma unroll
+                                for (int wd = 0; wd < GRP_NW; ++wd) {
+                                    coreW[wd] = 0u;
+                                    if (wd * 32 >= Mb || !anyOk) continue;
+                                    coreW[wd] = (uint32_t)__builtin_amdgcn_readfirstlane((int)~wave_or(ok ? ~mem[wd] : 0u));
+                                    nCore += __builtin_popcount(coreW[wd]);
+                                }
+                                if (nCore >= GRP_CORE_MIN) {
+                                    // slots that are members for EVERY served lane: their rows are summed once (four rows per load, lane = entry,
+                                    // row parity) and the sum enters as one more "row" whose member bits are the served lanes
+                                    uint32_t *clist = reinterpret_cast<uint32_t *>(L.miniD);
+                                    int basePos = 0;
+#pragma unroll
+                                    for (int r2 = 0; r2 < GRP_NW / 2; ++r2) {
+                                        if (r2 * 64 >= Mb) continue;
+                                        const unsigned long long c64 = (unsigned long long)coreW[2 * r2] | ((unsigned long long)coreW[2 * r2 + 1] << 32);
+                                        if ((c64 >> lane) & 1ull) clist[basePos + (int)lanes_below(c64, lane)] = __float_as_uint(bI[r2 * 64 + lane]);
+                                        basePos += __popcll(c64);
+                                    }
+                                    __syncthreads();
+                                    float cs = 0.f;
+                                    for (int c0 = 0; c0 < nCore; c0 += 32) {   // up to 32 rows in flight per trip
+                                        float v[8];
+#pragma unroll
+                                        for (int q2 = 0; q2 < 8; ++q2) {
+                                            const int at = c0 + 4 * q2 + qtr;
+                                            const bool on = at < nCore;
+                                            const uint32_t idx = clist[on ? at : 0];
+                                            const float w = momF[(size_t)idx * MOM_ROW + rowL];
+                                            v[q2] = on ? w : 0.f;
+                                        }
+                                        cs += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+                                    }
+                                    { auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(cs), __float_as_uint(cs), false, false); cs = __uint_as_float(r[0]) + __uint_as_float(r[1]); }
+                                    { auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(cs), __float_as_uint(cs), false, false); cs = __uint_as_float(r[0]) + __uint_as_float(r[1]); }
+                                    uint32_t okQ[4];
+                                    quarters(ok ? 1u : 0u, okQ);
+#pragma unroll
+                                    for (int g = 0; g < 4; ++g)   // the sum sits in every quarter: only slot 0 of the four counts
+                                        CM[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs, qtr ? 0.f : (float)okQ[g], CM[g], 0, 0, 0);
+                                    anyFlux = true;
+#pragma unroll
+                                    for (int wd = 0; wd < GRP_NW; ++wd) mem[wd] &= ~coreW[wd];
+                                    __syncthreads();
+                                }
+                            }
+#pragma unroll
+                            for (int wd = 0; wd < GRP_NW; ++wd) {
+                                if (wd * 32 >= Mb) continue;
+                                const uint32_t mine = ok ? mem[wd] : 0u;
+                                uint32_t any = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave_or(mine)));
+                                if (!any) continue;
+                                anyFlux = true;
+                                uint32_t W[4];   // every lane: the word of ray 16 g + (l & 15)
+                                quarters(mine, W);
+                                while (any) {   // four slot quartets per trip: their rows are requested before the first is used
+                                    uint32_t sel[4], wid[4];
+                                    float av[4];
+                                    bool on[4];
+#pragma unroll
+                                    for (int t = 0; t < 4; ++t) {
+                                        on[t] = any != 0u;
+                                        int bq[4], cnt = 0;
+#pragma unroll
+                                        for (int u = 0; u < 4; ++u) {   // 0 & anything stays 0: a quartet may hold fewer than four slots
+                                            const bool more = any != 0u;
+                                            bq[u] = more ? __builtin_ctz(any) : (u ? bq[0] : 0);
+                                            cnt += more ? 1 : 0;
+                                            any &= any - 1u;
+                                        }
+                                        sel[t] = (uint32_t)(qtr == 0 ? bq[0] : (qtr == 1 ? bq[1] : (qtr == 2 ? bq[2] : bq[3])));
+                                        wid[t] = qtr < cnt ? 1u : 0u;   // a quarter-wave without a slot contributes nothing
+                                        av[t] = 0.f;
+                                        if (on[t]) {   // wave-uniform
+                                            const uint32_t idx = __float_as_uint(bI[wd * 32 + sel[t]]);
+                                            av[t] = momF[(size_t)idx * MOM_ROW + rowL];
+                                        }
+                                    }
+#pragma unroll
+                                    for (int t = 0; t < 4; ++t) {
+                                        if (!on[t]) continue;   // wave-uniform
+#pragma unroll
+                                        for (int g = 0; g < 4; ++g)
+                                            CM[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], (float)__builtin_amdgcn_ubfe(W[g], sel[t], wid[t]), CM[g], 0, 0, 0);
+                                    }
+                                }
+                            }
+                            } else {
                             if (GRP_CORE_MIN < GRP_CAP) {
                                 const bool anyOk = __ballot(ok) != 0ull;
                                 int nCore = 0;
@@ -852,6 +971,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                     }
                                 }
                             }
+                            }   // !MOMENTS
                             if (ok) { done = true; rk = rkC; if (shortSet) nFoundLane = inRange; }
                             if (STATS) { wc.kept += (unsigned long long)k * __popcll(__ballot(ok)); wc.cyFlux += stamp() - tp3; }
                         }
@@ -905,14 +1025,50 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                 float ldScale = 0.f;
                 if (lit) ldScale = (distant ? 1.f : fallReg * __builtin_amdgcn_rcpf(d2Reg)) * ph * float(nLights);
                 const float kExit = -1.442695041f * exitLen;   // exp(-x) = exp2(-x log2 e)
-                if (anyFlux) {   // every lane takes its own ray's column: CA <- bins 8g + c, CB <- bins 8g + 4 + c
+                float Sm[MOM_ORDERS][3];   // MOMENTS: this lane's own sums, [order][channel]
+#pragma unroll
+                for (int n = 0; n < MOM_ORDERS; ++n) { Sm[n][0] = 0.f; Sm[n][1] = 0.f; Sm[n][2] = 0.f; }
+                if (MOMENTS && anyFlux) {
+                    // every lane takes its own ray's column: channel c of order n sits in register c of quarter-wave n of CM[this lane's
+                    // quarter] -- a 4 x 4 transposition of quarter-waves per channel, of which order 3 (the rows' zero tail) is not taken
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(CM[0][c]), __float_as_uint(CM[2][c]), false, false);
+                        auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(CM[1][c]), __float_as_uint(CM[3][c]), false, false);
+                        auto lo = __builtin_amdgcn_permlane16_swap(a[0], b[0], false, false);
+                        auto hi = __builtin_amdgcn_permlane16_swap(a[1], b[1], false, false);
+                        Sm[0][c] = __uint_as_float(lo[0]); Sm[1][c] = __uint_as_float(lo[1]); Sm[2][c] = __uint_as_float(hi[0]);
+                    }
+                }
+                if (!MOMENTS && anyFlux) {   // every lane takes its own ray's column: CA <- bins 8g + c, CB <- bins 8g + 4 + c
 #pragma unroll
                     for (int b = 0; b < 16; ++b) {
                         auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(CA[b]), __float_as_uint(CB[b]), false, false);
                         CA[b] = __uint_as_float(r[0]); CB[b] = __uint_as_float(r[1]);
                     }
                 }
-                if (act) {
+                if (MOMENTS && act) {
+                    // X += E [ stepE emit_X(kRem) + stepD liiU flux_X(kRem) ] + E_d stepD ldScale direct_X(kRem + kExit), Y and Z alike:
+                    // E = exp2(sigBar kRem), E_d = exp2(sigBar (kRem + kExit)), the polynomials in Horner form over the orders
+                    const float liiU = useLii ? liiScale : 0.f;
+                    const float kDir = kRem + kExit;
+                    const float E = __builtin_amdgcn_exp2f(S.momSigBar * kRem), wD = __builtin_amdgcn_exp2f(S.momSigBar * kDir) * (stepD * ldScale);
+                    const float wF = stepD * liiU;
+                    float acc3[3] = {accX, accY, accZ};
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float flux = __builtin_fmaf(__builtin_fmaf(Sm[2][c], kRem, Sm[1][c]), kRem, Sm[0][c]);
+                        const float emit = __builtin_fmaf(__builtin_fmaf(S.momEmit[6 + c], kRem, S.momEmit[3 + c]), kRem, S.momEmit[c]);
+                        const float *md = S.momDirect[0];
+                        const float dir = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(md[9 + c], kDir, md[6 + c]), kDir, md[3 + c]), kDir, md[c]);
+                        acc3[c] = __builtin_fmaf(E, __builtin_fmaf(wF, flux, stepE * emit), __builtin_fmaf(wD, dir, acc3[c]));
+                    }
+                    accX = acc3[0]; accY = acc3[1]; accZ = acc3[2];
+                    pPrev = p;
+                    inPrev = inP;
+                    lenLast = lenStep;
+                }
+                if (!MOMENTS && act) {
                     // per bin:  t = exp2(sT kRem) [ (sigA Le) stepE + (sigS stepD) (Ld + (albedo / sigS) acc liiScale) ],  fused multiply-adds
                     // (values only: no decision hangs on them)
                     const float liiU = useLii ? liiScale : 0.f;
@@ -1103,7 +1259,12 @@ extern "C" hipError_t pvol_launch_li_group(const LiArgs *args, size_t ldsBytes, 
 #define FIX_LAUNCH(ST, SP) do { if (fixGroup) hipLaunchKernelGGL((li_fixup_group_kernel<SP>), fgrid, block, fixGrpLds, stream, *args);   /* compact runs */ \
                                 if (big) hipLaunchKernelGGL((li_fixup_kernel<ST, SP, 12>), fgrid, block, fixLds, stream, *args); \
                                 else hipLaunchKernelGGL((li_fixup_kernel<ST, SP, 4>), fgrid, block, fixLds, stream, *args); } while (0)
-    if (replay == 0) {
+    if (replay == 0 && args->moments && !spectral && (!stats || GRP_PHASE_DIAG)) {   // the plan's decision (plan_path): XYZ from the moment rows
+#if GRP_PHASE_DIAG
+        if (stats) { GRP_LAUNCH(true, GRP_OUT_MOMENTS, false, false); FIX_LAUNCH(true, false); } else
+#endif
+        { GRP_LAUNCH(false, GRP_OUT_MOMENTS, false, false); FIX_LAUNCH(false, false); }
+    } else if (replay == 0) {
         if (stats) { if (spectral) { GRP_LAUNCH(true, true, false, false); FIX_LAUNCH(true, true); } else { GRP_LAUNCH(true, false, false, false); FIX_LAUNCH(true, false); } }
         else { if (spectral) { GRP_LAUNCH(false, true, false, false); FIX_LAUNCH(false, true); } else { GRP_LAUNCH(false, false, false, false); FIX_LAUNCH(false, false); } }
     } else if (replay == 1) {

@@ -129,6 +129,7 @@ extern "C" bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream);
 struct PVOL_LOCAL PhotonGrid {
     DevPtr<float4> pos4, alpha4, wi4;
     DevPtr<uint32_t> cellStart, subStart;   // subStart: second level of a clumpy map, else empty
+    DevPtr<float> mom;                      // volume map under a scene that passes pvol_moment_gate: MOM_ROW floats per photon, else empty
     uint32_t n = 0;
     float gridLo[3] = {0.f, 0.f, 0.f}, cellSize = 0.f, invCell = 0.f;
     int32_t gdim[3] = {0, 0, 0};
@@ -188,6 +189,8 @@ struct pvol_ctx {
     int groupWavesPerCU = 12; // resident li_group_kernel waves per CU (LDS plan: 8); PVOL_GROUP_WAVES overrides
     bool noGroup = false;       // PVOL_NO_GROUP=1: keep li_par_kernel (one wave per ray) where li_group_kernel (one ray per lane) would run
     bool forceSeq = false;      // PVOL_FORCE_SEQ=1: always take the stream-sequential kernel (testing)
+    bool noMoments = false;     // PVOL_NO_MOMENTS=1: li_group_kernel keeps summing 30 bins where it would sum XYZ moments
+    int momentTerms = 0;        // pvol_moment_scene's decision for the scene set last (0: no moment form, volMap.mom stays empty)
     bool statsOn = false;
     // kernel timing (HIP events on the launch stream)
     std::vector<std::pair<hipEvent_t, hipEvent_t> > pending;
@@ -286,13 +289,17 @@ struct PlanIn {
     int32_t roulette, distant;   // a march step can reach the Russian roulette (roulette_possible); the first light is a distant one
     int32_t forceSeq, noGroup, noLite, statsOn, nCU, groupWavesPerCU, fixWavesPerCU, tileWaves;   // context flags, device shape
     uint32_t nRays, nStreams, maxRays; int32_t hasInit, transOnly, hasTile; uint32_t spp; int32_t specOn, hasTauOut;   // the batch
+    // XYZ moments, in what was padding: the scene's gate (pvol_moment_gate: Taylor terms, 0 = keep the 30 bins; the
+    // volume map then carries its moment rows), the batch's output is PVOL_OUT_XYZ, PVOL_NO_MOMENTS=1
+    int16_t momentTerms; int8_t outXYZ, noMoments;
     LaunchKnobs knobs;
 };
 enum { PVOL_PATH_PAR, PVOL_PATH_SLICED, PVOL_PATH_SEQ };
 enum { PVOL_TILE_NONE, PVOL_TILE_COUNT, PVOL_TILE_GRID_COUNT, PVOL_TILE_FUSED };
 struct BatchPlan {
     int32_t rc, path, tile;
-    int32_t groupForm;        // li_group_kernel's form: 0 none, 1 homogeneous (PAR: no records), 2 density region (VolumeGrid, exponential)
+    int32_t groupForm;        // li_group_kernel's form: 0 none, 1 homogeneous (PAR: no records), 2 density region (VolumeGrid, exponential),
+                              // 3 form 1 of the PAR path summing XYZ moments instead of 30 bins (GRP_FORM_MOMENTS)
     int32_t fixGroup, liteResolve;
     int32_t resolve;          // SLICED: the slice runs its own resolve pass (no FUSED pre-pass wrote the records)
     uint32_t recStride, sliceM, nSlices, nWaves, gWaves, fixWaves; int32_t tileWavesPerTask;
@@ -303,6 +310,17 @@ static_assert(sizeof(PlanIn) == 152 && sizeof(BatchPlan) == 136, "tests/test_lau
 extern "C" size_t pvol_rec_stride(int maxSteps, bool grid);   // bytes of one record slot
 extern "C" BatchPlan plan_path(const PlanIn &in);             // everything that needs no maxRays
 extern "C" void plan_size(const PlanIn &in, BatchPlan &p);    // the rest, once in.maxRays is known
+#define GRP_FORM_MOMENTS 3
+// The gate of the moment form, a pure function (pvol_api.hip): the number N in 1..3 of Taylor terms of exp(-delta_b L) whose truncation
+// bound x^N / N! e^x, x = max_b |delta_b| pathBound, is below 2^-25, or 0 = none is (keep the 30-bin path).  sigA / sigS: 30 values;
+// delta_b = sigma_t_b - the midrange of sigma_t; pathBound: a bound on the optical path length of a ray inside the medium.
+extern "C" int pvol_moment_gate(const float *sigA, const float *sigS, double pathBound);
+// What the moment form reads besides the map: the gate's decision for the scene `h` (its extent's world-space diagonal bounds a ray's
+// path, twice that the direct term's, which carries one order more), h.momSigBar / momEmit / momDirect, and the rows of the
+// map's fill kernel (MomentWeights::w[4 n + c][b], pvol_grid.hip).  Pure; returns the terms (0: h's moment fields stay zero).
+struct MomentWeights { float w[12][32]; };
+extern "C" int pvol_moment_scene(DevScene &h, MomentWeights *w);
+extern "C" hipError_t pvol_fill_moments(const MomentWeights *w, const float4 *alpha4, float *mom, uint32_t n, hipStream_t stream);
 
 extern "C" {
 void pvol_phase_mark(pvol_ctx *c, hipStream_t stream, int id);
@@ -394,6 +412,8 @@ PVOL_LOCAL int pvol_scene_image(const pvol_params *params, const pvol_scene *s, 
 
 // writes a map (an empty one included) into the photon-map fields of the host scene (pvol_map_host.hip)
 PVOL_LOCAL void pvol_map_to_scene(const PhotonGrid &G, DevScene &h);
+// the volume map's moment rows under the scene h, with h's moment constants and the gate's decision (pvol_map_host.hip)
+PVOL_LOCAL int pvol_map_moments(const PhotonGrid &G, DevScene &h, DevPtr<float> &mom, int *terms);
 
 // ImageFilm's crop window behind the *_window entry points: a NULL window is the whole frame (crop 0 1 0 1), which is what the
 // entry points without a window pass

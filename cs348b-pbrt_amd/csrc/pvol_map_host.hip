@@ -58,6 +58,20 @@ void pvol_map_to_scene(const PhotonGrid &G, DevScene &h) {
     h.nPhotons = G.n; h.cellSize = G.cellSize; h.invCell = G.invCell;
     for (int a = 0; a < 3; ++a) { h.gridLo[a] = G.gridLo[a]; h.gdim[a] = G.gdim[a]; }
     h.cellStart = G.cellStart.get(); h.subStart = G.subStart.get(); h.pos4 = G.pos4.get(); h.alpha4 = G.alpha4.get(); h.wi4 = G.wi4.get();
+    h.mom = G.mom.get();
+}
+
+// The moment rows of the volume map G under the scene h (DevScene::mom): h's moment constants and the gate's decision (*terms) are
+// set either way; `mom` gets the rows where the gate passes and the map holds photons, and is emptied otherwise.  Runs where the
+// map is built and where pvol_set_scene commits a scene over a kept map -- never inside a render or Li call.
+int pvol_map_moments(const PhotonGrid &G, DevScene &h, DevPtr<float> &mom, int *terms) {
+    MomentWeights w;
+    *terms = pvol_moment_scene(h, &w);
+    mom.reset();
+    if (*terms < 1 || !G.n) return PVOL_OK;
+    if (!mom.alloc((size_t)MOM_ROW * G.n)) return PVOL_E_NO_MEMORY;
+    if (!ok(pvol_fill_moments(&w, G.alpha4.get(), mom.get(), G.n, 0))) { mom.reset(); return PVOL_E_NO_DEVICE; }
+    return PVOL_OK;
 }
 static void map_to_surface(const PhotonGrid &G, uint32_t nPaths, DevSurfMap &sf) {
     sf.nPhotons = G.n; sf.nPaths = (int32_t)nPaths; sf.cellSize = G.cellSize; sf.invCell = G.invCell;
@@ -148,6 +162,8 @@ int pvol_finish_map(pvol_ctx *c, uint32_t n, const float *hostPositions) {
             return PVOL_E_NO_DEVICE;
         }
     }
+    rc = pvol_map_moments(G, h, G.mom, &c->momentTerms);
+    if (rc != PVOL_OK) { pvol_free_photons(c); pvol_push_scene(c); return rc; }
     pvol_map_to_scene(G, h);
     return pvol_push_scene(c);
 }

@@ -323,6 +323,11 @@ extern "C" int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
     h.shootScene = c->dsh.get();
     pvol_map_to_scene(c->volMap, h);   // the volume map stays; the surface integrator belongs to the scene it was enabled on (h.surf is zero)
     h.ringMax = c->hs.ringMax; h.rkEstimate = c->hs.rkEstimate;
+    // the kept map's moment rows are a function of this scene's spectra: built aside, committed with the scene
+    DevPtr<float> mom;
+    int momTerms = 0;
+    if ((rc = pvol_map_moments(c->volMap, h, mom, &momTerms)) != PVOL_OK) return rc;
+    h.mom = mom.get();
     if (!ok(hipDeviceSynchronize()) || !ok(hipMemcpy(c->dsh.get(), &img.shoot, sizeof(img.shoot), hipMemcpyHostToDevice)) ||
         !ok(hipMemcpy(c->ds.get(), &h, sizeof(DevScene), hipMemcpyHostToDevice))) {
         pvol_push_scene(c);   // best effort: put the device copy of the previous scene back
@@ -332,6 +337,7 @@ extern "C" int pvol_set_scene(pvol_ctx *c, const pvol_scene *s) {
     c->dDensity = std::move(density);
     c->dBvhNodes = std::move(nodes); c->dBvhTris = std::move(tris);
     c->bvhBuildMs = bvhMs;
+    c->volMap.mom = std::move(mom); c->momentTerms = momTerms;
     c->triMatHost.swap(img.primMat);
     c->maxDensity = img.maxDensity;
     pvol_free_caustic_map(c);
