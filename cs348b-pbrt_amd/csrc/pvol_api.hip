@@ -71,6 +71,7 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     { const char *ng = getenv("PVOL_NO_GROUP"); c->noGroup = ng && ng[0] == '1'; }
     { const char *nl = getenv("PVOL_NO_LITE"); c->noLite = nl && nl[0] == '1'; }
     { const char *nm = getenv("PVOL_NO_MOMENTS"); c->noMoments = nm && nm[0] == '1'; }
+    { const char *tg = getenv("PVOL_TILE_GENERAL"); c->tileGeneral = tg && tg[0] == '1'; }
     { const char *gw = getenv("PVOL_GROUP_WAVES"); if (gw) c->groupWavesPerCU = std::max(1, atoi(gw)); }
     { const char *tw = getenv("PVOL_TILE_WAVES"); if (tw) c->tileWaves = std::max(0, atoi(tw)); }
     // li_fixup_kernel / li_fixup_group_kernel waves per CU (C3, 8 spp frame: 16.3 s at 8, 13.9 s at 16)
@@ -167,6 +168,15 @@ BatchPlan plan_path(const PlanIn &in) {
     return p;
 }
 
+// The form of the COUNT-mode tile pre-pass (pvol_host.h): PLAIN where every run-time test of the general kernels is decided by the scene.
+// No light at all keeps the general form (its early return needs no rows); a black light is still a distant light and takes PLAIN.
+int pvol_tile_plain_gate(const TilePlainIn *in) {
+    const bool extent = in->volKind == PVOL_VOLUME_HOMOGENEOUS || in->volKind == PVOL_VOLUME_RAINBOW;   // Inside() of a box: no density region, no "none"
+    return in->tile == PVOL_TILE_COUNT && !in->tileGeneral && extent && in->nLights > 0 &&
+           in->light0Kind == PVOL_LIGHT_DISTANT && !in->hasBvh && in->nSpheres == 0 && in->nTris >= 0 && in->nTris <= PVOL_MAX_TRIS &&
+           !in->surfOn && !in->specLink;
+}
+
 // Waves per render task of the COUNT-mode tile pre-pass.  A task is a serial chain (one MT19937 stream); with many tasks per CU
 // the chip is kept busy by running them side by side (one wave each), with few -- one rank's share of a multi-GPU frame -- the
 // draw count of every pixel is spread over several waves instead (tile_mw_kernel).  PVOL_TILE_WAVES overrides.
@@ -179,6 +189,15 @@ static int tile_waves_per_task(const PlanIn &in) {
     // 4 per CU 77 ms with two waves (134 before), 99 with four; 2 per CU 56.5 ms with four waves, 80.8 with eight at 128 VGPRs, 85.9 at 256)
     // 8 per CU: 131.5 ms with two waves, 146.9 with one; 16 per CU: 174.7 with one, 190.7 with two
     return perCU >= 12.0 ? 1 : (perCU >= 3.0 ? 2 : 4);
+}
+// The same for the PLAIN form (pvol_tile_plain_gate), whose two- and four-wave kernels take 152 VGPRs and spill nothing: three waves per SIMD
+// instead of two, so six two-wave tasks of a CU are resident instead of four.  Measured on the C2 frame (bench.py --emulate-ranks 2,4,8 by
+// PVOL_TILE_WAVES, profiles/tile_plain_emulate.txt), tile pre-pass in ms with one / two / four waves: 16 tasks per CU 158-163 / 139-141 / 194,
+// 8 per CU 137 / 87-88 / 119, 4 per CU 125-131 / 78-85 / 65, 2 per CU 121 / 74-76 / 55.  More than 16 per CU is not measured and keeps one wave.
+static int tile_waves_per_task_plain(uint32_t nStreams, int nCU, int tileWaves) {
+    if (tileWaves > 0) return tileWaves;
+    const double perCU = (double)nStreams / (double)std::max(1, nCU);
+    return perCU > 16.0 ? 1 : (perCU >= 6.0 ? 2 : 4);
 }
 
 void plan_size(const PlanIn &in, BatchPlan &p) {
@@ -455,7 +474,16 @@ static int spec_finish(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, cons
 // sampler + camera pre-pass that COUNTs Li()'s draws for the whole batch, once (`t`: the batch as one slice)
 static int run_tile_count(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, const LiArgs &t, const TileArgs *tile) {
     pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
-    return ok(pvol_launchers(c->hs.volKind).tile(&t, tile, false, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, &c->lastTileKernel)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    const DevScene &h = c->hs;
+    TilePlainIn g = {};
+    g.tile = p.tile; g.volKind = h.volKind; g.nLights = h.nLights; g.light0Kind = h.nLights > 0 ? h.lights[0].kind : -1;
+    g.hasBvh = h.bvhNodes != 0; g.nSpheres = h.nSpheres; g.nTris = h.nTris; g.surfOn = h.surf.enabled != 0;
+    g.specLink = tile->specOn || tile->specLink != 0; g.tileGeneral = c->tileGeneral;
+    const bool plain = pvol_tile_plain_gate(&g) != 0;
+    c->lastTileForm = plain ? "plain" : "general";
+    // the plan's wave count is the general form's; PLAIN has its own optimum (the LDS plan, p.ldsTile, is the same for every wave count)
+    const int waves = plain ? tile_waves_per_task_plain(b.nStreams, c->nCU, c->tileWaves) : p.tileWavesPerTask;
+    return ok(pvol_launchers(h.volKind).tile(&t, tile, false, p.ldsTile, h.candCap, b.stream, waves, plain, &c->lastTileKernel)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 static int run_par(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a) {
     const RegionLaunchers &K = pvol_launchers(c->hs.volKind);
@@ -485,7 +513,8 @@ static int run_sliced(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArg
         if (p.specCap && spec_pool_reset(c, tile, p.specCap, b.stream) != PVOL_OK) return PVOL_E_NO_DEVICE;
         if (p.tile == PVOL_TILE_FUSED) {
             pvol_phase_mark(c, b.stream, PVOL_PHASE_TILE);
-            if (!ok(K.tile(&a, tile, true, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, &c->lastTileKernel))) return PVOL_E_NO_DEVICE;
+            c->lastTileForm = "general";
+            if (!ok(K.tile(&a, tile, true, p.ldsTile, c->hs.candCap, b.stream, p.tileWavesPerTask, false, &c->lastTileKernel))) return PVOL_E_NO_DEVICE;
         }
         pvol_phase_mark(c, b.stream, PVOL_PHASE_MARCH);   // incl. the RNG-only resolve pass of a slice where there is one
         if (!ok(K.liSlice(&a, p.ldsResolve, p.ldsPar, c->hs.candCap, c->statsOn, p.nWaves, b.stream, p.resolve != 0, p.groupForm, p.ldsGroup,
@@ -711,6 +740,7 @@ int pvol_get_stats(pvol_ctx *c, pvol_stats *out, int reset) {
 
 const char *pvol_march_kernel_name(pvol_ctx *c) { return c ? c->lastKernel : ""; }
 const char *pvol_tile_kernel_name(pvol_ctx *c) { return c ? c->lastTileKernel : ""; }
+const char *pvol_tile_form_name(pvol_ctx *c) { return c ? c->lastTileForm : ""; }
 
 int pvol_enable_phase_timing(pvol_ctx *c, int on) {
     if (!c) return PVOL_E_INVALID;

@@ -64,7 +64,7 @@ extern "C" hipError_t pvol_launch_li_replay(const LiArgs *args, size_t ldsReplay
 extern "C" hipError_t pvol_launch_surface(const SurfArgs *a, uint32_t nWaves, hipStream_t stream);
 extern "C" size_t pvol_tile_lds_bytes(int maxSteps, uint32_t spp, bool fused, int nTris, bool shadowRows);
 extern "C" hipError_t pvol_launch_tile(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask,
-                                       const char **form);
+                                       bool plain, const char **form);
 extern "C" hipError_t pvol_launch_li_par(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, hipStream_t stream);
 // The launchers of one compilation of the marching kernels: VolumeGridDensity (and every medium that is no density region) or, from
 // pvol_march_exp.hip, ExponentialDensity (pvol_region_exp.h).  The host asks pvol_launchers(kind) wherever a launched kernel may
@@ -89,7 +89,7 @@ extern "C" hipError_t pvol_launch_li_replay_exp(const LiArgs *args, size_t ldsRe
 extern "C" hipError_t pvol_launch_li_par_exp(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, hipStream_t stream);
 extern "C" hipError_t pvol_launch_surface_exp(const SurfArgs *a, uint32_t nWaves, hipStream_t stream);
 extern "C" hipError_t pvol_launch_tile_exp(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream,
-                                           int wavesPerTask, const char **form);
+                                           int wavesPerTask, bool plain, const char **form);
 static inline const RegionLaunchers &pvol_launchers(int volKind) {
     static const RegionLaunchers base = {pvol_launch_li_seq, pvol_launch_li_slice, pvol_launch_li_group, pvol_launch_li_replay, pvol_launch_li_par,
                                          pvol_launch_surface, pvol_launch_tile};
@@ -185,6 +185,8 @@ struct pvol_ctx {
     bool noLite = false;      // PVOL_NO_LITE=1: keep the geometry inside the sequential resolve pass (testing)
     const char *lastKernel = "";
     const char *lastTileKernel = "";   // pvol_tile_kernel_name: set by the launch itself
+    const char *lastTileForm = "";     // pvol_tile_form_name: "plain" / "general", the form of the last tile launch (pvol_tile_plain_gate)
+    bool tileGeneral = false;   // PVOL_TILE_GENERAL=1: the COUNT-mode tile pre-pass keeps its general form where the plan would take PLAIN
     int fixWavesPerCU = 16;   // li_fixup_kernel waves per CU; PVOL_FIX_WAVES overrides
     int groupWavesPerCU = 12; // resident li_group_kernel waves per CU (LDS plan: 8); PVOL_GROUP_WAVES overrides
     bool noGroup = false;       // PVOL_NO_GROUP=1: keep li_par_kernel (one wave per ray) where li_group_kernel (one ray per lane) would run
@@ -311,6 +313,20 @@ extern "C" size_t pvol_rec_stride(int maxSteps, bool grid);   // bytes of one re
 extern "C" BatchPlan plan_path(const PlanIn &in);             // everything that needs no maxRays
 extern "C" void plan_size(const PlanIn &in, BatchPlan &p);    // the rest, once in.maxRays is known
 #define GRP_FORM_MOMENTS 3
+// The gate of the tile pre-pass's PLAIN form (pvol_tile_dev.h), a pure function beside plan_path (pvol_api.hip): every input of
+// the decision that PlanIn has no room for, its own struct so that PlanIn and BatchPlan keep their sizes.  1 = PLAIN exactly when the batch is
+// COUNT mode (BatchPlan::tile) over a homogeneous extent, at least one light and the first one distant, no hierarchy, no spheres, at most
+// PVOL_MAX_TRIS triangles (their shadow rows are then in LDS), surface integrator off, no specular link, and PVOL_TILE_GENERAL unset;
+// 0 = the general form.  A black light or a black sigma_s does not enter: both forms leave tile_count_draws at the same early return.
+struct TilePlainIn {
+    int32_t tile;                       // BatchPlan::tile of the batch (PVOL_TILE_*)
+    int32_t volKind, nLights, light0Kind;
+    int32_t hasBvh, nSpheres, nTris;    // DevScene::bvhNodes != 0, nSpheres, nTris
+    int32_t surfOn, specLink;           // DevScene::surf.enabled, TileArgs::specLink != 0 (TileArgs::specOn implies it)
+    int32_t tileGeneral;                // PVOL_TILE_GENERAL=1
+};
+static_assert(sizeof(TilePlainIn) == 40, "tests/test_tile_plain_gate.py mirrors it");
+extern "C" int pvol_tile_plain_gate(const TilePlainIn *in);
 // The gate of the moment form, a pure function (pvol_api.hip): the number N in 1..3 of Taylor terms of exp(-delta_b L) whose truncation
 // bound x^N / N! e^x, x = max_b |delta_b| pathBound, is below 2^-25, or 0 = none is (keep the 30-bin path).  sigA / sigS: 30 values;
 // delta_b = sigma_t_b - the midrange of sigma_t; pathBound: a bound on the optical path length of a ray inside the medium.

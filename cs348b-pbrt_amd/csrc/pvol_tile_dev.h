@@ -159,6 +159,9 @@ __device__ __forceinline__ CountConsts count_consts(const DevScene &S) {
 // `slice` of `nSlices` (multi-wave pre-pass): the march steps are dealt round-robin to the waves that share a sample group; every
 // wave still walks tcur through ALL the additions (the reference accumulates t0 step by step), tests only its own steps, and
 // slice 0 alone adds the 4 + 7n that do not depend on a test.
+// PLAIN (pvol_tile_plain_gate, pvol_api.hip: a homogeneous extent, a distant first light over the triangle rows, no hierarchy, no spheres):
+// only the two-step loop is compiled, with the same operations in the same order as the general form takes on such a scene.
+template <bool PLAIN = false>
 __device__ uint32_t tile_count_draws(const DevScene &S, const CountConsts &C, const float *ltri, const float *trows, V3 o, V3 d, float maxt, float scatterU, bool blackS, bool lightBlack, uint32_t dbg = 0u,
                                      int slice = 0, int nSlices = 1, float mint = 0.f) {
     float t0, t1;
@@ -171,12 +174,13 @@ __device__ uint32_t tile_count_draws(const DevScene &S, const CountConsts &C, co
     const bool tryLight = !blackS && C.nLights > 0 && !lightBlack;
     const uint32_t fixedDraws = slice == 0 ? 4u + 7u * (uint32_t)nSamples : 0u;
     if (!tryLight || (dbg & 16u)) return fixedDraws;
-    if (trows && !C.bvh && !C.nSpheres && !(dbg & 8u)) {
+    if (PLAIN || (trows && !C.bvh && !C.nSpheres && !(dbg & 8u))) {
         // A distant light over the precomputed triangle rows: two march steps per trip (written out: the same loop over
         // small arrays compiled to slower code, and four steps per trip measured slower than one -- registers) -- every row is read from LDS once for
         // both (the shadow rays share their direction), and the two steps' arithmetic overlaps the reads' latency.  tcur takes
         // the same additions in the same order; the count is an integer sum.
         const V3 ld = v3(C.ldir[0], C.ldir[1], C.ldir[2]);
+        const int nT = (PLAIN && (dbg & 8u)) ? 0 : C.nTris;   // (timing knob 8: no visibility tests)
         for (int j = 0; j < nSamples; j += 2) {
             const V3 pA = o + d * tcur;
             tcur += step;
@@ -185,11 +189,11 @@ __device__ uint32_t tile_count_draws(const DevScene &S, const CountConsts &C, co
             if (nSlices > 1 && ((j >> 1) % nSlices) != slice) continue;
             const V3 pvA = xform_point(C.w2v, pA), pvB = xform_point(C.w2v, pB);
             bool inA, inB = j + 1 < nSamples;
-            if (is_region(C.volKind)) { inA = region_density(S, pvA) != 0.f; inB = inB && region_density(S, pvB) != 0.f; }
+            if (!PLAIN && is_region(C.volKind)) { inA = region_density(S, pvA) != 0.f; inB = inB && region_density(S, pvB) != 0.f; }
             else { inA = box_inside(C.lo, C.hi, pvA); inB = inB && box_inside(C.lo, C.hi, pvB); }
             if (!inA && !inB) continue;
             bool occA = false, occB = false;
-            for (int t = 0; t < C.nTris; ++t) {
+            for (int t = 0; t < nT; ++t) {
                 const f4 r0 = *reinterpret_cast<const f4 *>(trows + 16 * t), r1 = *reinterpret_cast<const f4 *>(trows + 16 * t + 4),
                          r2 = *reinterpret_cast<const f4 *>(trows + 16 * t + 8), r3 = *reinterpret_cast<const f4 *>(trows + 16 * t + 12);
                 TriPre tp;
@@ -202,52 +206,54 @@ __device__ uint32_t tile_count_draws(const DevScene &S, const CountConsts &C, co
         }
         return fixedDraws + u;
     }
-    for (int j = 0; j < nSamples; ++j) {
-        const V3 p = o + d * tcur;
-        tcur += step;
-        if (nSlices > 1 && (j % nSlices) != slice) continue;
-        const V3 pv = xform_point(C.w2v, p);
-        // sigma_s(p) black: outside a homogeneous extent, or zero density of a VolumeGrid (volumegrid.cpp:39-57)
-        if (is_region(C.volKind) ? region_density(S, pv) == 0.f : !box_inside(C.lo, C.hi, pv)) continue;
-        RayD vis;
-        if (C.lightKind == PVOL_LIGHT_DISTANT) {
-            vis.o = p; vis.d = v3(C.ldir[0], C.ldir[1], C.ldir[2]); vis.mint = 0.f; vis.maxt = INFINITY;
-        } else {
-            const V3 lp = v3(C.lpos[0], C.lpos[1], C.lpos[2]);
-            const V3 wo = normalize(lp - p);
-            const float dist = len(p - lp);
-            vis.o = p; vis.d = vdiv(lp - p, dist); vis.mint = 0.f; vis.maxt = dist * (1.f - 0.f);
-            if (C.lightKind == PVOL_LIGHT_SPOT) {
-                V3 wl = normalize(v3(C.w2l[0] * -wo.x + C.w2l[1] * -wo.y + C.w2l[2] * -wo.z,
-                                     C.w2l[3] * -wo.x + C.w2l[4] * -wo.y + C.w2l[5] * -wo.z,
-                                     C.w2l[6] * -wo.x + C.w2l[7] * -wo.y + C.w2l[8] * -wo.z));
-                const float costheta = wl.z;   // SpotLight::Falloff, spot.cpp:60-69; 0 means L.IsBlack()
-                float fall = 1.f;
-                if (costheta < C.cosTotalWidth) fall = 0.f;
-                else if (!(costheta > C.cosFalloffStart)) {
-                    const float delta = (costheta - C.cosTotalWidth) / (C.cosFalloffStart - C.cosTotalWidth);
-                    fall = delta * delta * delta * delta;
+    if constexpr (!PLAIN) {
+        for (int j = 0; j < nSamples; ++j) {
+            const V3 p = o + d * tcur;
+            tcur += step;
+            if (nSlices > 1 && (j % nSlices) != slice) continue;
+            const V3 pv = xform_point(C.w2v, p);
+            // sigma_s(p) black: outside a homogeneous extent, or zero density of a VolumeGrid (volumegrid.cpp:39-57)
+            if (is_region(C.volKind) ? region_density(S, pv) == 0.f : !box_inside(C.lo, C.hi, pv)) continue;
+            RayD vis;
+            if (C.lightKind == PVOL_LIGHT_DISTANT) {
+                vis.o = p; vis.d = v3(C.ldir[0], C.ldir[1], C.ldir[2]); vis.mint = 0.f; vis.maxt = INFINITY;
+            } else {
+                const V3 lp = v3(C.lpos[0], C.lpos[1], C.lpos[2]);
+                const V3 wo = normalize(lp - p);
+                const float dist = len(p - lp);
+                vis.o = p; vis.d = vdiv(lp - p, dist); vis.mint = 0.f; vis.maxt = dist * (1.f - 0.f);
+                if (C.lightKind == PVOL_LIGHT_SPOT) {
+                    V3 wl = normalize(v3(C.w2l[0] * -wo.x + C.w2l[1] * -wo.y + C.w2l[2] * -wo.z,
+                                         C.w2l[3] * -wo.x + C.w2l[4] * -wo.y + C.w2l[5] * -wo.z,
+                                         C.w2l[6] * -wo.x + C.w2l[7] * -wo.y + C.w2l[8] * -wo.z));
+                    const float costheta = wl.z;   // SpotLight::Falloff, spot.cpp:60-69; 0 means L.IsBlack()
+                    float fall = 1.f;
+                    if (costheta < C.cosTotalWidth) fall = 0.f;
+                    else if (!(costheta > C.cosFalloffStart)) {
+                        const float delta = (costheta - C.cosTotalWidth) / (C.cosFalloffStart - C.cosTotalWidth);
+                        fall = delta * delta * delta * delta;
+                    }
+                    if (fall == 0.f) continue;
                 }
-                if (fall == 0.f) continue;
             }
-        }
-        // Scene::IntersectP over the world triangles, staged in LDS (12 floats each): every lane reads the same words
-        // (broadcast), no early exit, so the loads of all triangles are in flight together
-        bool occ = false;
-        if (C.nSpheres && spheres_occluded(S, vis.o, vis.d, vis.mint, vis.maxt)) {
-            occ = true;
-        } else if (C.bvh) {   // more triangles than LDS rows: the device-built hierarchy (pvol_bvh_dev.h)
-            occ = bvh_occluded(S, vis.o, vis.d, vis.mint, vis.maxt);
-        } else if (trows) {   // distant light: direction-only terms precomputed per triangle
-            if (!(dbg & 8u)) occ = tri_rows_occluded(trows, C.nTris, vis.o, vis.d, vis.mint, vis.maxt);
-        } else {
-            for (int t = 0; t < ((dbg & 8u) ? 0 : C.nTris); ++t) {
-                const f4 a = *reinterpret_cast<const f4 *>(ltri + 12 * t), b = *reinterpret_cast<const f4 *>(ltri + 12 * t + 4),
-                         c = *reinterpret_cast<const f4 *>(ltri + 12 * t + 8);
-                occ = occ | tri_hit_v(v3(a.x, a.y, a.z), v3(a.w, b.x, b.y), v3(b.z, b.w, c.x), vis);
+            // Scene::IntersectP over the world triangles, staged in LDS (12 floats each): every lane reads the same words
+            // (broadcast), no early exit, so the loads of all triangles are in flight together
+            bool occ = false;
+            if (C.nSpheres && spheres_occluded(S, vis.o, vis.d, vis.mint, vis.maxt)) {
+                occ = true;
+            } else if (C.bvh) {   // more triangles than LDS rows: the device-built hierarchy (pvol_bvh_dev.h)
+                occ = bvh_occluded(S, vis.o, vis.d, vis.mint, vis.maxt);
+            } else if (trows) {   // distant light: direction-only terms precomputed per triangle
+                if (!(dbg & 8u)) occ = tri_rows_occluded(trows, C.nTris, vis.o, vis.d, vis.mint, vis.maxt);
+            } else {
+                for (int t = 0; t < ((dbg & 8u) ? 0 : C.nTris); ++t) {
+                    const f4 a = *reinterpret_cast<const f4 *>(ltri + 12 * t), b = *reinterpret_cast<const f4 *>(ltri + 12 * t + 4),
+                             c = *reinterpret_cast<const f4 *>(ltri + 12 * t + 8);
+                    occ = occ | tri_hit_v(v3(a.x, a.y, a.z), v3(a.w, b.x, b.y), v3(b.z, b.w, c.x), vis);
+                }
             }
+            if (!occ) ++u;
         }
-        if (!occ) ++u;
     }
     return fixedDraws + u;
 }
@@ -344,8 +350,12 @@ struct SpecWalkPol {
 
 // SPEC: the scene holds a specular material and the surface integrator is on (the recursion of pvol_spec_dev.h is compiled in;
 // kept out of the other instantiations, whose register allocation it would otherwise weigh down)
-template <bool FUSED, int NREG, bool SPEC>
-__global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, TileArgs T) {   // FUSED: 256 VGPRs (it wants 385: one wave per SIMD, four tasks per CU at a time)
+// PLAIN (COUNT mode only; the plan's choice per batch, pvol_tile_plain_gate): the scene has a homogeneous extent, a distant first light whose
+// triangle rows are in LDS, no hierarchy, no spheres, no surface integrator and no specular link.  Every test of those is a constant here, so
+// the code behind them -- and the registers it holds across the per-pixel loop -- is gone; what is left runs exactly as in the general form.
+template <bool FUSED, int NREG, bool SPEC, bool PLAIN = false>
+__global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, TileArgs T) {
+    static_assert(!PLAIN || (!FUSED && !SPEC), "PLAIN is a form of the COUNT-mode pre-pass without the specular recursion");   // FUSED: 256 VGPRs (it wants 385: one wave per SIMD, four tasks per CU at a time)
     extern __shared__ __align__(16) unsigned char lds[];
     const DevScene &S = *A.scene;
     const int lane = threadIdx.x;
@@ -370,7 +380,7 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
     }
     __syncthreads();
     float *trows = 0;
-    if (!FUSED && S.nLights > 0 && S.lights[0].kind == PVOL_LIGHT_DISTANT) {
+    if (PLAIN || (!FUSED && S.nLights > 0 && S.lights[0].kind == PVOL_LIGHT_DISTANT)) {
         trows = ltri + S.nTris * 12;
         tri_rows_prepare(S, v3(S.lights[0].dir[0], S.lights[0].dir[1], S.lights[0].dir[2]), trows, lane);
     }
@@ -400,8 +410,8 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
     const bool blackS = spec_is_black(ld4(S.sigS, q));
     const bool lightBlack = S.nLights > 0 ? spec_is_black(ld4(S.lights[0].intensity, q)) : true;
     unsigned blackMask = 0u;   // per light, for the surface integrator's direct lighting
-    for (int l = 0; l < S.nLights; ++l) if (spec_is_black(ld4(S.lights[l].intensity, q))) blackMask |= 1u << l;
-    const bool surfOn = S.surf.enabled != 0;
+    if (!PLAIN) for (int l = 0; l < S.nLights; ++l) if (spec_is_black(ld4(S.lights[l].intensity, q))) blackMask |= 1u << l;
+    const bool surfOn = !PLAIN && S.surf.enabled != 0;
     pvol_ray *rays = T.rays;
     const CountConsts CC = count_consts(S);
     for (uint32_t k = begin; k < end; k += T.spp) {
@@ -425,9 +435,9 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
                 tm = lerpf(L.time[i], T.shutterOpen, T.shutterClose);
                 su = L.scatter[i];
                 tile_camera_ray(T, imageX, imageY, &o, &d);
-                if (S.bvhNodes) { float th; if (bvh_closest(S, o, d, 0.f, INFINITY, &th) >= 0) maxt = th; }
+                if (!PLAIN && S.bvhNodes) { float th; if (bvh_closest(S, o, d, 0.f, INFINITY, &th) >= 0) maxt = th; }
                 else maxt = tile_clip(ltri, S.nTris, o, d);
-                if (S.nSpheres) { V3 ph; spheres_closest(S, o, d, 0.f, &maxt, &ph); }
+                if (!PLAIN && S.nSpheres) { V3 ph; spheres_closest(S, o, d, 0.f, &maxt, &ph); }
                 uint32_t link = 0u;
                 if (surfOn && maxt < INFINITY) {
                     SurfHit sh;
@@ -437,7 +447,7 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
                         else glass = 1;   // the tree is walked below, with the whole wave
                     }
                 }
-                if (!FUSED && T.specLink) T.specLink[ri] = link;
+                if (!PLAIN && !FUSED && T.specLink) T.specLink[ri] = link;
                 pvol_ray pr;
                 pr.o[0] = o.x; pr.o[1] = o.y; pr.o[2] = o.z; pr.mint = 0.f;
                 pr.d[0] = d.x; pr.d[1] = d.y; pr.d[2] = d.z; pr.maxt = maxt;
@@ -447,7 +457,7 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
                 T.xy[2 * ri + 1] = imageY;
             }
             if (!FUSED) {
-                uint32_t nd = (on && !(T.debugSkip & 2u)) ? tile_count_draws(S, CC, ltri, trows, o, d, maxt, su, blackS, lightBlack, T.debugSkip) : ((T.debugSkip & 2u) ? 270u : 0u);
+                uint32_t nd = (on && !(T.debugSkip & 2u)) ? tile_count_draws<PLAIN>(S, CC, ltri, trows, o, d, maxt, su, blackS, lightBlack, T.debugSkip) : ((T.debugSkip & 2u) ? 270u : 0u);
                 // wave total (integer adds in any order are exact)
                 unsigned long long tot = nd + surfDraws;
                 for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
@@ -526,12 +536,15 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
 // shuffles, the advance) and ALL waves share the draw count of a pixel: wave = slice * G + g handles the samples of group g
 // (64 at a time) and the march steps of its slice (tile_count_draws: steps dealt round-robin), the partial counts meet in LDS.
 // Two workgroup barriers per pixel; the stream only ever needs the pixel's TOTAL, so one skip replaces the per-trip skips.
-template <int NW, bool SPEC>
+template <int NW, bool SPEC, bool PLAIN = false>
 // Register budget = residency: the kernel wants ~340 VGPRs, and at that size a CU holds one wave per SIMD -- ONE task's workgroup (four waves)
 // or two tasks' (two waves) at a time, while a rank of an 8-GPU frame has two tasks per CU and one of a 4-GPU frame four.  Two waves per SIMD
 // (256 VGPRs, 83 spilled) keeps every task of the CU resident: 512-task pre-pass 85.9 (eight waves, 256 VGPRs) -> 56.5 ms (four waves),
 // 1 024-task pre-pass 134 -> 77 ms (two waves).  Eight and sixteen waves per task ask for four per SIMD (128 VGPRs).
+// PLAIN with two and four waves takes 152 VGPRs of the 256 and spills nothing: three waves per SIMD.  Held to four per SIMD (128 VGPRs, 22 spilled)
+// it was slower wherever it differed: 2 048-task pre-pass with two waves 87.7 -> 95.8 ms, 512-task with four 55.4 -> 60.2 ms.
 __global__ __launch_bounds__(LANES * NW, (NW >= 8 ? 4 : 2)) void tile_mw_kernel(LiArgs A, TileArgs T, uint32_t partOff) {
+    static_assert(!PLAIN || !SPEC, "PLAIN has no specular recursion");
     extern __shared__ __align__(16) unsigned char lds[];
     constexpr bool W1 = (NW == 1);   // a one-wave workgroup (debugging form) may use the workgroup barrier inside the RNG helpers
     const DevScene &S = *A.scene;
@@ -546,7 +559,7 @@ __global__ __launch_bounds__(LANES * NW, (NW >= 8 ? 4 : 2)) void tile_mw_kernel(
     L.oth = reinterpret_cast<uint32_t *>(L.scatter + T.spp);
     const size_t triOff = (((size_t)MT_N * 4 + (size_t)T.spp * 5 * 4) + 15) & ~(size_t)15;
     float *ltri = reinterpret_cast<float *>(lds + triOff);
-    const bool shadowRows = S.nLights > 0 && S.lights[0].kind == PVOL_LIGHT_DISTANT;
+    const bool shadowRows = PLAIN || (S.nLights > 0 && S.lights[0].kind == PVOL_LIGHT_DISTANT);
     const size_t partHere = (triOff + (size_t)S.nTris * 12 * 4 + (shadowRows ? (size_t)S.nTris * 16 * 4 : 0) + 64 + 15) & ~(size_t)15;
     unsigned long long *part = reinterpret_cast<unsigned long long *>(lds + partHere);
     for (int i = tid; i < S.nTris * 12; i += LANES * NW) {
@@ -556,7 +569,7 @@ __global__ __launch_bounds__(LANES * NW, (NW >= 8 ? 4 : 2)) void tile_mw_kernel(
     }
     __syncthreads();
     float *trows = 0;
-    if (S.nLights > 0 && S.lights[0].kind == PVOL_LIGHT_DISTANT) {
+    if (shadowRows) {
         trows = ltri + S.nTris * 12;
         tri_rows_prepare(S, v3(S.lights[0].dir[0], S.lights[0].dir[1], S.lights[0].dir[2]), trows, tid);   // workgroup barrier inside
     }
@@ -573,8 +586,8 @@ __global__ __launch_bounds__(LANES * NW, (NW >= 8 ? 4 : 2)) void tile_mw_kernel(
     const bool blackS = spec_is_black(ld4(S.sigS, q));
     const bool lightBlack = S.nLights > 0 ? spec_is_black(ld4(S.lights[0].intensity, q)) : true;
     unsigned blackMask = 0u;
-    for (int l = 0; l < S.nLights; ++l) if (spec_is_black(ld4(S.lights[l].intensity, q))) blackMask |= 1u << l;
-    const bool surfOn = S.surf.enabled != 0;
+    if (!PLAIN) for (int l = 0; l < S.nLights; ++l) if (spec_is_black(ld4(S.lights[l].intensity, q))) blackMask |= 1u << l;
+    const bool surfOn = !PLAIN && S.surf.enabled != 0;
     pvol_ray *rays = T.rays;
     const CountConsts CC = count_consts(S);
     // sample groups served at once, and march-step slices per group
@@ -601,9 +614,9 @@ __global__ __launch_bounds__(LANES * NW, (NW >= 8 ? 4 : 2)) void tile_mw_kernel(
             V3 o, d;
             tile_camera_ray(T, imageX, imageY, &o, &d);
             float maxt = INFINITY;
-            if (S.bvhNodes) { float th; if (bvh_closest(S, o, d, 0.f, INFINITY, &th) >= 0) maxt = th; }
+            if (!PLAIN && S.bvhNodes) { float th; if (bvh_closest(S, o, d, 0.f, INFINITY, &th) >= 0) maxt = th; }
             else maxt = tile_clip(ltri, S.nTris, o, d);
-            if (S.nSpheres) { V3 ph; spheres_closest(S, o, d, 0.f, &maxt, &ph); }
+            if (!PLAIN && S.nSpheres) { V3 ph; spheres_closest(S, o, d, 0.f, &maxt, &ph); }
             if (slice == 0) {
                 uint32_t surfDraws = 0u;
                 const size_t ri = (size_t)st.first_ray + k + i;
@@ -612,7 +625,7 @@ __global__ __launch_bounds__(LANES * NW, (NW >= 8 ? 4 : 2)) void tile_mw_kernel(
                     SurfHit sh;
                     if (surf_closest(S, o, d, 0.f, &sh)) surfDraws = tile_surface_draws<SPEC>(S, T, CC, ltri, trows, sh, d, su, tm, ri, blackS, lightBlack, blackMask, A.counters, &link);
                 }
-                if (T.specLink) T.specLink[ri] = link;
+                if (!PLAIN && T.specLink) T.specLink[ri] = link;
                 pvol_ray pr;
                 pr.o[0] = o.x; pr.o[1] = o.y; pr.o[2] = o.z; pr.mint = 0.f;
                 pr.d[0] = d.x; pr.d[1] = d.y; pr.d[2] = d.z; pr.maxt = maxt;
@@ -622,7 +635,7 @@ __global__ __launch_bounds__(LANES * NW, (NW >= 8 ? 4 : 2)) void tile_mw_kernel(
                 T.xy[2 * ri + 1] = imageY;
                 mine += surfDraws;
             }
-            if (!(T.debugSkip & 2u)) mine += tile_count_draws(S, CC, ltri, trows, o, d, maxt, su, blackS, lightBlack, 0u, slice, NSL);
+            if (!(T.debugSkip & 2u)) mine += tile_count_draws<PLAIN>(S, CC, ltri, trows, o, d, maxt, su, blackS, lightBlack, 0u, slice, NSL);
             else if (slice == 0) mine += 270ull;   // timing knob (PVOL_TIMING_KNOBS builds only)
         }
         for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
@@ -645,29 +658,40 @@ extern "C" size_t pvol_tile_lds_bytes(int maxSteps, uint32_t spp, bool fused, in
 }
 
 // *form: the name of what was launched (pvol_tile_kernel_name), written next to each launch so that it cannot say anything else
-template <bool SPEC>
+template <bool SPEC, bool PLAIN>
 static hipError_t launch_tile_t(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask,
                                 const char **form) {
     dim3 grid(args->nStreams), block(LANES);
     if (!fused && wavesPerTask > 1 && args->state == 0 && args->sliceK == 0) {
         const uint32_t partOff = (uint32_t)((ldsBytes + 15) & ~(size_t)15);
         const size_t bytes = partOff + 16 * 8;
-        if (wavesPerTask >= 16) { *form = "tile_mw_kernel<16>"; hipLaunchKernelGGL((tile_mw_kernel<16, SPEC>), grid, dim3(LANES * 16), bytes, stream, *args, *tile, partOff); }
-        else if (wavesPerTask >= 8) { *form = "tile_mw_kernel<8>"; hipLaunchKernelGGL((tile_mw_kernel<8, SPEC>), grid, dim3(LANES * 8), bytes, stream, *args, *tile, partOff); }
-        else if (wavesPerTask >= 4) { *form = "tile_mw_kernel<4>"; hipLaunchKernelGGL((tile_mw_kernel<4, SPEC>), grid, dim3(LANES * 4), bytes, stream, *args, *tile, partOff); }
-        else { *form = "tile_mw_kernel<2>"; hipLaunchKernelGGL((tile_mw_kernel<2, SPEC>), grid, dim3(LANES * 2), bytes, stream, *args, *tile, partOff); }
+        if (wavesPerTask >= 16) { *form = "tile_mw_kernel<16>"; hipLaunchKernelGGL((tile_mw_kernel<16, SPEC, PLAIN>), grid, dim3(LANES * 16), bytes, stream, *args, *tile, partOff); }
+        else if (wavesPerTask >= 8) { *form = "tile_mw_kernel<8>"; hipLaunchKernelGGL((tile_mw_kernel<8, SPEC, PLAIN>), grid, dim3(LANES * 8), bytes, stream, *args, *tile, partOff); }
+        else if (wavesPerTask >= 4) { *form = "tile_mw_kernel<4>"; hipLaunchKernelGGL((tile_mw_kernel<4, SPEC, PLAIN>), grid, dim3(LANES * 4), bytes, stream, *args, *tile, partOff); }
+        else { *form = "tile_mw_kernel<2>"; hipLaunchKernelGGL((tile_mw_kernel<2, SPEC, PLAIN>), grid, dim3(LANES * 2), bytes, stream, *args, *tile, partOff); }
         return hipGetLastError();
     }
     *form = fused ? "tile_kernel<fused>" : "tile_kernel<count>";
-    if (!fused) hipLaunchKernelGGL((tile_kernel<false, 4, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
+    if (!fused) hipLaunchKernelGGL((tile_kernel<false, 4, SPEC, PLAIN>), grid, block, ldsBytes, stream, *args, *tile);
+    else if constexpr (PLAIN) return hipErrorInvalidValue;   // PLAIN is a form of COUNT mode
     else if (candCap <= 4 * LANES) hipLaunchKernelGGL((tile_kernel<true, 4, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
     else hipLaunchKernelGGL((tile_kernel<true, 12, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
     return hipGetLastError();
 }
 // wavesPerTask (COUNT mode, whole batch in one launch): 1 = the one-wave kernel; 2 / 4 / 8 / 16 = tile_mw_kernel, chosen by the host when
-// few tasks share a CU (pvol_api.hip)
+// few tasks share a CU (pvol_api.hip).  plain: the plan's pvol_tile_plain_gate held for this batch -- the PLAIN instantiations, which exist
+// in the first compilation only (the gate never holds over a density region); asking for one that does not exist is an error.  *form keeps
+// naming the kernel and its wave count; pvol_tile_form_name says which of the two forms ran.
 extern "C" hipError_t pvol_launch_tile(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask,
-                                       const char **form) {
-    return tile->specOn ? launch_tile_t<true>(args, tile, fused, ldsBytes, candCap, stream, wavesPerTask, form)
-                        : launch_tile_t<false>(args, tile, fused, ldsBytes, candCap, stream, wavesPerTask, form);
+                                       bool plain, const char **form) {
+    if (plain) {
+#if PVOL_REGION_EXP
+        return hipErrorInvalidValue;
+#else
+        if (fused || tile->specOn || tile->specLink) return hipErrorInvalidValue;
+        return launch_tile_t<false, true>(args, tile, false, ldsBytes, candCap, stream, wavesPerTask, form);
+#endif
+    }
+    return tile->specOn ? launch_tile_t<true, false>(args, tile, fused, ldsBytes, candCap, stream, wavesPerTask, form)
+                        : launch_tile_t<false, false>(args, tile, fused, ldsBytes, candCap, stream, wavesPerTask, form);
 }

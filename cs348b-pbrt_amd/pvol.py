@@ -176,6 +176,8 @@ def lib():
         L.pvol_march_kernel_name.restype = C.c_char_p
         L.pvol_tile_kernel_name.argtypes = [C.c_void_p]
         L.pvol_tile_kernel_name.restype = C.c_char_p
+        L.pvol_tile_form_name.argtypes = [C.c_void_p]
+        L.pvol_tile_form_name.restype = C.c_char_p
         L.pvol_gaussian_filter_table.argtypes = [C.c_float, C.c_float, C.c_float, _f32p]
         L.pvol_gaussian_filter_table.restype = None
         L.pvol_compute_sub_window.argtypes = [C.POINTER(abi.Sampler), C.c_uint32, C.POINTER(C.c_int32)]
@@ -222,7 +224,7 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_get_li_coalescing_stats", "pvol_preprocess_group", "pvol_render_frame_group",
            "pvol_film_window_from_crop", "pvol_film_sample_extent", "pvol_render_tasks_window_device",
            "pvol_film_add_samples_window_device", "pvol_film_resolve_window_device", "pvol_render_frame_ranks_window",
-           "pvol_render_frame_group_window", "pvol_tile_kernel_name", "pvol_set_triangle_normals",
+           "pvol_render_frame_group_window", "pvol_tile_kernel_name", "pvol_tile_form_name", "pvol_set_triangle_normals",
            "pvol_compute_radiance", "pvol_compute_radiance_arrays", "pvol_radiance_lo_count", "pvol_download_radiance_lo",
            "pvol_radiance_lookup", "pvol_radiance_lookup_device", "pvol_set_surface_integrator_maps",
            "pvol_build_gather_map", "pvol_build_gather_map_arrays", "pvol_gather_map_count", "pvol_gather_photons",
@@ -761,6 +763,10 @@ class PhotonVolume:
     def tile_kernel_name(self):
         """The form of the tile pre-pass the last render batch launched ("" if none ran)."""
         return lib().pvol_tile_kernel_name(self._h).decode()
+
+    def tile_form_name(self):
+        """"plain" or "general": which compilation of that kernel ran (pvol_tile_plain_gate; PVOL_TILE_GENERAL=1 keeps the general one)."""
+        return lib().pvol_tile_form_name(self._h).decode()
 
     def kernel_time_ms(self, reset=False):
         avg = C.c_double()

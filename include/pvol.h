@@ -624,6 +624,10 @@ const char *pvol_march_kernel_name(pvol_ctx *ctx);
  * "tile_kernel<fused>", "tile_mw_kernel<2>", "<4>", "<8>" or "<16>" (the multi-wave COUNT form; a requested wave count is rounded down
  * to one of these, and sliced launches take the one-wave kernel whatever was asked); "" before the first. */
 const char *pvol_tile_kernel_name(pvol_ctx *ctx);
+/* Which of its two compilations that launch was: "plain" (COUNT mode over a homogeneous extent lit by a distant first light, at most 64
+ * triangles, no spheres, no surface integrator: the tests of all of these compiled out) or "general" (everything else, and every scene
+ * with PVOL_TILE_GENERAL=1 in the environment when the context was created).  Both give the same rays and stream ends bit for bit. */
+const char *pvol_tile_form_name(pvol_ctx *ctx);
 
 /* Per-phase device time of pvol_render_tasks_device, HIP events on the launch stream (off by default).  out[6], milliseconds
  * summed since the last reset: [0] tile pre-pass (LDSampler + camera + Scene::Intersect clip + draw count: tile_kernel),
