@@ -71,6 +71,7 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     { const char *ng = getenv("PVOL_NO_GROUP"); c->noGroup = ng && ng[0] == '1'; }
     { const char *nl = getenv("PVOL_NO_LITE"); c->noLite = nl && nl[0] == '1'; }
     { const char *nm = getenv("PVOL_NO_MOMENTS"); c->noMoments = nm && nm[0] == '1'; }
+    c->groupPrecore = pvol_precore_kappa(getenv("PVOL_GROUP_PRECORE"));
     { const char *tg = getenv("PVOL_TILE_GENERAL"); c->tileGeneral = tg && tg[0] == '1'; }
     { const char *gw = getenv("PVOL_GROUP_WAVES"); if (gw) c->groupWavesPerCU = std::max(1, atoi(gw)); }
     { const char *tw = getenv("PVOL_TILE_WAVES"); if (tw) c->tileWaves = std::max(0, atoi(tw)); }
@@ -274,6 +275,16 @@ static int moment_terms(const float *sigA, const float *sigS, double pathBound, 
 int pvol_moment_gate(const float *sigA, const float *sigS, double pathBound) {
     if (!sigA || !sigS) return 0;
     return moment_terms(sigA, sigS, pathBound, MOM_ORDERS);
+}
+
+float pvol_precore_bound(float theta, float rho) { return precore_bound(theta, rho); }
+// PVOL_GROUP_PRECORE: unset or unreadable = the default, 0 = the rule off; a kappa above 1 would put theta beyond the guess itself
+float pvol_precore_kappa(const char *env) {
+    if (!env || !env[0]) return PVOL_PRECORE_DEFAULT;
+    char *end = 0;
+    const float v = strtof(env, &end);
+    if (end == env || !(v >= 0.f)) return PVOL_PRECORE_DEFAULT;
+    return std::min(v, 1.f);
 }
 
 // The longest main diagonal of the medium's extent in world space (the inverse of w2v's linear part applied to the box's edges): no
@@ -575,6 +586,7 @@ int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
     a.out = b.out; a.draws = b.draws; a.initState = b.initState; a.finalState = b.finalState; a.counters = c->dCounters.get();
     a.transmittanceOnly = b.transOnly; a.chunkCounter = c->dWords.get(); a.needSeq = c->dWords.get() + 1; a.gated = 0;
     a.tauOut = b.tauOut; a.status = b.status; a.grpGuess = in.knobs.groupGuess; a.moments = p.groupForm == GRP_FORM_MOMENTS;
+    a.grpPrecore = c->groupPrecore;
     if (p.groupForm) {
         a.defer = pvol_buf<DeferRec>(c, PVOL_BUF_DEFER); a.deferCount = c->dWords.get() + 2;
         a.deferCap = (uint32_t)std::min<size_t>(c->buf[PVOL_BUF_DEFER].bytes / sizeof(DeferRec), 0xffffffffu);

@@ -14,6 +14,7 @@
 #ifndef PVOL_DEV_H
 #define PVOL_DEV_H
 
+#include <math.h>
 #include <stdint.h>
 #include "../../include/pvol.h"
 
@@ -29,6 +30,22 @@
 __host__ __device__
 #endif
 static inline bool is_density_region(int kind) { return kind == PVOL_VOLUME_GRID || kind == PVOL_VOLUME_EXPONENTIAL; }
+
+// li_group_kernel's settled class: the threshold t on a photon's distance^2 to the group's centre c below which
+// the photon lies inside radius^2 theta of EVERY point within rho of c.  Triangle inequality, d_p <= d_c + rho, with the rounding
+// slack of the staging radius Rs the other way round:  (sqrt(t) + rho) 1.0001 + 1e-6 <= sqrt(theta),  so that the claim holds for
+// the fp32 DistanceSquared in the reference's operation order (a few 2^-24 relative, against 2e-4 here).  0 = nothing qualifies
+// (sqrt(theta) <= rho, or no room left after the slack).  Monotone in theta: every operation below is.
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline float precore_bound(float theta, float rho) {
+    if (!(theta > 0.f) || !(rho >= 0.f)) return 0.f;
+    const float s = sqrtf(theta);
+    if (!(s > rho)) return 0.f;
+    const float r = (s - 1e-6f) / 1.0001f - rho;
+    return r > 0.f ? r * r : 0.f;
+}
 
 struct DevLight {
     int32_t kind;

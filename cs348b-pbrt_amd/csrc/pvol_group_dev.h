@@ -14,6 +14,10 @@
 //   3. FLUX    for every bucket slot that is a member for SOME lane, the 128-byte alpha row comes through the scalar
 //              cache into SGPRs (wave-uniform address) and is added with v_pk_fma_f32(row, bit, acc): the exact
 //              addition for members, a no-op for the others.  No distance is evaluated a third time.
+//   0. SETTLE  (first attempt, guesses that were measured) the staged photons close enough to the centre to lie
+//              inside kappa x the smallest guessed k-th distance^2 of EVERY served lane (precore_bound) keep only their index: they are
+//              members for all, SELECT runs over the rest with k' = k - their number, each lane verifies kappa's claim with one compare
+//              (its k'-th distance^2 >= theta, else it asks again with the rule off), and FLUX adds their rows once for the wave.
 // Both passes evaluate kdtree.h:180's DistanceSquared per lane in the reference's operation order, so the k-NN sets
 // are the reference's; only the order of the flux additions differs (as in lphoton).
 //
@@ -81,13 +85,20 @@ __device__ float grid_tau_lane(const DevScene &S, V3 o, V3 d, float mint, float 
 
 // Photons within Rs of c -> LDS bucket of CAP slots (SoA, pitch CAP + 4).  Returns the count, or -1 if the bucket would overflow.
 // IDX_ONLY: the bucket is the list of photon indices alone (CAP + 8 words, padded with index 0 to a multiple of eight).
-template <int CAP, bool FINE = false, bool IDX_ONLY = false>
-__device__ int stage_bucket_g(const GridView &S, Gather &G, float *bucket, V3 c, float Rs, int lane, unsigned long long &tested) {
+// PRE (li_group_kernel): an accepted photon whose distance^2 to c is below dPre is SETTLED -- a member for every
+// lane the attempt serves -- and leaves only its index, from the top of the index array downwards (bI[CAP + 3 - i], i < *nPreOut); the
+// others are compacted from slot 0 upwards in unchanged relative order.  The count returned is that of the others; overflow is judged on
+// the sum, which keeps the settled class clear of the four sentinel slots: count + 4 <= CAP + 4 - *nPreOut.
+template <int CAP, bool FINE = false, bool IDX_ONLY = false, bool PRE = false>
+__device__ int stage_bucket_g(const GridView &S, Gather &G, float *bucket, V3 c, float Rs, int lane, unsigned long long &tested,
+                              float dPre = 0.f, int *nPreOut = nullptr) {
+    static_assert(!(PRE && IDX_ONLY), "the settled class lives in the index component of the SoA bucket");
     constexpr int GRP_PITCH_ = CAP + 4;
     float *bX = bucket, *bY = bucket + GRP_PITCH_, *bZ = bucket + 2 * GRP_PITCH_, *bI = IDX_ONLY ? bucket : bucket + 3 * GRP_PITCH_;
     const float T = Rs * Rs;
     const GridRows rows = grid_rows<FINE>(S, c, Rs, 0);
-    int count = 0;
+    int count = 0, nPre = 0;
+    if (PRE) *nPreOut = 0;
     for (int rb = 0; rb < rows.nrows; rb += LANES) {
         uint32_t start, rlen;
         grid_row_range<FINE>(S, rows, rb + lane, c, T, &start, &rlen);
@@ -141,13 +152,18 @@ __device__ int stage_bucket_g(const GridView &S, Gather &G, float *bucket, V3 c,
                     uint64_t m = __ballot(acc);
                     if (m) {
                         const int add = __popcll(m);
-                        if (count + add > CAP) return -1;
-                        if (acc) {
+                        if (count + nPre + add > CAP) return -1;
+                        const bool pre = PRE && acc && d2 < dPre;
+                        const uint64_t mp = PRE ? __ballot(pre) : 0ull;
+                        m &= ~mp;
+                        if (acc && !pre) {
                             const int at = count + (int)lanes_below(m, lane);
                             if (!IDX_ONLY) { bX[at] = P[k].x; bY[at] = P[k].y; bZ[at] = P[k].z; }
                             bI[at] = __uint_as_float(I[k]);
                         }
-                        count += add;
+                        if (PRE && pre) bI[GRP_PITCH_ - 1 - nPre - (int)lanes_below(mp, lane)] = __uint_as_float(I[k]);
+                        count += __popcll(m);
+                        if (PRE) nPre += __popcll(mp);
                     }
                 }
             }
@@ -162,12 +178,15 @@ __device__ int stage_bucket_g(const GridView &S, Gather &G, float *bucket, V3 c,
     }
     if (IDX_ONLY) { if (lane < 8) bI[count + lane] = 0.f; }
     else if (lane < 4) { bX[count + lane] = 3.0e18f; bY[count + lane] = 3.0e18f; bZ[count + lane] = 3.0e18f; bI[count + lane] = 0.f; }   // pad to a multiple of four: never inside any radius
+    if (PRE) *nPreOut = nPre;
     __syncthreads();
     return count;
 }
-__device__ __forceinline__ int stage_bucket(const DevScene &S, Gather &G, float *bucket, V3 c, float Rs, int lane, unsigned long long &tested) {
+// li_group_kernel's staging: one compilation, dPre = 0 settles nothing (no distance^2 is below 0)
+__device__ __forceinline__ int stage_bucket(const DevScene &S, Gather &G, float *bucket, V3 c, float Rs, int lane, unsigned long long &tested,
+                                            float dPre, int *nPre) {
     const GridView g = volume_grid(S);
-    return stage_bucket_g<GRP_CAP>(g, G, bucket, c, Rs, lane, tested);
+    return stage_bucket_g<GRP_CAP, false, false, true>(g, G, bucket, c, Rs, lane, tested, dPre, nPre);
 }
 
 typedef float nf4 __attribute__((ext_vector_type(4)));
@@ -577,6 +596,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                     // What is still open afterwards is handed to li_fixup_kernel.
                     float guessBase = lastRk;
                     if (j < PREV_N) guessBase = fmaxf(guessBase, prevRk[j]);
+                    const bool measured = guessBase > 0.f;   // a k-th distance^2 that was found, not one of the cold fallbacks below
                     {   // cold: what the other lanes found at their previous step, else the map-wide estimate
                         const float nbr = wave_max(lastRk);
                         if (!(guessBase > 0.f)) guessBase = nbr > 0.f ? nbr : S.rkEstimate;
@@ -619,14 +639,31 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                             rho = wave_max(needP ? len(p - c) : 0.f);
                         }
                         const float Rs = (sqrtf(T) + rho) * 1.0001f + 1e-6f;   // superset by the triangle inequality, with rounding slack
+                        // The settled class, first attempt only: theta = kappa x the smallest guess among the served lanes
+                        // is meant to lie below every served lane's k-th distance^2; a photon within precore_bound(theta, rho) of the centre is
+                        // then a member for all of them and stays out of both passes.  Wave-uniform.  Only guesses that were measured count
+                        // (lastRk, prevRk[j]), and no served lane may reach the full radius, even after the widening below: the EXACT
+                        // compilation of the passes and the short sets never meet a settled slot.
+                        float theta = 0.f;
+                        if (GRP_CORE_MIN < GRP_CAP && attempt == 0 && !fixedR && A.grpPrecore > 0.f && __ballot(needP) &&
+                            !__ballot(needP && (!measured || !(Tl * GRP_WIDEN < S.maxDistSq))))
+                            theta = A.grpPrecore * -wave_max(needP ? -guessBase : -3.0e38f);
+                        int nPre = 0;
                         unsigned long long tst = 0, ts0 = STATS ? stamp() : 0ull;
                         __syncthreads();   // the U region changes hands: mini lists -> paint list
-                        const int Mb = stage_bucket(S, G, L.pos, c, Rs, lane, tst);
-                        if (STATS) { wc.tested += (unsigned long long)max(Mb, 0); wc.cySearch += stamp() - ts0; }
+                        const int Mb = stage_bucket(S, G, L.pos, c, Rs, lane, tst, precore_bound(theta, rho), &nPre);
+                        if (STATS) { wc.tested += (unsigned long long)max(Mb, 0); wc.cySearch += stamp() - ts0; }   // slots the passes run over
                         if (STATS) wc.diag5 += 1;
                         if (Mb < 0) {   // bucket overflow
                             if (STATS && !GRP_PHASE_DIAG) wc.diag1 += __popcll(__ballot(needP));
                             if (needP) { Twant = fixedR ? 0.f : 0.4f * Tl; lastFail = 1; }   // fixed radius: nothing smaller to try
+                            continue;
+                        }
+                        if (nPre == 0) theta = 0.f;   // nothing settled: nothing to verify
+                        const int kq = k - nPre;      // rank of a lane's k-th among the slots it looks at
+                        if (kq < 1) {   // theta lay above everybody's k-th distance^2: the next attempt asks again (Twant = Tl) with the rule off
+                            if (STATS && !GRP_PHASE_DIAG) wc.diag0 += __popcll(__ballot(needP));
+                            if (needP) lastFail = 3;
                             continue;
                         }
                         // the bucket covers more than this lane asked for when other lanes asked for more: take it (up to
@@ -654,7 +691,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                         for (int wd = 0; wd < GRP_BINS / 8; ++wd) {
                             const uint32_t w = histLane[wd * LANES];
                             const int t = (int)nib_sum(w);
-                            const bool here = wsel < 0 && cum + t >= k;
+                            const bool here = wsel < 0 && cum + t >= kq;
                             wsel = here ? wd : wsel;
                             selBits = here ? w : selBits;
                             cumWord = here ? cum : cumWord;
@@ -667,7 +704,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
 #pragma unroll
                             for (int s = 0; s < 8; ++s) {
                                 const int cb = (int)((selBits >> (4 * s)) & 15u);
-                                const bool here = bstarI < 0 && c2 + cb >= k;
+                                const bool here = bstarI < 0 && c2 + cb >= kq;
                                 bstarI = here ? 8 * wsel + s : bstarI;
                                 cumBelow = here ? c2 : cumBelow;
                                 binCount = here ? cb : binCount;
@@ -678,8 +715,8 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                         const bool sane = needP && cum == inRange;
                         bool ok = sane && wsel >= 0 && bstarI >= 0 && binCount <= GRP_MINI;
                         // the full radius holds fewer than k photons: all of them count, r^2 = the farthest (photonvolume.cpp:76-105)
-                        const bool shortSet = sane && fullR && inRange < k;
-                        const bool tooFew = needP && !fullR && cum < k;
+                        const bool shortSet = sane && fullR && inRange + nPre < k;
+                        const bool tooFew = needP && !fullR && cum + nPre < k;
                         if (STATS && !GRP_PHASE_DIAG && attempt == 0) wc.diag0 += __popcll(__ballot(needP && !ok && !shortSet));
                         if (needP) {   // what to ask for next time (0 = nothing: crowded bin or wrapped counter, the exact lookup takes it)
                             Twant = 0.f;
@@ -688,7 +725,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                             // the k-th's bin still holds k photons and spreads them over finer bins
                             if (!tooFew && !ok && !shortSet) Twant = (sane && bstarI >= 0) ? Tl * ((float)(bstarI + 1) * (1.f / GRP_BINS)) * 1.001f : 0.6f * Tl;
                             if (tooFew) {   // the count seen inside Tl gives the local density: k photons need ~ (k / count)^(2/3) x Tl
-                                const float grow = cum > 0 ? 1.35f * __builtin_amdgcn_exp2f(0.6666667f * __builtin_amdgcn_logf((float)k / (float)cum)) : 1.0e9f;
+                                const float grow = cum + nPre > 0 ? 1.35f * __builtin_amdgcn_exp2f(0.6666667f * __builtin_amdgcn_logf((float)k / (float)(cum + nPre))) : 1.0e9f;
                                 Twant = fminf(S.maxDistSq, Tl * fmaxf(1.5f, grow));
                             }
                         }
@@ -739,7 +776,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                     sv[t] = lo; sv[t + 1] = hi;
                                 }
                             }
-                            const int m = k - cumBelow;   // 1-based rank of the k-th inside its bin
+                            const int m = kq - cumBelow;   // 1-based rank of the k-th inside its bin
                             float rkC = sv[0];
 #pragma unroll
                             for (int t = 1; t < GRP_MINI; ++t) rkC = (m == t + 1) ? sv[t] : rkC;
@@ -748,6 +785,12 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                             for (int t = 0; t < GRP_MINI; ++t) nLessIn += (sv[t] < rkC) ? 1 : 0;
                             int quota = m - nLessIn;   // ties at rkC are taken in bucket order
                             ok = ok && nb == binCount && rkC < INFINITY;
+                            {   // the verification of the settled class: strict, so no settled slot ties with the k-th.  A lane that fails it asks
+                                // again for the same radius (the next attempt has the rule off)
+                                const bool unverified = ok && !(rkC >= theta);
+                                if (unverified) { ok = false; Twant = Tl; }
+                                if (STATS && !GRP_PHASE_DIAG && theta > 0.f) wc.diag0 += __popcll(__ballot(unverified));
+                            }
                             // member bits of bin b*: d2 < r_k, or d2 == r_k while the tie quota lasts
                             {
                                 int t2 = 0;
@@ -802,7 +845,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                     coreW[wd] = (uint32_t)__builtin_amdgcn_readfirstlane((int)~wave_or(ok ? ~mem[wd] : 0u));
                                     nCore += __builtin_popcount(coreW[wd]);
                                 }
-                                if (nCore >= GRP_CORE_MIN) {
+                                if (anyOk && (nPre > 0 || nCore >= GRP_CORE_MIN)) {
                                     // slots that are members for EVERY served lane: their rows are summed once (four rows per load, lane = entry,
                                     // row parity) and the sum enters as one more "row" whose member bits are the served lanes
                                     uint32_t *clist = reinterpret_cast<uint32_t *>(L.miniD);
@@ -814,14 +857,16 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                         if ((c64 >> lane) & 1ull) clist[basePos + (int)lanes_below(c64, lane)] = __float_as_uint(bI[r2 * 64 + lane]);
                                         basePos += __popcll(c64);
                                     }
+                                    for (int i = lane; i < nPre; i += LANES) clist[nCore + i] = __float_as_uint(bI[GRP_PITCH - 1 - i]);   // the settled class
+                                    const int nSum = nCore + nPre;
                                     __syncthreads();
                                     float cs = 0.f;
-                                    for (int c0 = 0; c0 < nCore; c0 += 32) {   // up to 32 rows in flight per trip
+                                    for (int c0 = 0; c0 < nSum; c0 += 32) {   // up to 32 rows in flight per trip
                                         float v[8];
 #pragma unroll
                                         for (int q2 = 0; q2 < 8; ++q2) {
                                             const int at = c0 + 4 * q2 + qtr;
-                                            const bool on = at < nCore;
+                                            const bool on = at < nSum;
                                             const uint32_t idx = clist[on ? at : 0];
                                             const float w = momF[(size_t)idx * MOM_ROW + rowL];
                                             v[q2] = on ? w : 0.f;
@@ -894,7 +939,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                     coreW[wd] = (uint32_t)__builtin_amdgcn_readfirstlane((int)~wave_or(ok ? ~mem[wd] : 0u));
                                     nCore += __builtin_popcount(coreW[wd]);
                                 }
-                                if (nCore >= GRP_CORE_MIN) {
+                                if (anyOk && (nPre > 0 || nCore >= GRP_CORE_MIN)) {
                                     // slots that are members for EVERY served lane: their rows are summed once (two rows per load, lane = bin)
                                     // and the sum enters as one more "row" whose member bits are the served lanes
                                     uint32_t *clist = reinterpret_cast<uint32_t *>(L.miniD);
@@ -906,14 +951,16 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                         if ((c64 >> lane) & 1ull) clist[basePos + (int)lanes_below(c64, lane)] = __float_as_uint(bI[r2 * 64 + lane]);
                                         basePos += __popcll(c64);
                                     }
+                                    for (int i = lane; i < nPre; i += LANES) clist[nCore + i] = __float_as_uint(bI[GRP_PITCH - 1 - i]);   // the settled class
+                                    const int nSum = nCore + nPre;
                                     __syncthreads();
                                     float cs = 0.f;
-                                    for (int c0 = 0; c0 < nCore; c0 += 16) {   // up to 16 rows in flight per trip
+                                    for (int c0 = 0; c0 < nSum; c0 += 16) {   // up to 16 rows in flight per trip
                                         float v[8];
 #pragma unroll
                                         for (int q2 = 0; q2 < 8; ++q2) {
                                             const int at = c0 + 2 * q2 + half;
-                                            const bool on = at < nCore;
+                                            const bool on = at < nSum;
                                             const uint32_t idx = clist[on ? at : 0];
                                             const float w = alphaF[(size_t)idx * 32 + binL];
                                             v[q2] = on ? w : 0.f;
@@ -972,7 +1019,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                 }
                             }
                             }   // !MOMENTS
-                            if (ok) { done = true; rk = rkC; if (shortSet) nFoundLane = inRange; }
+                            if (ok) { done = true; rk = rkC; if (shortSet) nFoundLane = inRange + nPre; }
                             if (STATS) { wc.kept += (unsigned long long)k * __popcll(__ballot(ok)); wc.cyFlux += stamp() - tp3; }
                         }
                     }   // attempt

@@ -192,6 +192,7 @@ struct pvol_ctx {
     bool noGroup = false;       // PVOL_NO_GROUP=1: keep li_par_kernel (one wave per ray) where li_group_kernel (one ray per lane) would run
     bool forceSeq = false;      // PVOL_FORCE_SEQ=1: always take the stream-sequential kernel (testing)
     bool noMoments = false;     // PVOL_NO_MOMENTS=1: li_group_kernel keeps summing 30 bins where it would sum XYZ moments
+    float groupPrecore = 0.f;   // PVOL_GROUP_PRECORE (pvol_precore_kappa): li_group_kernel settles the bucket's inner photons once per wave, 0 = off
     int momentTerms = 0;        // pvol_moment_scene's decision for the scene set last (0: no moment form, volMap.mom stays empty)
     bool statsOn = false;
     // kernel timing (HIP events on the launch stream)
@@ -331,6 +332,11 @@ extern "C" int pvol_tile_plain_gate(const TilePlainIn *in);
 // bound x^N / N! e^x, x = max_b |delta_b| pathBound, is below 2^-25, or 0 = none is (keep the 30-bin path).  sigA / sigS: 30 values;
 // delta_b = sigma_t_b - the midrange of sigma_t; pathBound: a bound on the optical path length of a ray inside the medium.
 extern "C" int pvol_moment_gate(const float *sigA, const float *sigS, double pathBound);
+// li_group_kernel's settled class, pure: precore_bound (pvol_dev.h) for the host, and the knob's value.  The knob
+// lives in the context beside PVOL_NO_MOMENTS and not in LaunchKnobs, whose layout the plan's tests mirror.
+#define PVOL_PRECORE_DEFAULT 0.7f
+extern "C" float pvol_precore_bound(float theta, float rho);
+extern "C" float pvol_precore_kappa(const char *env);
 // What the moment form reads besides the map: the gate's decision for the scene `h` (its extent's world-space diagonal bounds a ray's
 // path, twice that the direct term's, which carries one order more), h.momSigBar / momEmit / momDirect, and the rows of the
 // map's fill kernel (MomentWeights::w[4 n + c][b], pvol_grid.hip).  Pure; returns the terms (0: h's moment fields stay zero).

@@ -34,5 +34,6 @@ struct LiArgs {
     float fxgWiden, fxgAim;     // li_fixup_group_kernel's radius policy (0 = the defaults 1.3 / 1.4): first radius^2 = widen x the probe's, the probe aims at aim x nused photons
     int32_t *status;            // optional: per ray PVOL_E_LIMIT where the record / LDS plan refused it (coalesced per-sample batches)
     int32_t moments;            // li_group_kernel, ray-parallel XYZ form: sum the map's moment rows (BatchPlan::groupForm 3)
+    float grpPrecore;           // li_group_kernel: kappa of the settled class (theta = kappa x the smallest guessed k-th distance^2 served), 0 = off
 };
 #endif
