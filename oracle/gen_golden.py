@@ -217,6 +217,14 @@ def main_specular():
     shoot_caustic("sphereroom", 4000, "sph", keep=3000)
     render_case("sph_surf", "sphereroom", "sph", 32, 32, 4, 16, tasks=[5, 6, 9, 10], stepsize=0.1, nused=50,
                 surface=os.path.join(GOLD, "caustic_sph.bin"))
+    # the same frame at other values of "maxspeculardepth" (1: glass gives nothing and a matte hit loses its 6 draws; 2: one
+    # level), and with a reflective glass (Kr 0.25: a glass hit spawns two rays, the samples own trees) at depths 3 and 5.
+    # photons_sph / caustic_sph are inputs of both sides and serve the reflective scene as they are.
+    cap("scene", "sphereroom_kr", os.path.join(GOLD, "scene_sphereroom_kr.bin"))
+    for tag, scene_name, depth in (("sph_surf_d1", "sphereroom", 1), ("sph_surf_d2", "sphereroom", 2),
+                                   ("sphkr_surf_d3", "sphereroom_kr", 3), ("sphkr_surf_d5", "sphereroom_kr", 5)):
+        render_case(tag, scene_name, "sph", 32, 32, 4, 16, tasks=[5, 6, 9, 10], stepsize=0.1, nused=50,
+                    surface=os.path.join(GOLD, "caustic_sph.bin"), surfspecdepth=depth)
 
 
 # ----------------------------------------------------------------------------- hit records for chosen rays (`hits`)

@@ -91,6 +91,8 @@ def lib():
         L.orc_render_tasks.argtypes = [C.c_void_p, C.POINTER(abi.Camera), C.POINTER(abi.Film), C.POINTER(abi.Sampler), _u32p, C.c_uint32,
                                        _f32p, C.c_void_p, _f32p, _f32p, _u64p, C.c_int, _f32p]
         L.orc_set_surface_integrator.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _f32p, _f32p, C.c_uint32, C.c_uint32]
+        L.orc_set_surface_integrator_depth.argtypes = L.orc_set_surface_integrator.argtypes + [C.c_int]
+        L.orc_render_tasks_counts.argtypes = L.orc_render_tasks.argtypes + [_u32p]
         _lib = L
     return _lib
 
@@ -168,18 +170,20 @@ class Oracle:
         lib().orc_get_counters(self._h, _p(v, _u64p), int(reset))
         return dict(zip(COUNTER_NAMES, [int(x) for x in v]))
 
-    def set_surface_integrator(self, n_used=300, max_dist=0.15, final_gather=True, caustic=None, n_paths=0):
+    def set_surface_integrator(self, n_used=300, max_dist=0.15, final_gather=True, caustic=None, n_paths=0, max_specular_depth=5):
         """PhotonIntegrator for render_tasks(): caustic = (p, wo, alpha) or None (no caustic map); None for n_used removes it."""
         if n_used is None:
             lib().orc_set_surface_integrator(self._h, 0, 0, 0.0, 0, None, None, None, 0, 0)
             return
+        depth = int(max_specular_depth)
         if caustic is None or len(caustic[0]) == 0:
-            lib().orc_set_surface_integrator(self._h, 1, n_used, max_dist, int(final_gather), None, None, None, 0, int(n_paths))
+            lib().orc_set_surface_integrator_depth(self._h, 1, n_used, max_dist, int(final_gather), None, None, None, 0, int(n_paths), depth)
             return
         p = np.ascontiguousarray(caustic[0], np.float32).reshape(-1)
         w = np.ascontiguousarray(caustic[1], np.float32).reshape(-1)
         a = np.ascontiguousarray(caustic[2], np.float32).reshape(-1)
-        lib().orc_set_surface_integrator(self._h, 1, n_used, max_dist, int(final_gather), _p(p, _f32p), _p(w, _f32p), _p(a, _f32p), p.size // 3, int(n_paths))
+        lib().orc_set_surface_integrator_depth(self._h, 1, n_used, max_dist, int(final_gather), _p(p, _f32p), _p(w, _f32p), _p(a, _f32p), p.size // 3,
+                                               int(n_paths), depth)
 
     def shoot(self, n_tasks=1, n_threads=1, block_paths=4096):
         return lib().orc_shoot_blocks(self._h, n_tasks, n_threads, block_paths)
@@ -265,7 +269,9 @@ def film_resolve(film, pixels):
 
 
 def render_tasks(oracle, camera, film, sampler, task_ids, records=True, n_threads=1):
-    """SamplerRendererTask::Run for the listed tasks -> dict(pixels, rays, image_xy, xyzT, end_draws)."""
+    """SamplerRendererTask::Run for the listed tasks -> dict(pixels, rays, image_xy, xyzT, end_draws, ...).  With a surface integrator,
+    per camera sample: spec_segments (rays its specular recursion spawned), spec_depth (the deepest ray.depth among them) and
+    spec_both (glass hits at which SpecularReflect and SpecularTransmit both spawned a ray)."""
     ids = np.ascontiguousarray(task_ids, np.uint32)
     n = 0
     for t in ids:
@@ -277,7 +283,9 @@ def render_tasks(oracle, camera, film, sampler, task_ids, records=True, n_thread
     xt = np.zeros((n if records else 0, 4), np.float32)
     sx = np.zeros((n if records else 0, 3), np.float32)
     end = np.zeros(len(ids), np.uint64)
-    rc = lib().orc_render_tasks(oracle._h, C.byref(camera), C.byref(film), C.byref(sampler), _p(ids, _u32p), len(ids), _p(pixels, _f32p),
+    sc = np.zeros((n if records else 0, 3), np.uint32)
+    rc = lib().orc_render_tasks_counts(oracle._h, C.byref(camera), C.byref(film), C.byref(sampler), _p(ids, _u32p), len(ids), _p(pixels, _f32p),
                                 rays.ctypes.data if records else None, _p(xy, _f32p) if records else None, _p(xt, _f32p) if records else None,
-                                _p(end, _u64p), n_threads, _p(sx, _f32p) if records else None)
-    return {"pixels": pixels, "rays": rays, "image_xy": xy, "xyzT": xt, "surf_xyz": sx, "end_draws": end, "n_samples": n, "unsupported_hits": bool(rc)}
+                                _p(end, _u64p), n_threads, _p(sx, _f32p) if records else None, _p(sc, _u32p) if records else None)
+    return {"pixels": pixels, "rays": rays, "image_xy": xy, "xyzT": xt, "surf_xyz": sx, "end_draws": end, "n_samples": n, "unsupported_hits": bool(rc),
+            "spec_segments": sc[:, 0].copy(), "spec_depth": sc[:, 1].copy(), "spec_both": sc[:, 2].copy()}

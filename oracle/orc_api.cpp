@@ -422,8 +422,9 @@ void orc_film_resolve(const pvol_film *film, const float *pixels, float *rgb) {
 // (optional) one per task.
 // PhotonIntegrator (integrators/photonmap.cpp) for the tile driver: "nused", "maxdist", "finalgather" and a caustic map built
 // from n photons (p, wo: 3 floats, alpha: 30 floats each; n == 0: no map) shot over n_paths paths.  on == 0 removes it.
-int orc_set_surface_integrator(orc_ctx *c, int on, int n_used, float max_dist, int final_gather, const float *p, const float *wo,
-                               const float *alpha, uint32_t n, uint32_t n_paths) {
+// orc_set_surface_integrator_depth: the same with "maxspeculardepth" (the reference's default is 5, photonmap.cpp:325).
+int orc_set_surface_integrator_depth(orc_ctx *c, int on, int n_used, float max_dist, int final_gather, const float *p, const float *wo,
+                                     const float *alpha, uint32_t n, uint32_t n_paths, int max_specular_depth) {
     delete c->causticMap;
     c->causticMap = 0;
     c->causticPhotons.clear();
@@ -437,17 +438,23 @@ int orc_set_surface_integrator(orc_ctx *c, int on, int n_used, float max_dist, i
         c->causticPhotons.push_back(ph);
     }
     if (n) c->causticMap = new KdTree(c->causticPhotons);
-    c->si.nLookup = n_used; c->si.maxDistSquared = max_dist * max_dist; c->si.maxSpecularDepth = 5; c->si.finalGather = final_gather != 0;
+    c->si.nLookup = n_used; c->si.maxDistSquared = max_dist * max_dist; c->si.maxSpecularDepth = max_specular_depth; c->si.finalGather = final_gather != 0;
     c->si.causticMap = c->causticMap; c->si.nCausticPaths = (int)n_paths;
     return 0;
 }
+int orc_set_surface_integrator(orc_ctx *c, int on, int n_used, float max_dist, int final_gather, const float *p, const float *wo,
+                               const float *alpha, uint32_t n, uint32_t n_paths) {
+    return orc_set_surface_integrator_depth(c, on, n_used, max_dist, final_gather, p, wo, alpha, n, n_paths, 5);
+}
 
-// returns 0, or 1 when a camera ray met a surface the surface integrator's restatement does not cover (specular BSDF)
-int orc_render_tasks(orc_ctx *c, const pvol_camera *cam, const pvol_film *film, const pvol_sampler *smp, const uint32_t *task_ids,
-                     uint32_t n_task_ids, float *pixels, pvol_ray *rays, float *imageXY, float *xyzT, uint64_t *end_draws, int n_threads,
-                     float *surfXYZ) {
+// returns 0, or 1 when a camera ray met a surface the surface integrator's restatement does not cover (specular BSDF).
+// specCounts (optional, 3 per sample, only with a surface integrator): the rays the specular recursion spawned for the sample
+// (segments), the deepest ray.depth among them, and the glass hits at which both lobes spawned a ray.
+int orc_render_tasks_counts(orc_ctx *c, const pvol_camera *cam, const pvol_film *film, const pvol_sampler *smp, const uint32_t *task_ids,
+                            uint32_t n_task_ids, float *pixels, pvol_ray *rays, float *imageXY, float *xyzT, uint64_t *end_draws, int n_threads,
+                            float *surfXYZ, uint32_t *specCounts) {
     Integrator I = make_integrator(c);
-    const bool wantRec = rays || imageXY || xyzT || surfXYZ;
+    const bool wantRec = rays || imageXY || xyzT || surfXYZ || specCounts;
     std::atomic<int> unsupported(0);
     std::vector<uint64_t> first(n_task_ids + 1, 0);
     for (uint32_t i = 0; i < n_task_ids; ++i) {
@@ -467,11 +474,13 @@ int orc_render_tasks(orc_ctx *c, const pvol_camera *cam, const pvol_film *film, 
             if (i >= n_task_ids) break;
             std::vector<pvol_ray> r;
             std::vector<float> xy, xt, sx;
-            TileRecords rec = {&r, &xy, &xt, (surfXYZ && c->have_si) ? &sx : 0};
+            std::vector<uint32_t> sc;
+            TileRecords rec = {&r, &xy, &xt, (surfXYZ && c->have_si) ? &sx : 0, (specCounts && c->have_si) ? &sc : 0};
             bool sup = true;
             uint64_t d = render_task(I, *cam, *smp, task_ids[i], pixels ? &F : 0, wantRec ? &rec : 0, &local, c->have_si ? &c->si : 0, &sup);
             if (!sup) unsupported = 1;
             if (surfXYZ && c->have_si) memcpy(surfXYZ + 3 * first[i], sx.data(), sizeof(float) * sx.size());
+            if (specCounts && c->have_si) memcpy(specCounts + 3 * first[i], sc.data(), sizeof(uint32_t) * sc.size());
             if (end_draws) end_draws[i] = d;
             if (rays) memcpy(rays + first[i], r.data(), sizeof(pvol_ray) * r.size());
             if (imageXY) memcpy(imageXY + 2 * first[i], xy.data(), sizeof(float) * xy.size());
@@ -488,6 +497,11 @@ int orc_render_tasks(orc_ctx *c, const pvol_camera *cam, const pvol_film *film, 
         for (auto &t : th) t.join();
     }
     return unsupported.load();
+}
+int orc_render_tasks(orc_ctx *c, const pvol_camera *cam, const pvol_film *film, const pvol_sampler *smp, const uint32_t *task_ids,
+                     uint32_t n_task_ids, float *pixels, pvol_ray *rays, float *imageXY, float *xyzT, uint64_t *end_draws, int n_threads,
+                     float *surfXYZ) {
+    return orc_render_tasks_counts(c, cam, film, smp, task_ids, n_task_ids, pixels, rays, imageXY, xyzT, end_draws, n_threads, surfXYZ, 0);
 }
 
 }  // extern "C"

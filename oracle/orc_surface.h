@@ -39,9 +39,13 @@ inline float photon_kernel(V3 photonP, V3 p, float maxDist2) {
     return 3.f * kInvPi * s * s;
 }
 
+struct SpecCounts {   // the shape of one camera sample's tree, for the tests: rays spawned (segments), the deepest ray.depth among
+    uint32_t nSeg, maxLevel, nBoth;   // them, and the glass hits at which SpecularReflect and SpecularTransmit both spawned one
+};
 struct SpecCtx {   // what the specular recursion carries besides the ray: the camera sample's scatter offset (every nested
     float scatterU;             // volume Li() reads the SAME Sample, samplerrenderer.cpp:247) and the volume integrator's scratch
     std::vector<float> *scratch;
+    SpecCounts *counts;         // optional
 };
 inline Spec surface_li(const Integrator &I, const SurfaceIntegrator &S, const Ray &ray, const Hit &isect, Rng &rng, Counters *ctr,
                        std::vector<ClosePhoton> &lookupBuf, bool *supported, int depth = 0, const SpecCtx *sx = 0);
@@ -62,7 +66,7 @@ inline Spec renderer_li(const Integrator &I, const SurfaceIntegrator &S, Ray ray
 // them): BSDFSample(rng) draws three numbers, Sample_f is restricted to the one specular lobe, the spawned ray starts at
 // rayEpsilon and carries depth + 1.
 inline Spec specular_bounce(const Integrator &I, const SurfaceIntegrator &S, const Ray &ray, const Hit &isect, int lobe, int depth, Rng &rng,
-                            Counters *ctr, std::vector<ClosePhoton> &lookupBuf, bool *supported, const SpecCtx &sx) {
+                            Counters *ctr, std::vector<ClosePhoton> &lookupBuf, bool *supported, const SpecCtx &sx, bool *spawned = 0) {
     const float u0 = rng.random_float(), u1 = rng.random_float(), uc = rng.random_float();   // BSDFSample(RNG&), reflection.h:491-495
     const V3 wo = -ray.d;
     V3 wi = v3(0.f, 0.f, 0.f);
@@ -72,6 +76,8 @@ inline Spec specular_bounce(const Integrator &I, const SurfaceIntegrator &S, con
     Spec L = spec_const(0.f);
     if (pdf > 0.f && !is_black(f) && fabsf(dot(wi, isect.nn)) != 0.f) {
         Ray rd = make_ray(isect.p, wi, isect.rayEpsilon, kInfinity, ray.time);
+        if (spawned) *spawned = true;
+        if (sx.counts) { ++sx.counts->nSeg; sx.counts->maxLevel = std::max(sx.counts->maxLevel, (uint32_t)(depth + 1)); }
         Spec Li = renderer_li(I, S, rd, depth + 1, rng, ctr, lookupBuf, supported, sx);
         L = f * Li * (fabsf(dot(wi, isect.nn)) / pdf);
     }
@@ -91,8 +97,10 @@ inline Spec surface_li(const Integrator &I, const SurfaceIntegrator &S, const Ra
         // draw: the transmittance of the shadow ray is only asked for when f is not black, core/integrator.cpp:131-134);
         // LPhoton returns before its rho() draws (no non-specular component, photonmap.cpp:66-68).
         if (depth + 1 < S.maxSpecularDepth) {
-            L = L + specular_bounce(I, S, ray, isect, BSDF_REFLECTION, depth, rng, ctr, lookupBuf, supported, *sx);
-            L = L + specular_bounce(I, S, ray, isect, BSDF_TRANSMISSION, depth, rng, ctr, lookupBuf, supported, *sx);
+            bool refl = false, trans = false;
+            L = L + specular_bounce(I, S, ray, isect, BSDF_REFLECTION, depth, rng, ctr, lookupBuf, supported, *sx, &refl);
+            L = L + specular_bounce(I, S, ray, isect, BSDF_TRANSMISSION, depth, rng, ctr, lookupBuf, supported, *sx, &trans);
+            if (refl && trans && sx->counts) ++sx->counts->nBoth;
         }
         return L;
     }

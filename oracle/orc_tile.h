@@ -156,6 +156,7 @@ struct TileRecords {   // optional per-sample records of render_task
     std::vector<pvol_ray> *rays;
     std::vector<float> *imageXY, *xyzT;
     std::vector<float> *surfXYZ;   // surface integrator's Li as X, Y, Z (only with a surface integrator)
+    std::vector<uint32_t> *specCounts;   // per sample: rays the specular recursion spawned, the deepest ray.depth, hits that spawned both lobes
 };
 
 // SamplerRendererTask::Run, renderers/samplerrenderer.cpp:59-157, with Ls = Lvi (no surface term) and the
@@ -183,7 +184,8 @@ inline uint64_t render_task(const Integrator &I, const pvol_camera &cam, const p
                 const bool hitSurface = scene_intersect(*I.scene, &ray, &hit);   // SamplerRenderer::Li, samplerrenderer.cpp:236-249: clips ray.maxt
                 Spec Lsurf = spec_const(0.f);
                 const uint64_t ds0 = rng.draws;
-                SpecCtx sx = {ps.scatter[i], &scratch};
+                SpecCounts sc = {0u, 0u, 0u};
+                SpecCtx sx = {ps.scatter[i], &scratch, &sc};
                 if (SI && hitSurface) Lsurf = surface_li(I, *SI, ray, hit, rng, ctr, lookupBuf, supported, 0, &sx);
                 const uint64_t surfDraws = rng.draws - ds0;
                 Spec T;
@@ -207,6 +209,7 @@ inline uint64_t render_task(const Integrator &I, const pvol_camera &cam, const p
                     rec->imageXY->push_back(ps.imageX[i]); rec->imageXY->push_back(ps.imageY[i]);
                     rec->xyzT->push_back(xyz[0]); rec->xyzT->push_back(xyz[1]); rec->xyzT->push_back(xyz[2]);
                     rec->xyzT->push_back(spec_y(cie, T));
+                    if (rec->specCounts) { rec->specCounts->push_back(sc.nSeg); rec->specCounts->push_back(sc.maxLevel); rec->specCounts->push_back(sc.nBoth); }
                     if (rec->surfXYZ) { float sx[3]; spec_xyz(cie, Lsurf, sx); rec->surfXYZ->push_back(sx[0]); rec->surfXYZ->push_back(sx[1]); rec->surfXYZ->push_back(sx[2]); }
                 }
             }

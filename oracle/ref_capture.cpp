@@ -454,7 +454,7 @@ static int cmdRender(const std::string &name, const char *photonPath, const char
     // SurfaceIntegrator parameters on a caustic map built from the given photons (oracle-shot: the reference's shooter does
     // not link here); Ls then is T * Lsurface + Lvi as SamplerRenderer::Li composes it
     const char *causticPath = NULL;
-    int surfNused = 300, surfGatherSamples = 64;
+    int surfNused = 300, surfGatherSamples = 64, surfSpecDepth = -1;   // -1: not given, the reference's own default (5)
     float surfMaxDist = .15f;
     bool surfFinalGather = true;
     std::vector<uint32_t> tasks;
@@ -470,6 +470,7 @@ static int cmdRender(const std::string &name, const char *photonPath, const char
         else if (!strcmp(argv[i], "surfnused")) surfNused = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "surfmaxdist")) surfMaxDist = (float)atof(argv[i + 1]);
         else if (!strcmp(argv[i], "surffinalgather")) surfFinalGather = atoi(argv[i + 1]) != 0;
+        else if (!strcmp(argv[i], "surfspecdepth")) surfSpecDepth = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "tasks")) {
             const char *q = argv[i + 1];
             while (*q) { tasks.push_back((uint32_t)strtoul(q, (char **)&q, 10)); if (*q == ',') ++q; }
@@ -511,6 +512,7 @@ static int cmdRender(const std::string &name, const char *photonPath, const char
         sp.AddFloat("maxdist", &surfMaxDist, 1);
         sp.AddBool("finalgather", &surfFinalGather, 1);
         sp.AddInt("finalgathersamples", &surfGatherSamples, 1);
+        if (surfSpecDepth >= 0) sp.AddInt("maxspeculardepth", &surfSpecDepth, 1);
         si = CreatePhotonMapSurfaceIntegrator(sp, psh);
     }
     CaptureRenderer renderer(vi, si);
@@ -628,6 +630,7 @@ static int cmdRender(const std::string &name, const char *photonPath, const char
         int32_t sn[3] = {surfNused, surfFinalGather ? 1 : 0, psh->nCausticPaths};
         out.putf("surf.params.f", sf, 1);
         out.put("surf.params.i", blob::I32, sn, 3);
+        if (surfSpecDepth >= 0) out.puti1("surf.maxspeculardepth", surfSpecDepth);
     }
     out.put("task.window", blob::I32, windows.data(), windows.size());
     out.put("task.end_draw", blob::U64, endDraws.data(), endDraws.size());
@@ -638,10 +641,14 @@ static int cmdRender(const std::string &name, const char *photonPath, const char
             pix.push_back(px.Lxyz[0]); pix.push_back(px.Lxyz[1]); pix.push_back(px.Lxyz[2]); pix.push_back(px.weightSum);
         }
     out.putf("film.pixels", pix);
-    float *rgb = NULL;
-    int fwid = 0, fhei = 0;
-    film->WriteRGB(&rgb, &fwid, &fhei, 1.f);
-    out.putf("film.rgb", rgb, (size_t)3 * fwid * fhei);
+    // a capture at a given maxspeculardepth is about the surface term: the resolved image, a function of film.pixels that the
+    // other captures pin, is left out of it, so that it stays no larger than the capture of the same frame without the depth
+    if (surfSpecDepth < 0) {
+        float *rgb = NULL;
+        int fwid = 0, fhei = 0;
+        film->WriteRGB(&rgb, &fwid, &fhei, 1.f);
+        out.putf("film.rgb", rgb, (size_t)3 * fwid * fhei);
+    }
     return out.save(outPath) ? 0 : 1;
 }
 
@@ -875,6 +882,8 @@ int main(int argc, char **argv) {
     if (argc >= 5 && !strcmp(argv[1], "render")) return cmdRender(argv[2], argv[3], argv[4], argc - 5, argv + 5);
     if (argc >= 6 && !strcmp(argv[1], "li")) return cmdLi(argv[2], argv[3], argv[4], argv[5], argc - 6, argv + 6);
     fprintf(stderr,
-            "usage: ref_capture tables OUT | scene NAME OUT | shimscene NAME OUT | units NAME OUT | hits NAME RAYS OUT | li NAME PHOTONS|- RAYS OUT [stepsize v] [nused v] [maxdist v]\n");
+            "usage: ref_capture tables OUT | scene NAME OUT | shimscene NAME OUT | units NAME OUT | hits NAME RAYS OUT | li NAME PHOTONS|- RAYS OUT [stepsize v] [nused v] [maxdist v] | "
+            "render NAME PHOTONS|- OUT [xres v] [yres v] [spp v] [ntasks v] [tasks a,b,..] [stepsize v] [nused v] [maxdist v] "
+            "[surface CAUSTIC|- [surfnused v] [surfmaxdist v] [surffinalgather 0|1] [surfspecdepth v]]\n");
     return 64;
 }

@@ -354,8 +354,9 @@ static void buildMeshRoom(BuiltScene &B, int nu, int nv) {
 
 // projectScene/scene.pbrt: a glass ball (Shape "sphere", index 1.5, Vn 0: no dispersion) in the medium, spot + point light,
 // three matte walls.  `extra` adds a second, partial matte sphere under a rotation and a non-uniform scale, so that zmin / zmax
-// / phimax clipping, the second root and a general ObjectToWorld are exercised too.
-static void buildSphereScene(BuiltScene &B, bool extra) {
+// / phimax clipping, the second root and a general ObjectToWorld are exercised too.  `glassKr` is the grey Kr of the
+// ball's glass: 0 in the scene file (camera paths through it are chains), > 0 gives the reflective lobe too (trees).
+static void buildSphereScene(BuiltScene &B, bool extra, float glassKr = 0.f) {
     B.stepSize = .05f; B.nUsed = 300; B.maxDist = 0.5f; B.nVolumePhotons = 1000000;
     B.shooterStep = 0.1f; B.maxPhotonDepth = 5; B.nCaustic = 50000; B.nIndirect = 0; B.finalGather = 1;
     B.xres = B.yres = 300; B.spp = 8; B.fov = 70.f;
@@ -368,7 +369,7 @@ static void buildSphereScene(BuiltScene &B, bool extra) {
     addSpot(B, ctm, sf, st, 2500.f, 6.f);
     float pf[3] = {0, 2, -4};
     addPoint(B, ctm, pf, 8.f);
-    float kr[3] = {0, 0, 0}, kt[3] = {1, 1, 1};
+    float kr[3] = {glassKr, glassKr, glassKr}, kt[3] = {1, 1, 1};
     int glass = addGlass(B, 1.5f, 0.f, kr, kt);
     addSphere(B, ctm * Translate(Vector(0, 2, 0)), .6f, -.6f, .6f, 360.f, glass);
     int matte = addMatte(B, .6f, .6f, .9f);
@@ -490,6 +491,7 @@ static bool buildByName(BuiltScene &B, const std::string &name) {
     else if (name == "meshroom") buildMeshRoom(B, 32, 16);
     else if (name == "spherescene") buildSphereScene(B, false);
     else if (name == "sphereroom") buildSphereScene(B, true);
+    else if (name == "sphereroom_kr") buildSphereScene(B, true, 0.25f);   // reflective glass: SpecularReflect and SpecularTransmit both spawn
     else if (name == "meshroom_big") buildMeshRoom(B, 256, 128);
     else if (name == "spherezoo") buildSphereZoo(B);
     else if (name == "trizoo") buildTriZoo(B, false);

@@ -133,3 +133,39 @@ def test_reference_scene_parameters_as_written():
     d = ps.load(os.path.join(REF_SCENES, "pinkfloyd.pbrt"))
     assert int(d["params.i"][0]) == 500 and int(d["surf.params.i"][0]) == 50
     assert abs(float(d["params.f"][2]) - 0.1) < 1e-7
+
+
+@pytest.mark.parametrize("depth,final_gather,stored_indirect,entry", [(3, "true", 0, "set_surface_integrator"), (0, "false", 0, "set_surface_integrator"),
+                                                                      (2, "false", 700, "set_surface_integrator_maps")])
+def test_scene_file_maxspeculardepth_reaches_the_surface_integrator(tmp_path, depth, final_gather, stored_indirect, entry):
+    """`"integer maxspeculardepth"` of SurfaceIntegrator "photonmap" goes through pbrt_scene.load into surf.params.i[1] and from there,
+    in tools/render_pbrt.py, into the max_specular_depth argument of the entry point the frame takes -- on every context."""
+    import inspect
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import render_pbrt
+    pvol = importlib.import_module("cs348b-pbrt_amd.pvol")
+    f = tmp_path / "m.pbrt"
+    f.write_text('Camera "perspective"\nSurfaceIntegrator "photonmap" "integer maxspeculardepth" [%d] "bool finalgather" ["%s"] "integer nused" [70]\n'
+                 'VolumeIntegrator "photonvolume"\nWorldBegin\n'
+                 'Shape "trianglemesh" "integer indices" [0 1 2] "point P" [0 0 0  1 0 0  0 1 0]\nWorldEnd\n' % (depth, final_gather))
+    d = ps.load(str(f))
+    assert list(d["surf.params.i"])[:3] == [70, depth, int(final_gather == "true")]
+
+    class Recorder:
+        def __init__(self):
+            self.calls = []
+
+        def set_surface_integrator(self, *a, **kw):
+            self.calls.append(("set_surface_integrator", inspect.signature(pvol.PhotonVolume.set_surface_integrator).bind(self, *a, **kw).arguments))
+
+        def set_surface_integrator_maps(self, *a, **kw):
+            self.calls.append(("set_surface_integrator_maps", inspect.signature(pvol.PhotonVolume.set_surface_integrator_maps).bind(self, *a, **kw).arguments))
+    pvs = [Recorder(), Recorder()]
+    render_pbrt.apply_surface_integrator(pvs, d, stored_indirect)
+    for q in pvs:
+        assert len(q.calls) == 1 and q.calls[0][0] == entry
+        args = q.calls[0][1]
+        assert args["max_specular_depth"] == depth and args["n_used"] == 70 and args["final_gather"] == (final_gather == "true")
+        assert args["from_preprocess"] is True

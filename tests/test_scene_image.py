@@ -39,7 +39,7 @@ TEXTURED = {"projectScene/rainbow_png.pbrt", "projectScene/rainbow2_png.pbrt"}
 
 def test_the_golden_set_is_the_one_the_suite_loads():
     names = [n for n, _ in _golden_scenes()]
-    assert len([n for n in names if n.endswith(".bin")]) == 12 and len(names) == 12 + 4 + 10   # 12: with the hit zoos spherezoo, trizoo, trizoo_h
+    assert len([n for n in names if n.endswith(".bin")]) == 13 and len(names) == 13 + 4 + 10   # 13: with the hit zoos spherezoo, trizoo, trizoo_h and sphereroom_kr
 
 
 @pytest.mark.parametrize("name,path", _golden_scenes(), ids=[n for n, _ in _golden_scenes()])

@@ -27,6 +27,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def apply_surface_integrator(pvs, scene, stored_indirect):
+    """The scene file's SurfaceIntegrator "photonmap" on every context of `pvs`: nused, maxdist, maxspeculardepth and finalgather as
+    the file states them (or the reference's defaults), the maps taken from the last preprocess.  `finalgather false` with indirect
+    photons: LPhoton over both stores (set_surface_integrator_maps).  Everything else takes the caustic-only entry point, which
+    refuses an indirect map by name -- `finalgather true` with one is the final gather."""
+    final_gather = bool(scene["surf.params.i"][2])
+    both_maps = not final_gather and stored_indirect > 0
+    for q in pvs:
+        setter = q.set_surface_integrator_maps if both_maps else q.set_surface_integrator
+        setter(int(scene["surf.params.i"][0]), float(scene["surf.params.f"][0]), int(scene["surf.params.i"][1]), final_gather,
+               from_preprocess=True)
+
+
 def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_tasks=2048, surface=True, log=print, caustic_photons=None,
                       devices=None, cropwindow=None, phases=False, indirect_photons=None):
     """cropwindow: (x0, x1, y0, y1) overrides the file's; None keeps it (the whole frame when the file names none).
@@ -79,15 +92,8 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
                                                                                         st["paths"]))
         used_surface = False
         if surface and scene["surf.name"] == "photonmap":
-            # `finalgather false` with indirect photons: LPhoton over both stores (set_surface_integrator_maps).  Everything else takes
-            # the caustic-only entry point, which refuses an indirect map by name -- `finalgather true` with one is the final gather
-            final_gather = bool(scene["surf.params.i"][2])
-            both_maps = not final_gather and st["stored_indirect"] > 0
             try:
-                for q in pvs:
-                    setter = q.set_surface_integrator_maps if both_maps else q.set_surface_integrator
-                    setter(int(scene["surf.params.i"][0]), float(scene["surf.params.f"][0]), int(scene["surf.params.i"][1]), final_gather,
-                           from_preprocess=True)
+                apply_surface_integrator(pvs, scene, st["stored_indirect"])
                 used_surface = True
             except pvol.PvolError as e:
                 log("surface integrator not applied (%s): the image holds the volume term only" % e)
