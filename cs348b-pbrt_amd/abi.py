@@ -285,6 +285,14 @@ class PhotonArray(C.Structure):   # pvol_photon_array: one surface map handed to
     _fields_ = [("p", C.POINTER(C.c_float)), ("wi", C.POINTER(C.c_float)), ("alpha", C.POINTER(C.c_float)), ("n", C.c_uint32), ("n_paths", C.c_uint32)]
 
 
+class LPhotonCheck(C.Structure):   # the arguments pvol_check_lphoton judges (csrc/pvol_host.h): pvol_lphoton_batch*'s pointers and numbers
+    _fields_ = [("p", C.c_void_p), ("w", C.c_void_p), ("n", C.c_uint32), ("output_kind", C.c_int32), ("out", C.c_void_p)]
+
+
+LPHOTON_SCRATCH_BYTES = 64 << 20   # PVOL_LPHOTON_SCRATCH_BYTES
+LPHOTON_POINT_SCRATCH = 16         # bytes of ordering scratch per point of a slice (csrc/pvol_host.h)
+
+
 def make_camera(raster_to_camera, camera_to_world, shutter_open=0.0, shutter_close=1.0, lens_radius=0.0, focal_distance=1e30):
     c = Camera()
     for i, v in enumerate(np.asarray(raster_to_camera, np.float32).reshape(16)):

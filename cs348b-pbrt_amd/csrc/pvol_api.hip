@@ -71,6 +71,7 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     { const char *ng = getenv("PVOL_NO_GROUP"); c->noGroup = ng && ng[0] == '1'; }
     { const char *nl = getenv("PVOL_NO_LITE"); c->noLite = nl && nl[0] == '1'; }
     { const char *nm = getenv("PVOL_NO_MOMENTS"); c->noMoments = nm && nm[0] == '1'; }
+    { const char *ns = getenv("PVOL_LPHOTON_NO_SORT"); c->lpNoSort = ns && ns[0] == '1'; }
     c->groupPrecore = pvol_precore_kappa(getenv("PVOL_GROUP_PRECORE"));
     { const char *tg = getenv("PVOL_TILE_GENERAL"); c->tileGeneral = tg && tg[0] == '1'; }
     { const char *gw = getenv("PVOL_GROUP_WAVES"); if (gw) c->groupWavesPerCU = std::max(1, atoi(gw)); }
@@ -100,6 +101,7 @@ void pvol_destroy(pvol_ctx *c) {
     for (auto &e : c->phasePool) hipEventDestroy(e);
     if (c->groupFilmEv) hipEventDestroy(c->groupFilmEv);
     if (c->groupStageEv) hipEventDestroy(c->groupStageEv);
+    if (c->lpEv) hipEventDestroy(c->lpEv);
     pvol_free_li_staging(c);
     delete c;
 }

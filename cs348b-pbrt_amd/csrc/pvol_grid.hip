@@ -39,6 +39,41 @@ __global__ void cell_keys_kernel(GridBuildArgs a, uint32_t *keys, uint32_t *vals
     vals[i] = i;
 }
 
+// pvol_lphoton_batch*: the cell of every query point by the photons' cell function -- a point outside the grid's box lands in the
+// nearest cell (cell_coord clamps) -- and the point's slot in the call's arrays as the value
+struct PointKeyArgs { const float *p; uint32_t first, n; float lo[3], inv; int32_t gdim[3]; };
+__global__ void point_keys_kernel(PointKeyArgs a, uint32_t *keys, uint32_t *vals) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const size_t s = (size_t)a.first + i;
+    int cx = cell_coord(a.p[3 * s], a.lo[0], a.inv, a.gdim[0]);
+    int cy = cell_coord(a.p[3 * s + 1], a.lo[1], a.inv, a.gdim[1]);
+    int cz = cell_coord(a.p[3 * s + 2], a.lo[2], a.inv, a.gdim[2]);
+    keys[i] = (uint32_t)((cz * a.gdim[1] + cy) * a.gdim[0] + cx);
+    vals[i] = a.first + i;
+}
+static int key_bits(unsigned long long nkeys) {
+    int bits = 1;
+    while ((1ull << bits) < nkeys) ++bits;
+    return bits;
+}
+// Orders the points [first, first + n) of d_p by the cell of grid G they fall in (stable: points of one cell stay in input order).
+// work: 4 n words (keys, sorted keys, slots, sorted slots); the sorted slots are its last n.  temp == 0: only *tempBytes is set, to
+// what a sort of n points needs.  Enqueued on `stream`, not synchronised.
+extern "C" hipError_t pvol_order_points(const PhotonGrid *G, const float *d_p, uint32_t first, uint32_t n, uint32_t *work, void *temp,
+                                        size_t *tempBytes, hipStream_t stream) {
+    uint32_t *keysIn = work, *keysOut = work + n, *valsIn = work + 2 * (size_t)n, *valsOut = work + 3 * (size_t)n;
+    const int bits = key_bits((unsigned long long)G->cells());
+    if (!temp) return hipcub::DeviceRadixSort::SortPairs(0, *tempBytes, keysIn, keysOut, valsIn, valsOut, (int)n, 0, bits, stream);
+    PointKeyArgs a;
+    a.p = d_p; a.first = first; a.n = n; a.inv = G->invCell;
+    for (int i = 0; i < 3; ++i) { a.lo[i] = G->gridLo[i]; a.gdim[i] = G->gdim[i]; }
+    hipLaunchKernelGGL(point_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a, keysIn, valsIn);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return hipcub::DeviceRadixSort::SortPairs(temp, *tempBytes, keysIn, keysOut, valsIn, valsOut, (int)n, 0, bits, stream);
+}
+
 // sorted slot j <- photon order[j]; one 8-lane group writes one 128-B alpha row
 __global__ void scatter_photons_kernel(GridBuildArgs a, const uint32_t *order, float4 *pos4, float4 *alpha4, float4 *wi4) {
     uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;

@@ -66,6 +66,7 @@ extern "C" size_t pvol_tile_lds_bytes(int maxSteps, uint32_t spp, bool fused, in
 extern "C" hipError_t pvol_launch_tile(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream, int wavesPerTask,
                                        bool plain, const char **form);
 extern "C" hipError_t pvol_launch_li_par(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, hipStream_t stream);
+extern "C" hipError_t pvol_launch_lphoton_points(const PointsArgs *args, int candCap, uint32_t nWaves, hipStream_t stream);
 // The launchers of one compilation of the marching kernels: VolumeGridDensity (and every medium that is no density region) or, from
 // pvol_march_exp.hip, ExponentialDensity (pvol_region_exp.h).  The host asks pvol_launchers(kind) wherever a launched kernel may
 // evaluate a density; launchers that never do (spec_compose, spec_fill) are called directly.
@@ -77,6 +78,7 @@ struct RegionLaunchers {
     decltype(&pvol_launch_li_par) liPar;
     decltype(&pvol_launch_surface) surface;
     decltype(&pvol_launch_tile) tile;
+    decltype(&pvol_launch_lphoton_points) lphotonPoints;
 };
 #if !PVOL_REGION_EXP   /* undefined or 0: the first compilation and the host units */
 extern "C" hipError_t pvol_launch_li_seq_exp(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, hipStream_t stream);
@@ -90,11 +92,12 @@ extern "C" hipError_t pvol_launch_li_par_exp(const LiArgs *args, size_t ldsBytes
 extern "C" hipError_t pvol_launch_surface_exp(const SurfArgs *a, uint32_t nWaves, hipStream_t stream);
 extern "C" hipError_t pvol_launch_tile_exp(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream,
                                            int wavesPerTask, bool plain, const char **form);
+extern "C" hipError_t pvol_launch_lphoton_points_exp(const PointsArgs *args, int candCap, uint32_t nWaves, hipStream_t stream);
 static inline const RegionLaunchers &pvol_launchers(int volKind) {
     static const RegionLaunchers base = {pvol_launch_li_seq, pvol_launch_li_slice, pvol_launch_li_group, pvol_launch_li_replay, pvol_launch_li_par,
-                                         pvol_launch_surface, pvol_launch_tile};
+                                         pvol_launch_surface, pvol_launch_tile, pvol_launch_lphoton_points};
     static const RegionLaunchers expo = {pvol_launch_li_seq_exp, pvol_launch_li_slice_exp, pvol_launch_li_group_exp, pvol_launch_li_replay_exp,
-                                         pvol_launch_li_par_exp, pvol_launch_surface_exp, pvol_launch_tile_exp};
+                                         pvol_launch_li_par_exp, pvol_launch_surface_exp, pvol_launch_tile_exp, pvol_launch_lphoton_points_exp};
     return volKind == PVOL_VOLUME_EXPONENTIAL ? expo : base;
 }
 #endif
@@ -120,6 +123,7 @@ enum {
     PVOL_BUF_LI_IN, PVOL_BUF_LI_OUT,    // device staging of the coalesced per-sample batches (pvol_li_coalesce.hip)
     PVOL_BUF_GROUP_STAGE,               // pvol_render_frame_group: the other contexts' films next to the root's
     PVOL_BUF_FG_DIRS, PVOL_BUF_FG_RAYS, // pvol_final_gather* (pvol_final_gather.hip): a slice's direction records and ray records
+    PVOL_BUF_LP_ORDER, PVOL_BUF_LP_TEMP, // pvol_lphoton_batch* (pvol_lphoton.hip): a slice's cell keys and slots (pvol_order_points), the sort's own scratch
     PVOL_N_BUFS
 };
 extern "C" bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream);
@@ -224,6 +228,10 @@ struct pvol_ctx {
     RadianceResult rad;    // pvol_compute_radiance*: dropped by every shoot and by pvol_free_surface_stores
     GatherMap gather;      // pvol_build_gather_map*: dropped wherever `rad` is
     uint64_t fgScratchBound = 0;   // pvol_final_gather_set_scratch_bound (tests): bytes of scratch a slice may take, 0 = PVOL_FINAL_GATHER_SCRATCH_BYTES
+    // pvol_lphoton_batch* (pvol_lphoton.hip)
+    bool lpNoSort = false;         // PVOL_LPHOTON_NO_SORT=1: the points are served in the caller's order (testing; the results are the same bytes)
+    uint64_t lpScratchBound = 0;   // pvol_lphoton_set_scratch_bound (tests): bytes of ordering scratch a slice may take, 0 = PVOL_LPHOTON_SCRATCH_BYTES
+    hipEvent_t lpEv = 0;           // the end of the last call's kernels: the next call, on whatever stream, reuses their scratch behind it
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     PhotonGrid causticMap;
     // ... and its indirect map (pvol_set_surface_integrator_maps: LPhoton(indirectMap) without the final gather), built by the same builder
@@ -389,6 +397,19 @@ int pvol_check_final_gather(int haveCtx, const FinalGatherCheck *args, int haveS
 uint32_t pvol_final_gather_slice(int32_t nSamples, uint64_t bound);
 // lowers (or, with 0, restores) the scratch bound of this context's pvol_final_gather* calls, for the tests
 int pvol_final_gather_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
+// every status of pvol_lphoton_batch* in its one order (include/pvol.h), reachable without a device for the tests (pvol_lphoton.hip);
+// no HIP call.  args: the call's pointers and numbers; g: the medium's HG parameter (0 without a scene)
+struct LPhotonCheck { const float *p, *w; uint32_t n; int32_t outputKind; const void *out; };
+int pvol_check_lphoton(int haveCtx, const LPhotonCheck *args, int haveScene, float g);
+// points per slice of pvol_lphoton_batch*: as many as keep a slice's ordering scratch (PVOL_LPHOTON_POINT_SCRATCH bytes per point)
+// within `bound` bytes (0 or more than PVOL_LPHOTON_SCRATCH_BYTES: that), whole runs of 64 where that many fit, never fewer than one
+#define PVOL_LPHOTON_POINT_SCRATCH 16u
+uint32_t pvol_lphoton_slice(uint64_t bound);
+// lowers (or, with 0, restores) the scratch bound of this context's pvol_lphoton_batch* calls, for the tests
+int pvol_lphoton_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
+// the points [first, first + n) of d_p ordered by their cell of G (pvol_grid.hip)
+hipError_t pvol_order_points(const PhotonGrid *G, const float *d_p, uint32_t first, uint32_t n, uint32_t *work, void *temp, size_t *tempBytes,
+                             hipStream_t stream);
 // the shoot's merge (ShootMerge, pvol_shoot_merge.h) replayed over recorded count tables, for the tests (pvol_shoot_host.hip)
 size_t pvol_shoot_merge_replay(const uint32_t *cfg, const uint32_t *tables, uint32_t nTables, uint64_t *out, size_t cap);
 // the plan of a render call (RenderPlan below) flattened for the tests (pvol_render_host.hip)

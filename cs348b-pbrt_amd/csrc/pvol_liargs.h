@@ -36,4 +36,16 @@ struct LiArgs {
     int32_t moments;            // li_group_kernel, ray-parallel XYZ form: sum the map's moment rows (BatchPlan::groupForm 3)
     float grpPrecore;           // li_group_kernel: kappa of the settled class (theta = kappa x the smallest guessed k-th distance^2 served), 0 = off
 };
+// One slice of pvol_lphoton_batch* (lphoton_points_kernel, pvol_points_dev.h): LPhoton at the caller's points.  p, w, out, nFound and
+// radius2 are the CALL's arrays, indexed by the point's input slot; order lists the slice's slots in the order the waves serve them.
+struct PointsArgs {
+    const DevScene *scene;
+    const float *p, *w;         // [call's n][3]; w == 0: no direction (g == 0 reads none)
+    const uint32_t *order;      // [n] input slots, sorted by grid cell (pvol_order_points); 0: first, first + 1, ...
+    uint32_t first, n;          // the slice: n lookups, and where the unsorted order starts
+    int32_t spectral;
+    float *out;                 // 30 floats per point, or X, Y, Z, 0
+    uint32_t *nFound;           // optional
+    float *radius2;             // optional
+};
 #endif

@@ -118,11 +118,16 @@ __device__ float select_k(Gather &G, int M, int k, float T, int lane) {
 // returns total flux / (4/3 pi r^3 sigma_s) in the float4 layout, or 0 when fewer than 10 are found.
 // `guess` (> 0) is a previous k-th distance^2 at a nearby point; `rkOut` returns this lookup's
 // (0 when fewer than k photons lie within maxDist).
-template <bool STATS, int NREG, bool FINE = false>
-__device__ f4 lphoton(const DevScene &S, Gather &G, V3 w, V3 pt, f4 sigS_at_p, int lane, WaveCounters &wc, float guess, float *rkOut) {
+// REPORT (lphoton_points_kernel, pvol_points_dev.h): 1 also reports proc.nFound and the reference's maxmd (the largest kept
+// distance^2, 0 when nothing was kept), 2 reports them and returns before the flux sum.  The default 0 compiles both out and the two
+// pointers with them: the march and group kernels hold the instructions they held before.
+template <bool STATS, int NREG, bool FINE = false, int REPORT = 0>
+__device__ f4 lphoton(const DevScene &S, Gather &G, V3 w, V3 pt, f4 sigS_at_p, int lane, WaveCounters &wc, float guess, float *rkOut,
+                      int *nFoundOut = nullptr, float *maxmdOut = nullptr) {
     const int q = lane & 7;
     f4 zero = mk4(0.f);
     *rkOut = 0.f;
+    if (REPORT) { *nFoundOut = 0; *maxmdOut = 0.f; }
     if (S.nPhotons == 0u) return zero;
     const GridView gv = volume_grid(S);
     const int k = S.nUsed;
@@ -257,6 +262,8 @@ __device__ f4 lphoton(const DevScene &S, Gather &G, V3 w, V3 pt, f4 sigS_at_p, i
         if (nFound < 10) wc.lt10 += 1; else wc.kept += (unsigned long long)nFound;
     }
     if (nFound == k) *rkOut = maxmd;
+    if (REPORT) { *nFoundOut = nFound; *maxmdOut = maxmd; }
+    if (REPORT == 2) return zero;
     if (nFound < 10) return zero;   // photonvolume.cpp:83-84
     // totalFlux += alpha * p(pt_i, wi_i, -w): 8 photons per pass, one 128-B row per 8-lane group
     const int grp = lane >> 3;
@@ -1432,6 +1439,7 @@ extern "C" hipError_t pvol_launch_li_replay(const LiArgs *args, size_t ldsReplay
 }
 
 #include "pvol_group_dev.h"
+#include "pvol_points_dev.h"   // lphoton_points_kernel: LPhoton at the caller's points (pvol_lphoton_batch*)
 #include "pvol_surface_dev.h"
 #include "pvol_spec_dev.h"
 #include "pvol_tile_dev.h"

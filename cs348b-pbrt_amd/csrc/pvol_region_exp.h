@@ -18,6 +18,7 @@
 #define li_group_kernel li_group_kernel_exp
 #define li_fixup_kernel li_fixup_kernel_exp
 #define li_fixup_group_kernel li_fixup_group_kernel_exp
+#define lphoton_points_kernel lphoton_points_kernel_exp
 #define stream_begin_kernel stream_begin_kernel_exp
 #define surface_kernel surface_kernel_exp
 #define spec_compose_kernel spec_compose_kernel_exp
@@ -34,6 +35,7 @@
 #define pvol_launch_li_slice pvol_launch_li_slice_exp
 #define pvol_launch_li_replay pvol_launch_li_replay_exp
 #define pvol_launch_li_group pvol_launch_li_group_exp
+#define pvol_launch_lphoton_points pvol_launch_lphoton_points_exp
 #define pvol_launch_surface pvol_launch_surface_exp
 #define pvol_launch_spec_compose pvol_launch_spec_compose_exp
 #define pvol_launch_spec_fill pvol_launch_spec_fill_exp

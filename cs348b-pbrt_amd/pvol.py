@@ -168,6 +168,12 @@ def lib():
         L.pvol_final_gather_slice.argtypes = [C.c_int32, C.c_uint64]
         L.pvol_final_gather_slice.restype = C.c_uint32
         L.pvol_final_gather_set_scratch_bound.argtypes = [C.c_void_p, C.c_uint64]
+        L.pvol_lphoton_batch.argtypes = [C.c_void_p, _f32p, _f32p, C.c_uint32, C.c_int, _f32p, _u32p, _f32p]
+        L.pvol_lphoton_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pvol_check_lphoton.argtypes = [C.c_int, C.POINTER(abi.LPhotonCheck), C.c_int, C.c_float]
+        L.pvol_lphoton_slice.argtypes = [C.c_uint64]
+        L.pvol_lphoton_slice.restype = C.c_uint32
+        L.pvol_lphoton_set_scratch_bound.argtypes = [C.c_void_p, C.c_uint64]
         L.pvol_probe_hits.argtypes =[C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _f32p, C.POINTER(C.c_int32)]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_set_surface_integrator_maps.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), C.POINTER(abi.PhotonArray), C.POINTER(abi.PhotonArray)]
@@ -229,7 +235,7 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_radiance_lookup", "pvol_radiance_lookup_device", "pvol_set_surface_integrator_maps",
            "pvol_build_gather_map", "pvol_build_gather_map_arrays", "pvol_gather_map_count", "pvol_gather_photons",
            "pvol_gather_photons_device", "pvol_gather_directions", "pvol_gather_directions_device", "pvol_final_gather",
-           "pvol_final_gather_device"]
+           "pvol_final_gather_device", "pvol_lphoton_batch", "pvol_lphoton_batch_device"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -579,6 +585,32 @@ class PhotonVolume:
     def final_gather_set_scratch_bound(self, nbytes):
         """Test hook: the bytes of scratch a slice of final_gather() may take (0: the header's PVOL_FINAL_GATHER_SCRATCH_BYTES)."""
         _check(lib().pvol_final_gather_set_scratch_bound(self._h, int(nbytes)), "pvol_final_gather_set_scratch_bound")
+
+    def lphoton_batch(self, points, w=None, output_kind=abi.OUT_SPECTRAL, want_counts=False):
+        """LPhoton (photonvolume.cpp:65-108) on the current volume map at points[n,3], in the caller's order: L[n,30], or X, Y, Z, 0
+        with OUT_XYZ.  w[n,3]: the direction LPhoton is given; None only where the medium's g is 0.  want_counts: also
+        (n_found[n], radius2[n]) -- proc.nFound and the largest kept fp32 distance^2."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1)
+        n = p.size // 3
+        if w is not None:
+            w = np.ascontiguousarray(w, np.float32).reshape(-1)
+            if w.size != 3 * n:
+                raise ValueError("lphoton_batch: %d points, %d directions" % (n, w.size // 3))
+        out = np.zeros((n, 30 if output_kind == abi.OUT_SPECTRAL else 4), np.float32)
+        found, r2 = (np.zeros(n, np.uint32), np.zeros(n, np.float32)) if want_counts else (None, None)
+        _check(lib().pvol_lphoton_batch(self._h, p.ctypes.data_as(_f32p), w.ctypes.data_as(_f32p) if w is not None else None, n, int(output_kind),
+                                        out.ctypes.data_as(_f32p), found.ctypes.data_as(_u32p) if want_counts else None,
+                                        r2.ctypes.data_as(_f32p) if want_counts else None), "pvol_lphoton_batch")
+        return (out, found, r2) if want_counts else out
+
+    def lphoton_batch_device(self, d_p, d_w, n, output_kind, d_out, d_n_found=0, d_radius2=0, hip_stream=0):
+        """Device-pointer variant (integers; d_w, d_n_found, d_radius2 may be 0): enqueue only, no synchronisation."""
+        _check(lib().pvol_lphoton_batch_device(self._h, d_p, d_w or None, n, int(output_kind), d_out, d_n_found or None, d_radius2 or None, hip_stream),
+               "pvol_lphoton_batch_device")
+
+    def lphoton_set_scratch_bound(self, nbytes):
+        """Test hook: the bytes of ordering scratch a slice of lphoton_batch() may take (0: the header's PVOL_LPHOTON_SCRATCH_BYTES)."""
+        _check(lib().pvol_lphoton_set_scratch_bound(self._h, int(nbytes)), "pvol_lphoton_set_scratch_bound")
 
     def check_errors(self):
         """Raises PvolError(PVOL_E_LIMIT) if a batch enqueued through a device entry point hit a kernel limit."""

@@ -541,6 +541,34 @@ int pvol_final_gather_device(pvol_ctx *ctx, const float *d_p, const float *d_fra
                              const float *d_u_bsdf, const float *d_u_photon, float *d_L, uint32_t *d_draws,
                              pvol_gather_ray *d_rays_bsdf, pvol_gather_ray *d_rays_photon, void *hip_stream);
 
+/* ---- LPhoton at explicit points
+ * PhotonVolumeIntegrator::LPhoton (integrators/photonvolume.cpp:65-108) on the current volume map, with the context's n_used and
+ * max_dist, at n points the caller names: the k-nearest-photon estimate of the in-scattered radiance the march evaluates at every
+ * step.  p, w: n x 3 floats, world space; w is the direction LPhoton is given (the phase function is p(photon.p, photon.wi, -w))
+ * and may be NULL only when the medium's g is 0.  out: n x 30 floats (PVOL_OUT_SPECTRAL), or n x 4 (PVOL_OUT_XYZ): X, Y, Z of
+ * the CIE projection, then 0.  n_found (optional): proc.nFound = min(n_used, photons with dist^2 < max_dist^2).  radius2
+ * (optional): the reference's maxmd, the largest fp32 DistanceSquared among the kept photons, 0 when none was kept.  Both are
+ * written even where n_found < 10 and out is therefore zero (photonvolume.cpp:83-84).  sigma_s is taken at the point: zero
+ * outside a homogeneous (or rainbow) extent, density x sigma_s in a VolumeGrid or exponential region; out is zero where it is
+ * black.  Results are in the caller's order; there are no atomics: two runs agree byte for byte, and a point's bytes do not depend
+ * on which other points share the call.  n == 0 does nothing.  The points are walked in slices whose ordering scratch (16 bytes a
+ * point, the context's) stays within PVOL_LPHOTON_SCRATCH_BYTES; PVOL_LPHOTON_NO_SORT=1 (read at pvol_create) serves the points in
+ * the caller's order instead of by grid cell, with the same bytes.
+ *
+ * Statuses, decided in this one order (pvol_check_lphoton):
+ *   1. PVOL_E_INVALID      NULL ctx
+ *   2. PVOL_E_INVALID      an unknown output_kind; with n > 0: a NULL p or out, or a NULL w under a medium with g != 0
+ *   3. PVOL_E_NO_SCENE
+ *   then PVOL_E_NO_DEVICE / PVOL_E_NO_MEMORY from the device.  No map, or an empty one: PVOL_OK and zeros everywhere.  A rejected
+ *   call writes nothing.
+ * The host form holds the context from upload to copy-back; the device form takes DEVICE pointers, is enqueued on `hip_stream`
+ * and not synchronised. */
+#define PVOL_LPHOTON_SCRATCH_BYTES (64ull << 20)
+int pvol_lphoton_batch(pvol_ctx *ctx, const float *p, const float *w, uint32_t n, int output_kind, float *out, uint32_t *n_found,
+                       float *radius2);
+int pvol_lphoton_batch_device(pvol_ctx *ctx, const float *d_p, const float *d_w, uint32_t n, int output_kind, float *d_out,
+                              uint32_t *d_n_found, float *d_radius2, void *hip_stream);
+
 /* Number of photons in the current volume map. */
 int pvol_photon_count(pvol_ctx *ctx, uint32_t *n);
 /* Copies the current map back (same layout as pvol_upload_photons); capacity in photons. */
