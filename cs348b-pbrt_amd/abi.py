@@ -293,6 +293,22 @@ LPHOTON_SCRATCH_BYTES = 64 << 20   # PVOL_LPHOTON_SCRATCH_BYTES
 LPHOTON_POINT_SCRATCH = 16         # bytes of ordering scratch per point of a slice (csrc/pvol_host.h)
 
 
+class RadianceOut(C.Structure):   # pvol_radiance_out: the outputs of pvol_radiance_batch* (host or device pointers as integers; all but L optional)
+    _fields_ = [("L", C.c_void_p), ("surf_xyz", C.c_void_p), ("t_hit", C.c_void_p), ("draws", C.c_void_p), ("surf_draws", C.c_void_p),
+                ("n_segments", C.c_void_p)]
+
+
+class RadianceBatchCheck(C.Structure):   # the arguments pvol_radiance_batch_check judges (csrc/pvol_host.h)
+    _fields_ = [("rays", C.c_void_p), ("streams", C.c_void_p), ("n_rays", C.c_uint32), ("n_streams", C.c_uint32), ("output_kind", C.c_int32),
+                ("out", C.POINTER(RadianceOut))]
+
+
+RADIANCE_SCRATCH_BYTES = 256 << 20   # PVOL_RADIANCE_SCRATCH_BYTES
+RADIANCE_RAY_SCRATCH = 324           # bytes of scratch per expanded ray of a slice (csrc/pvol_host.h) ...
+RADIANCE_CALLER_SCRATCH = 248        # ... and per caller ray
+RADIANCE_WANT = ("surf_xyz", "t_hit", "draws", "surf_draws", "n_segments")   # the optional outputs, by their field names
+
+
 def make_camera(raster_to_camera, camera_to_world, shutter_open=0.0, shutter_close=1.0, lens_radius=0.0, focal_distance=1e30):
     c = Camera()
     for i, v in enumerate(np.asarray(raster_to_camera, np.float32).reshape(16)):

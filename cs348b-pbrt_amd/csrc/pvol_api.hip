@@ -102,6 +102,7 @@ void pvol_destroy(pvol_ctx *c) {
     if (c->groupFilmEv) hipEventDestroy(c->groupFilmEv);
     if (c->groupStageEv) hipEventDestroy(c->groupStageEv);
     if (c->lpEv) hipEventDestroy(c->lpEv);
+    if (c->rrEv) hipEventDestroy(c->rrEv);
     pvol_free_li_staging(c);
     delete c;
 }

@@ -67,6 +67,13 @@ extern "C" hipError_t pvol_launch_tile(const LiArgs *args, const TileArgs *tile,
                                        bool plain, const char **form);
 extern "C" hipError_t pvol_launch_li_par(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, hipStream_t stream);
 extern "C" hipError_t pvol_launch_lphoton_points(const PointsArgs *args, int candCap, uint32_t nWaves, hipStream_t stream);
+// pvol_radiance_batch* (pvol_rays_dev.h, first compilation only: none of them evaluates a density).  count: the members of every block;
+// emit: the blocks, and the slice's stream table `st` rewritten onto the expanded array (`continued`: the caller's entry of the stream
+// an earlier slice began, or 0); patch: in front of surface_kernel; compose: the fold, and the end_draws into the caller's table
+extern "C" hipError_t pvol_launch_rays_count(const RaysArgs *a, hipStream_t stream);
+extern "C" hipError_t pvol_launch_rays_emit(const RaysArgs *a, pvol_stream *st, uint32_t nStreams, const pvol_stream *continued, hipStream_t stream);
+extern "C" hipError_t pvol_launch_rays_patch(const RaysArgs *a, hipStream_t stream);
+extern "C" hipError_t pvol_launch_rays_compose(const RaysArgs *a, const pvol_stream *st, uint32_t nStreams, pvol_stream *caller, hipStream_t stream);
 // The launchers of one compilation of the marching kernels: VolumeGridDensity (and every medium that is no density region) or, from
 // pvol_march_exp.hip, ExponentialDensity (pvol_region_exp.h).  The host asks pvol_launchers(kind) wherever a launched kernel may
 // evaluate a density; launchers that never do (spec_compose, spec_fill) are called directly.
@@ -124,6 +131,9 @@ enum {
     PVOL_BUF_GROUP_STAGE,               // pvol_render_frame_group: the other contexts' films next to the root's
     PVOL_BUF_FG_DIRS, PVOL_BUF_FG_RAYS, // pvol_final_gather* (pvol_final_gather.hip): a slice's direction records and ray records
     PVOL_BUF_LP_ORDER, PVOL_BUF_LP_TEMP, // pvol_lphoton_batch* (pvol_lphoton.hip): a slice's cell keys and slots (pvol_order_points), the sort's own scratch
+    // pvol_radiance_batch* (pvol_rays.hip), one slice: the expanded rays, their SegInfo, 60-float rows and draw counts; per caller ray the block
+    // sizes and their scan (2 x (n + 1) words) and the primaries' stashed rows; the slice's stream table; the scan's own scratch
+    PVOL_BUF_RR_RAYS, PVOL_BUF_RR_INFO, PVOL_BUF_RR_ROWS, PVOL_BUF_RR_DRAWS, PVOL_BUF_RR_COUNT, PVOL_BUF_RR_STASH, PVOL_BUF_RR_STREAMS, PVOL_BUF_RR_TEMP,
     PVOL_N_BUFS
 };
 extern "C" bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream);
@@ -232,6 +242,9 @@ struct pvol_ctx {
     bool lpNoSort = false;         // PVOL_LPHOTON_NO_SORT=1: the points are served in the caller's order (testing; the results are the same bytes)
     uint64_t lpScratchBound = 0;   // pvol_lphoton_set_scratch_bound (tests): bytes of ordering scratch a slice may take, 0 = PVOL_LPHOTON_SCRATCH_BYTES
     hipEvent_t lpEv = 0;           // the end of the last call's kernels: the next call, on whatever stream, reuses their scratch behind it
+    // pvol_radiance_batch* (pvol_rays.hip)
+    uint64_t rrScratchBound = 0;   // pvol_radiance_set_scratch_bound (tests): bytes of scratch a slice may take, 0 = PVOL_RADIANCE_SCRATCH_BYTES
+    hipEvent_t rrEv = 0;           // the end of the last call's kernels: the next call, on whatever stream, reuses their scratch behind it
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     PhotonGrid causticMap;
     // ... and its indirect map (pvol_set_surface_integrator_maps: LPhoton(indirectMap) without the final gather), built by the same builder
@@ -407,6 +420,24 @@ int pvol_check_lphoton(int haveCtx, const LPhotonCheck *args, int haveScene, flo
 uint32_t pvol_lphoton_slice(uint64_t bound);
 // lowers (or, with 0, restores) the scratch bound of this context's pvol_lphoton_batch* calls, for the tests
 int pvol_lphoton_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
+// every status of pvol_radiance_batch* in its one order (include/pvol.h), reachable without a device for the tests (pvol_rays.hip); no
+// HIP call.  args: the call's pointers and numbers; volKind: the scene's medium; surfOn: a surface integrator is described and on.
+// (pvol_check_radiance is the radiance photons' check above; this one carries the entry point's full name.)
+struct RadianceBatchCheck { const void *rays, *streams; uint32_t nRays, nStreams; int32_t outputKind; const pvol_radiance_out *out; };
+int pvol_radiance_batch_check(int haveCtx, const RadianceBatchCheck *args, int haveScene, int volKind, int surfOn);
+// caller rays per slice of pvol_radiance_batch*: as many as keep a slice's scratch within `bound` bytes (0 or more than
+// PVOL_RADIANCE_SCRATCH_BYTES: that) when every ray spawns maxSegments rays -- PVOL_RADIANCE_RAY_SCRATCH bytes per expanded ray (48 of
+// ray, 32 of SegInfo, 240 of output, 4 of draw count), PVOL_RADIANCE_CALLER_SCRATCH per caller ray (its stashed row, block size and
+// offset) -- whole runs of 64 where that many fit, never fewer than one.  maxSegments: pvol_radiance_max_segments for the worst case; the
+// entry point asks with 0 (nobody spawns), counts, and cuts the slice back to the longest run of its rays whose blocks fit
+#define PVOL_RADIANCE_RAY_SCRATCH 324u
+#define PVOL_RADIANCE_CALLER_SCRATCH 248u
+uint32_t pvol_radiance_slice(uint32_t maxSegments, uint64_t bound);
+// rays the specular recursion can spawn for one ray: 2 + 4 + ... + 2^(maxSpecularDepth - 1), 0 unless specOn (glass in the scene, the
+// surface integrator on, maxspeculardepth > 1)
+uint32_t pvol_radiance_max_segments(int specOn, int32_t maxSpecularDepth);
+// lowers (or, with 0, restores) the scratch bound of this context's pvol_radiance_batch* calls, for the tests
+int pvol_radiance_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
 // the points [first, first + n) of d_p ordered by their cell of G (pvol_grid.hip)
 hipError_t pvol_order_points(const PhotonGrid *G, const float *d_p, uint32_t first, uint32_t n, uint32_t *work, void *temp, size_t *tempBytes,
                              hipStream_t stream);

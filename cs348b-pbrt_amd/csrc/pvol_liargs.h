@@ -48,4 +48,21 @@ struct PointsArgs {
     uint32_t *nFound;           // optional
     float *radius2;             // optional
 };
+// One slice of pvol_radiance_batch* (pvol_rays_dev.h): n caller rays and the expanded array their blocks are laid out in.
+struct RaysArgs {
+    const DevScene *scene;
+    const pvol_ray *in;         // [n] the slice's caller rays
+    uint32_t n;
+    int32_t surfOn, specOn;     // the surface integrator is on; ... and a glass hit can spawn rays (pvol_ctx::specOn)
+    int32_t spectral;           // L: 60 floats per ray, else X, Y, Z, T.y
+    uint32_t *count;            // [n + 1] members per block, entry n zero
+    const uint32_t *offset;     // [n + 1] its exclusive scan: where every block starts, entry n the expanded rays of the slice
+    pvol_ray *rays;             // expanded: per block the segments in post-order, the primary last
+    SegInfo *info;              // expanded; the primary's: Fs = maxt after the clip, pad[0] = 1 when Scene::Intersect hit inside [mint, maxt]
+    float *rows;                // expanded: Lv[30], T[30] of the volume batch, then of surface_kernel's spectral mode
+    const uint32_t *draws;      // expanded: RandomUInt calls of every member's own volume Li()
+    float *stash;               // [n][60] the primaries' rows while theirs hold Ls_matte
+    float *L, *surfXyz, *tHit;  // the slice's part of pvol_radiance_out; all but L optional
+    uint32_t *outDraws, *surfDraws, *nSegments;
+};
 #endif

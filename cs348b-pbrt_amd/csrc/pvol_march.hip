@@ -1443,3 +1443,6 @@ extern "C" hipError_t pvol_launch_li_replay(const LiArgs *args, size_t ldsReplay
 #include "pvol_surface_dev.h"
 #include "pvol_spec_dev.h"
 #include "pvol_tile_dev.h"
+#if !PVOL_REGION_EXP
+#include "pvol_rays_dev.h"   // pvol_radiance_batch*: the pre-pass and the fold for the caller's own rays; reads no density, so compiled once
+#endif

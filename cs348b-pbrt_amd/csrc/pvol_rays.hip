@@ -1,0 +1,225 @@
+// pvol_rays.hip -- the host side of pvol_radiance_batch*: SamplerRenderer::Li (renderers/samplerrenderer.cpp:228-251, :95-97) for rays
+// the caller generated.  The kernels of the pre-pass and the fold are pvol_rays_dev.h's (compiled in pvol_march.hip,
+// beside spec_surface and surface_kernel, which they use); this unit checks the call, walks the rays in slices, and per slice runs
+//   count -> exclusive scan (hipCUB) -> emit + stream table -> pvol_launch_batch (the path pvol_li_batch_device takes, SPECTRAL)
+//   -> patch + surface_kernel in its spectral mode (surface integrator on) -> compose.
+// No atomics of its own; the block sizes are known before anything is written.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <string.h>
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "pvol_host.h"
+
+static bool ok(hipError_t e) { return e == hipSuccess; }
+
+extern "C" {
+
+int pvol_radiance_batch_check(int haveCtx, const RadianceBatchCheck *a, int haveScene, int volKind, int surfOn) {
+    if (!haveCtx || !a) return PVOL_E_INVALID;
+    if (a->outputKind != PVOL_OUT_SPECTRAL && a->outputKind != PVOL_OUT_XYZ) return PVOL_E_INVALID;
+    if ((a->nRays && !a->rays) || (a->nStreams && !a->streams)) return PVOL_E_INVALID;
+    if (a->nRays && (!a->out || !a->out->L)) return PVOL_E_INVALID;
+    if (!haveScene) return PVOL_E_NO_SCENE;
+    if (surfOn && is_density_region(volKind)) return PVOL_E_UNSUPPORTED;   // the shadow rays' tau() offsets are drawn values
+    return PVOL_OK;
+}
+
+uint32_t pvol_radiance_max_segments(int specOn, int32_t maxSpecularDepth) {
+    if (!specOn || maxSpecularDepth < 2) return 0u;
+    return (1u << std::min<int32_t>(maxSpecularDepth, SPEC_MAX_DEPTH)) - 2u;
+}
+
+uint32_t pvol_radiance_slice(uint32_t maxSegments, uint64_t bound) {
+    if (!bound || bound > PVOL_RADIANCE_SCRATCH_BYTES) bound = PVOL_RADIANCE_SCRATCH_BYTES;
+    const uint64_t perRay = ((uint64_t)maxSegments + 1u) * PVOL_RADIANCE_RAY_SCRATCH + PVOL_RADIANCE_CALLER_SCRATCH;
+    uint64_t n = bound / perRay;
+    if (n >= 64) n -= n % 64;
+    return (uint32_t)std::max<uint64_t>(n, 1);
+}
+
+int pvol_radiance_set_scratch_bound(pvol_ctx *c, uint64_t bytes) {
+    if (!c) return PVOL_E_INVALID;
+    std::lock_guard<std::recursive_mutex> api(c->apiMu);
+    c->rrScratchBound = std::min<uint64_t>(bytes, PVOL_RADIANCE_SCRATCH_BYTES);   // the hook only lowers the bound
+    return PVOL_OK;
+}
+
+}  // extern "C"
+
+static int check_ctx(const pvol_ctx *c, const RadianceBatchCheck *a) {
+    return pvol_radiance_batch_check(c != 0, a, c && c->haveScene, c ? c->hs.volKind : 0, c && c->hs.surf.enabled != 0);
+}
+
+// the streams partition the ray array in order, as host_batch asks (pvol_api.hip)
+static bool streams_partition(const pvol_stream *st, uint32_t nStreams, uint32_t nRays) {
+    uint64_t next = 0;
+    for (uint32_t s = 0; s < nStreams; ++s) {
+        if (st[s].first_ray != next) return false;
+        next += st[s].n_rays;
+    }
+    return next == nRays;
+}
+
+// The call, slice by slice, on device arrays.  hs: host copy of the caller's stream table (already checked).  Caller holds apiMu and has
+// the device set.
+static int radiance_slices(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_stream *dStreams, const std::vector<pvol_stream> &hs,
+                           int outputKind, const pvol_radiance_out &out, hipStream_t stream) {
+    const uint32_t nStreams = (uint32_t)hs.size();
+    const bool surfOn = c->hs.surf.enabled != 0, specOn = surfOn && c->specOn;
+    const uint32_t maxSeg = pvol_radiance_max_segments(specOn, c->hs.surf.maxSpecularDepth);
+    // A slice is sized for rays that spawn nothing, counted, and cut back to the longest run of its rays whose blocks fit the bound: sizing
+    // it for the worst case (30 spawned rays each at depth 5) would make slices of a few thousand rays, launches too small for the device
+    const uint64_t budget = c->rrScratchBound ? c->rrScratchBound : PVOL_RADIANCE_SCRATCH_BYTES;
+    const uint32_t slice = std::min(nRays, pvol_radiance_slice(0, budget));
+    // an earlier call's kernels, on whatever stream, may still read the scratch
+    if (c->rrEv) { if (!ok(hipStreamWaitEvent(stream, c->rrEv, 0))) return PVOL_E_NO_DEVICE; }
+    else if (!ok(hipEventCreateWithFlags(&c->rrEv, hipEventDisableTiming))) { c->rrEv = 0; return PVOL_E_NO_DEVICE; }
+    size_t tempBytes = 0;
+    if (!ok(hipcub::DeviceScan::ExclusiveSum((void *)0, tempBytes, (const uint32_t *)0, (uint32_t *)0, (int)(slice + 1u), stream))) return PVOL_E_NO_DEVICE;
+    if (!pvol_reserve(c->buf[PVOL_BUF_RR_COUNT], sizeof(uint32_t) * 2 * ((size_t)slice + 1), stream) ||
+        !pvol_reserve(c->buf[PVOL_BUF_RR_TEMP], std::max<size_t>(tempBytes, 16), stream) ||
+        !pvol_reserve(c->buf[PVOL_BUF_RR_STASH], surfOn ? sizeof(float) * 60 * (size_t)slice : 0, stream))
+        return PVOL_E_NO_MEMORY;
+    const size_t width = outputKind == PVOL_OUT_SPECTRAL ? 60 : 4;
+    const RegionLaunchers &K = pvol_launchers(c->hs.volKind);
+    std::vector<pvol_stream> table;
+    std::vector<uint32_t> hostOffset;
+    uint32_t s = 0;   // the first stream that may reach into the slice
+    for (uint32_t r0 = 0; r0 < nRays;) {
+        uint32_t n = std::min(slice, nRays - r0);
+        RaysArgs A;
+        memset(&A, 0, sizeof(A));
+        A.scene = c->ds.get(); A.in = dRays + r0; A.n = n; A.surfOn = surfOn; A.specOn = specOn; A.spectral = outputKind == PVOL_OUT_SPECTRAL;
+        A.count = pvol_buf<uint32_t>(c, PVOL_BUF_RR_COUNT); A.offset = A.count + (size_t)slice + 1;
+        A.stash = pvol_buf<float>(c, PVOL_BUF_RR_STASH);
+        uint32_t total = 0;
+        size_t tb = c->buf[PVOL_BUF_RR_TEMP].bytes;
+        if (!ok(pvol_launch_rays_count(&A, stream)) ||
+            !ok(hipcub::DeviceScan::ExclusiveSum(pvol_buf<unsigned char>(c, PVOL_BUF_RR_TEMP), tb, (const uint32_t *)A.count, (uint32_t *)A.offset, (int)(n + 1u), stream)) ||
+            !ok(hipMemcpyAsync(&total, A.offset + n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream)))
+            return PVOL_E_NO_DEVICE;
+        if (n > 1 && (uint64_t)total * PVOL_RADIANCE_RAY_SCRATCH + (uint64_t)n * PVOL_RADIANCE_CALLER_SCRATCH > budget) {
+            // the longest run of the candidate's rays that fits (never fewer than one ray, whole runs of 64 where that many fit): the offsets
+            // of a run do not depend on what follows it, so the scan stands
+            hostOffset.resize((size_t)n + 1);
+            if (!ok(hipMemcpy(hostOffset.data(), A.offset, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
+            uint32_t lo = 1, hi = n;   // fits(lo) is taken for granted, fits(hi) is false
+            while (hi - lo > 1) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                if ((uint64_t)hostOffset[mid] * PVOL_RADIANCE_RAY_SCRATCH + (uint64_t)mid * PVOL_RADIANCE_CALLER_SCRATCH <= budget) lo = mid; else hi = mid;
+            }
+            n = lo >= 64 ? lo - lo % 64 : lo;
+            total = hostOffset[n];
+            A.n = n;
+        }
+        const uint32_t r1 = r0 + n;
+        const bool last = r1 == nRays;
+        // the slice's streams: those with rays in [r0, r1), and the empty ones that stand there (at the very end: in the last slice)
+        table.clear();
+        const uint32_t s0 = s;
+        for (; s < nStreams; ++s) {
+            const pvol_stream &h = hs[s];
+            const uint32_t end = h.first_ray + h.n_rays;
+            if (h.first_ray >= r1 && !(last && !h.n_rays)) break;
+            pvol_stream t = h;
+            t.first_ray = std::max(h.first_ray, r0) - r0; t.n_rays = std::min(end, r1) - std::max(h.first_ray, r0); t.end_draw = 0;
+            table.push_back(t);
+            if (end > r1) break;   // the boundary cuts this stream: the next slice begins with the rest of it
+        }
+        const uint32_t ns = (uint32_t)table.size();
+        const bool continued = ns && hs[s0].first_ray < r0;
+        if (!pvol_reserve(c->buf[PVOL_BUF_RR_STREAMS], sizeof(pvol_stream) * std::max<size_t>(ns, 1), stream)) return PVOL_E_NO_MEMORY;
+        pvol_stream *dTable = pvol_buf<pvol_stream>(c, PVOL_BUF_RR_STREAMS);
+        // the table is read from pageable memory that the next slice rewrites: wait for the copy
+        if (ns && (!ok(hipMemcpyAsync(dTable, table.data(), sizeof(pvol_stream) * ns, hipMemcpyHostToDevice, stream)) || !ok(hipStreamSynchronize(stream))))
+            return PVOL_E_NO_DEVICE;
+        A.L = out.L + width * (size_t)r0;
+        A.surfXyz = out.surf_xyz ? out.surf_xyz + 3 * (size_t)r0 : 0; A.tHit = out.t_hit ? out.t_hit + r0 : 0;
+        A.outDraws = out.draws ? out.draws + r0 : 0; A.surfDraws = out.surf_draws ? out.surf_draws + r0 : 0;
+        A.nSegments = out.n_segments ? out.n_segments + r0 : 0;
+        if (total < n || (uint64_t)total > (uint64_t)n * (maxSeg + 1u)) return PVOL_E_NO_DEVICE;   // cannot happen: the count pass bounds every block
+        if (!pvol_reserve(c->buf[PVOL_BUF_RR_RAYS], sizeof(pvol_ray) * (size_t)total, stream) || !pvol_reserve(c->buf[PVOL_BUF_RR_INFO], sizeof(SegInfo) * (size_t)total, stream) ||
+            !pvol_reserve(c->buf[PVOL_BUF_RR_ROWS], sizeof(float) * 60 * (size_t)total, stream) || !pvol_reserve(c->buf[PVOL_BUF_RR_DRAWS], sizeof(uint32_t) * (size_t)total, stream))
+            return PVOL_E_NO_MEMORY;
+        A.rays = pvol_buf<pvol_ray>(c, PVOL_BUF_RR_RAYS); A.info = pvol_buf<SegInfo>(c, PVOL_BUF_RR_INFO);
+        A.rows = pvol_buf<float>(c, PVOL_BUF_RR_ROWS);
+        uint32_t *dDraws = pvol_buf<uint32_t>(c, PVOL_BUF_RR_DRAWS);
+        A.draws = dDraws;
+        if (!ok(pvol_launch_rays_emit(&A, dTable, ns, continued ? dStreams + s0 : 0, stream)) ||
+            !ok(hipMemsetAsync(A.rows, 0, sizeof(float) * 60 * (size_t)total, stream)) || !ok(hipMemsetAsync(dDraws, 0, sizeof(uint32_t) * (size_t)total, stream)))
+            return PVOL_E_NO_DEVICE;
+        if (ns) {
+            BatchArgs b = {};   // maxRaysPerStream 0: the table lives on the device, as for pvol_li_batch_device
+            b.rays = A.rays; b.nRays = total; b.streams = dTable; b.nStreams = ns; b.outputKind = PVOL_OUT_SPECTRAL; b.out = A.rows; b.draws = dDraws;
+            b.stream = stream;
+            const int rc = pvol_launch_batch(c, b);
+            if (rc != PVOL_OK) return rc;
+        }
+        if (surfOn) {   // Ls at the matte hits of every member, T (.) Ls added into the segments' Lv, Ls itself left in the primaries' rows
+            SurfArgs su = {};
+            su.scene = c->ds.get(); su.rays = A.rays; su.nRays = total; su.out = A.rows; su.counters = c->dCounters.get(); su.spectral = 1;
+            const uint32_t nWaves = (uint32_t)std::min<unsigned long long>(((unsigned long long)total + 63) / 64, (unsigned long long)c->nCU * 24ull);
+            if (!ok(pvol_launch_rays_patch(&A, stream)) || !ok(K.surface(&su, nWaves, stream))) return PVOL_E_NO_DEVICE;
+        }
+        if (!ok(pvol_launch_rays_compose(&A, dTable, ns, dStreams + s0, stream))) return PVOL_E_NO_DEVICE;
+        r0 = r1;
+    }
+    return ok(hipEventRecord(c->rrEv, stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+}
+
+extern "C" {
+
+int pvol_radiance_batch_device(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_stream *dStreams, uint32_t nStreams, int outputKind,
+                               const pvol_radiance_out *out, void *hipStream) {
+    const RadianceBatchCheck a = {dRays, dStreams, nRays, nStreams, outputKind, out};
+    if (!c) return check_ctx(0, &a);
+    std::lock_guard<std::recursive_mutex> api(c->apiMu);   // the context's state is read under the lock only
+    const int rc0 = check_ctx(c, &a);
+    if (rc0 != PVOL_OK) return rc0;
+    if (!nRays || !nStreams) return PVOL_OK;
+    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
+    hipStream_t stream = (hipStream_t)hipStream;
+    std::vector<pvol_stream> hs(nStreams);   // read on the caller's stream: ordered behind whatever produced the table
+    if (!ok(hipMemcpyAsync(hs.data(), dStreams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyDeviceToHost, stream)) ||
+        !ok(hipStreamSynchronize(stream))) return PVOL_E_NO_DEVICE;
+    if (!streams_partition(hs.data(), nStreams, nRays)) return PVOL_E_INVALID;
+    return radiance_slices(c, dRays, nRays, dStreams, hs, outputKind, *out, stream);
+}
+
+int pvol_radiance_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, pvol_stream *streams, uint32_t nStreams, int outputKind,
+                        const pvol_radiance_out *out) {
+    const RadianceBatchCheck a = {rays, streams, nRays, nStreams, outputKind, out};
+    if (!c) return check_ctx(0, &a);
+    std::lock_guard<std::recursive_mutex> api(c->apiMu);   // from the upload to the copy-back: the launches share the context's scratch
+    int rc = check_ctx(c, &a);
+    if (rc != PVOL_OK) return rc;
+    if (!nRays || !nStreams) return PVOL_OK;
+    if (!streams_partition(streams, nStreams, nRays)) return PVOL_E_INVALID;
+    if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
+    const size_t width = outputKind == PVOL_OUT_SPECTRAL ? 60 : 4, n = nRays;
+    DevPtr<pvol_ray> dRays; DevPtr<pvol_stream> dStreams; DevPtr<float> dL, dSurf, dT; DevPtr<uint32_t> dDraws, dSurfDraws, dSeg;
+    if (!dRays.alloc(n) || !dStreams.alloc(nStreams) || !dL.alloc(width * n) || (out->surf_xyz && !dSurf.alloc(3 * n)) || (out->t_hit && !dT.alloc(n)) ||
+        (out->draws && !dDraws.alloc(n)) || (out->surf_draws && !dSurfDraws.alloc(n)) || (out->n_segments && !dSeg.alloc(n)))
+        return PVOL_E_NO_MEMORY;
+    if (!ok(hipMemcpy(dRays.get(), rays, sizeof(pvol_ray) * n, hipMemcpyHostToDevice)) ||
+        !ok(hipMemcpy(dStreams.get(), streams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyHostToDevice)))
+        return PVOL_E_NO_DEVICE;
+    const pvol_radiance_out d = {dL.get(), dSurf.get(), dT.get(), dDraws.get(), dSurfDraws.get(), dSeg.get()};
+    rc = radiance_slices(c, dRays.get(), nRays, dStreams.get(), std::vector<pvol_stream>(streams, streams + nStreams), outputKind, d, 0);
+    if (rc == PVOL_OK && !ok(hipDeviceSynchronize())) rc = PVOL_E_NO_DEVICE;
+    if (rc == PVOL_OK) rc = pvol_check_errors(c);
+    if (rc != PVOL_OK) return rc;   // nothing is written unless all of it ran
+    const bool good = ok(hipMemcpy(out->L, dL.get(), sizeof(float) * width * n, hipMemcpyDeviceToHost)) &&
+                      (!out->surf_xyz || ok(hipMemcpy(out->surf_xyz, dSurf.get(), sizeof(float) * 3 * n, hipMemcpyDeviceToHost))) &&
+                      (!out->t_hit || ok(hipMemcpy(out->t_hit, dT.get(), sizeof(float) * n, hipMemcpyDeviceToHost))) &&
+                      (!out->draws || ok(hipMemcpy(out->draws, dDraws.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost))) &&
+                      (!out->surf_draws || ok(hipMemcpy(out->surf_draws, dSurfDraws.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost))) &&
+                      (!out->n_segments || ok(hipMemcpy(out->n_segments, dSeg.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost))) &&
+                      ok(hipMemcpy(streams, dStreams.get(), sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyDeviceToHost));
+    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+}
+
+}  // extern "C"

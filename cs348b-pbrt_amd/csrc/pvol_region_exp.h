@@ -48,4 +48,16 @@
 #define pvol_launch_merge_surface pvol_launch_merge_surface_exp
 #define pvol_launch_place_rows pvol_launch_place_rows_exp
 #define pvol_shoot_state_words pvol_shoot_state_words_exp
+// pvol_rays_dev.h (pvol_radiance_batch*) reads no density and is left out of the second compilation altogether (pvol_march.hip); its names
+// stand here so that nothing of the sources compiled twice is off the list
+#define rays_count_kernel rays_count_kernel_exp
+#define rays_emit_kernel rays_emit_kernel_exp
+#define rays_streams_kernel rays_streams_kernel_exp
+#define rays_end_kernel rays_end_kernel_exp
+#define rays_patch_kernel rays_patch_kernel_exp
+#define rays_compose_kernel rays_compose_kernel_exp
+#define pvol_launch_rays_count pvol_launch_rays_count_exp
+#define pvol_launch_rays_emit pvol_launch_rays_emit_exp
+#define pvol_launch_rays_patch pvol_launch_rays_patch_exp
+#define pvol_launch_rays_compose pvol_launch_rays_compose_exp
 #endif

@@ -174,6 +174,14 @@ def lib():
         L.pvol_lphoton_slice.argtypes = [C.c_uint64]
         L.pvol_lphoton_slice.restype = C.c_uint32
         L.pvol_lphoton_set_scratch_bound.argtypes = [C.c_void_p, C.c_uint64]
+        L.pvol_radiance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(abi.RadianceOut)]
+        L.pvol_radiance_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(abi.RadianceOut), C.c_void_p]
+        L.pvol_radiance_batch_check.argtypes = [C.c_int, C.POINTER(abi.RadianceBatchCheck), C.c_int, C.c_int, C.c_int]
+        L.pvol_radiance_slice.argtypes = [C.c_uint32, C.c_uint64]
+        L.pvol_radiance_slice.restype = C.c_uint32
+        L.pvol_radiance_max_segments.argtypes = [C.c_int, C.c_int32]
+        L.pvol_radiance_max_segments.restype = C.c_uint32
+        L.pvol_radiance_set_scratch_bound.argtypes = [C.c_void_p, C.c_uint64]
         L.pvol_probe_hits.argtypes =[C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _f32p, C.POINTER(C.c_int32)]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_set_surface_integrator_maps.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), C.POINTER(abi.PhotonArray), C.POINTER(abi.PhotonArray)]
@@ -235,7 +243,8 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_radiance_lookup", "pvol_radiance_lookup_device", "pvol_set_surface_integrator_maps",
            "pvol_build_gather_map", "pvol_build_gather_map_arrays", "pvol_gather_map_count", "pvol_gather_photons",
            "pvol_gather_photons_device", "pvol_gather_directions", "pvol_gather_directions_device", "pvol_final_gather",
-           "pvol_final_gather_device", "pvol_lphoton_batch", "pvol_lphoton_batch_device"]
+           "pvol_final_gather_device", "pvol_lphoton_batch", "pvol_lphoton_batch_device", "pvol_radiance_batch",
+           "pvol_radiance_batch_device"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -611,6 +620,38 @@ class PhotonVolume:
     def lphoton_set_scratch_bound(self, nbytes):
         """Test hook: the bytes of ordering scratch a slice of lphoton_batch() may take (0: the header's PVOL_LPHOTON_SCRATCH_BYTES)."""
         _check(lib().pvol_lphoton_set_scratch_bound(self._h, int(nbytes)), "pvol_lphoton_set_scratch_bound")
+
+    def radiance_batch(self, rays, streams, output_kind=abi.OUT_SPECTRAL, want=()):
+        """SamplerRenderer::Li for the caller's own rays (pvol_radiance_batch): Scene::Intersect clips each ray, the surface integrator
+        (if one is on) runs at the hit, specular recursion included, then the volume Li().  Returns a dict: "L"[n, 60|4] = T * Ls + Lvi
+        then T, and the optional outputs named in `want` (abi.RADIANCE_WANT): "surf_xyz"[n,3], "t_hit"[n], "draws"[n], "surf_draws"[n],
+        "n_segments"[n].  rays['rng_skip'] holds the caller's own draws only; streams['end_draw'] is updated."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype == abi.RAY_DTYPE and streams.dtype == abi.STREAM_DTYPE and streams.flags["C_CONTIGUOUS"]
+        n = len(rays)
+        res = {"L": np.zeros((n, 60 if output_kind == abi.OUT_SPECTRAL else 4), np.float32)}
+        for k in want:
+            if k not in abi.RADIANCE_WANT:
+                raise ValueError("radiance_batch: unknown output %r" % (k,))
+            res[k] = np.zeros((n, 3), np.float32) if k == "surf_xyz" else np.zeros(n, np.float32 if k == "t_hit" else np.uint32)
+        out = abi.RadianceOut(**{k: v.ctypes.data for k, v in res.items()})
+        _check(lib().pvol_radiance_batch(self._h, rays.ctypes.data, n, streams.ctypes.data, len(streams), int(output_kind), C.byref(out)),
+               "pvol_radiance_batch")
+        return res
+
+    def radiance_batch_device(self, d_rays, n_rays, d_streams, n_streams, output_kind, d_L, hip_stream=0, **d_optional):
+        """Device-pointer variant (integers; d_optional: surf_xyz=, t_hit=, draws=, surf_draws=, n_segments=).  Enqueued on hip_stream,
+        which is synchronised once for the stream table and once per slice; the last slice's kernels are left in flight."""
+        for k in d_optional:
+            if k not in abi.RADIANCE_WANT:
+                raise ValueError("radiance_batch_device: unknown output %r" % (k,))
+        out = abi.RadianceOut(L=d_L or None, **{k: (v or None) for k, v in d_optional.items()})
+        _check(lib().pvol_radiance_batch_device(self._h, d_rays, n_rays, d_streams, n_streams, int(output_kind), C.byref(out), hip_stream),
+               "pvol_radiance_batch_device")
+
+    def radiance_set_scratch_bound(self, nbytes):
+        """Test hook: the bytes of scratch a slice of radiance_batch() may take (0: the header's PVOL_RADIANCE_SCRATCH_BYTES)."""
+        _check(lib().pvol_radiance_set_scratch_bound(self._h, int(nbytes)), "pvol_radiance_set_scratch_bound")
 
     def check_errors(self):
         """Raises PvolError(PVOL_E_LIMIT) if a batch enqueued through a device entry point hit a kernel limit."""

@@ -591,6 +591,55 @@ int pvol_li_batch_device(pvol_ctx *ctx, const pvol_ray *d_rays, uint32_t n_rays,
                          int output_kind, float *d_out, uint32_t *d_draws,
                          void *hip_stream);
 
+/* ---- full radiance for rays the caller generated
+ * SamplerRenderer::Li (renderers/samplerrenderer.cpp:228-251, :95-97) per ray of the batch, in its stream's order, for a caller with
+ * its own camera and sampler (pvol_render_tasks_device insists on LDSampler and a pinhole PerspectiveCamera):
+ *   1. Scene::Intersect over [mint, maxt] (:236): with a hit at t <= maxt, maxt becomes t; without one Ls = 0 and nothing is drawn.
+ *   2. No surface integrator described (pvol_set_surface_integrator*), or one switched off: Ls = 0, nothing is drawn at the hit, and
+ *      the result is pvol_li_batch's on the clipped ray, for every medium.
+ *   3. Surface integrator on: PhotonIntegrator::Li at the hit (integrators/photonmap.cpp:154-319) as pvol_render_tasks_device runs it --
+ *      matte: direct light + LPhoton(caustic) + LPhoton(indirect, `finalgather false`), their BSDF::rho draws, one draw per unoccluded
+ *      light sample under a medium, 6 for the two absent lobes; glass: SpecularReflect + SpecularTransmit (core/integrator.cpp:177-262),
+ *      3 draws each, the spawned ray through these same steps at depth + 1 on the parent's scatter_u and time, in post-order, before the
+ *      parent's own volume Li().
+ *   4. L = T (.) Ls + Lvi and T, T the ray's own volume transmittance (PhotonVolumeIntegrator::Li, photonvolume.cpp:112-222).
+ * rays[i].rng_skip is what the CALLER drew since the previous ray of the stream (its sampler); the surface integrator's draws are this
+ * entry point's business.  streams[].end_draw is written as pvol_li_batch writes it.
+ *
+ * Statuses, decided in this one order (pvol_radiance_batch_check):
+ *   1. PVOL_E_INVALID      NULL ctx
+ *   2. PVOL_E_INVALID      an unknown output_kind
+ *   3. PVOL_E_INVALID      NULL rays with n_rays > 0, NULL streams with n_streams > 0
+ *   4. PVOL_E_INVALID      NULL out, or NULL out->L, with n_rays > 0
+ *   5. PVOL_E_NO_SCENE
+ *   6. PVOL_E_UNSUPPORTED  a surface integrator that is on over a density region (VolumeGrid, exponential): the shadow rays'
+ *                          transmittance there needs drawn values, as pvol_render_tasks_device refuses it
+ *   then PVOL_E_INVALID for streams that do not partition the rays in order (as pvol_li_batch; the device form reads its table back
+ *   to see), and PVOL_E_NO_DEVICE / PVOL_E_NO_MEMORY from the device.  A rejected call writes nothing; n_rays == 0 or n_streams == 0
+ *   does nothing and returns PVOL_OK.
+ * The rays are walked in slices whose scratch (the context's) stays within PVOL_RADIANCE_SCRATCH_BYTES: 324 bytes per ray and spawned
+ * ray, 248 per ray.  A slice is sized for rays that spawn nothing, its spawned rays are counted, and it is cut back to the longest
+ * run of its rays that fits (never fewer than one ray); it may end inside a stream, which the next slice continues.  No atomics of
+ * its own and no pool that can overflow. */
+#define PVOL_RADIANCE_SCRATCH_BYTES (256ull << 20)
+typedef struct pvol_radiance_out {   /* host arrays in the host form, device arrays in the device form; all but L optional (NULL) */
+    float    *L;           /* per ray, pvol_output_kind's layout: T (.) Ls + Lvi, then T (Spectrum Li, *T of samplerrenderer.cpp:228)    */
+    float    *surf_xyz;    /* 3 per ray: Ls as X, Y, Z (what pvol_render_debug.d_surf_xyz reports)                                       */
+    float    *t_hit;       /* per ray: maxt after the clip (ray.maxt behind Scene::Intersect, samplerrenderer.cpp:236)                   */
+    uint32_t *draws;       /* per ray: RandomUInt calls of the ray's own volume Li(), as pvol_li_batch                                   */
+    uint32_t *surf_draws;  /* per ray: calls made for it before that Li(), the caller's rng_skip excluded -- the surface integrator at   */
+                           /* the hit, every spawned ray's surface draws and volume Li()                                                 */
+    uint32_t *n_segments;  /* per ray: rays the specular recursion spawned (core/integrator.cpp:198, :243)                               */
+} pvol_radiance_out;
+/* Host pointers; holds the context from upload to copy-back and checks the device's error flag (pvol_check_errors) itself. */
+int pvol_radiance_batch(pvol_ctx *ctx, const pvol_ray *rays, uint32_t n_rays, pvol_stream *streams, uint32_t n_streams, int output_kind,
+                        const pvol_radiance_out *out);
+/* All arrays (the members of *out too; *out itself is host memory) are DEVICE pointers; the work is enqueued on `hip_stream`.  That
+ * stream is synchronised once to read the stream table back and twice per slice (the slice's expanded size comes back, its stream
+ * table goes up; pvol_li_batch_device synchronises it likewise where it sizes a slice); the kernels of the last slice are left in flight. */
+int pvol_radiance_batch_device(pvol_ctx *ctx, const pvol_ray *d_rays, uint32_t n_rays, pvol_stream *d_streams, uint32_t n_streams,
+                               int output_kind, const pvol_radiance_out *out, void *hip_stream);
+
 /* Device-side error flags of the batches enqueued so far (pvol_li_batch_device, pvol_render_tasks_device): waits
  * for the device and returns PVOL_E_LIMIT if a ray needed more march steps than the kernels' record/LDS plan holds
  * (such a ray's output is zero, never a guess), clearing the flag.  The host entry points check this themselves. */
