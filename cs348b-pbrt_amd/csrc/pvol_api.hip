@@ -14,8 +14,6 @@
 
 #include "pvol_host.h"
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 extern "C" {
 
 int pvol_abi_version(void) { return PVOL_ABI_VERSION; }
@@ -99,10 +97,6 @@ void pvol_destroy(pvol_ctx *c) {
     for (auto &p : c->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     for (auto &p : c->phaseMarks) hipEventDestroy(p.second);
     for (auto &e : c->phasePool) hipEventDestroy(e);
-    if (c->groupFilmEv) hipEventDestroy(c->groupFilmEv);
-    if (c->groupStageEv) hipEventDestroy(c->groupStageEv);
-    if (c->lpEv) hipEventDestroy(c->lpEv);
-    if (c->rrEv) hipEventDestroy(c->rrEv);
     pvol_free_li_staging(c);
     delete c;
 }
@@ -655,45 +649,28 @@ static int host_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, pvol_st
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
     uint32_t maxRays = 1;
-    {   // streams must partition the ray array in order (every ray belongs to exactly one stream)
-        uint64_t next = 0;
-        for (uint32_t s = 0; s < nStreams; ++s) {
-            if (streams[s].first_ray != next) return PVOL_E_INVALID;
-            next += streams[s].n_rays;
-            maxRays = std::max(maxRays, streams[s].n_rays);
-        }
-        if (next != nRays) return PVOL_E_INVALID;
-    }
+    if (!streams_partition(streams, nStreams, nRays, &maxRays)) return PVOL_E_INVALID;
     if (!nStreams || !nRays) return PVOL_OK;
     const size_t width = transOnly ? 60 : (outputKind == PVOL_OUT_SPECTRAL ? 60 : 4);
-    DevPtr<pvol_ray> dRays; DevPtr<pvol_stream> dStreams; DevPtr<float> dOut; DevPtr<uint32_t> dDraws, dState;
-    if (!dRays.alloc(nRays) || !dStreams.alloc(nStreams) || !dOut.alloc(width * nRays) || !dDraws.alloc(nRays) ||
-        (mtState && !dState.alloc(625 * (size_t)nStreams)))
-        return PVOL_E_NO_MEMORY;
-    bool good = ok(hipMemcpy(dRays.get(), rays, sizeof(pvol_ray) * (size_t)nRays, hipMemcpyHostToDevice)) &&
-                ok(hipMemcpy(dStreams.get(), streams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyHostToDevice)) &&
-                ok(hipMemset(dOut.get(), 0, sizeof(float) * width * nRays));
-    if (good && mtState) good = ok(hipMemcpy(dState.get(), mtState, sizeof(uint32_t) * 625 * (size_t)nStreams, hipMemcpyHostToDevice));
-    if (!good) return PVOL_E_NO_DEVICE;
+    std::vector<float> rows(transOnly ? width * nRays : 0);   // the kernel writes [Lv(30) | T(30)] rows; the ABI returns T only
+    HostStage st;
     BatchArgs b = {};
-    b.rays = dRays.get(); b.nRays = nRays; b.streams = dStreams.get(); b.nStreams = nStreams; b.outputKind = transOnly ? PVOL_OUT_SPECTRAL : outputKind;
-    b.out = dOut.get(); b.draws = dDraws.get(); b.initState = dState.get(); b.finalState = dState.get(); b.transOnly = transOnly; b.maxRaysPerStream = maxRays;
-    int rc = pvol_launch_batch(c, b);
+    b.rays = st.in(rays, nRays); b.nRays = nRays; b.nStreams = nStreams; b.outputKind = transOnly ? PVOL_OUT_SPECTRAL : outputKind;
+    b.out = st.out(transOnly ? rows.data() : out, width * nRays);
+    b.streams = st.inout(streams, nStreams);
+    b.draws = draws ? st.out(draws, nRays) : st.scratch<uint32_t>(nRays);
+    b.initState = b.finalState = st.inout(mtState, 625 * (size_t)nStreams);
+    b.transOnly = transOnly; b.maxRaysPerStream = maxRays;
+    int rc = st.upload();
+    if (rc != PVOL_OK) return rc;
+    if (!ok(hipMemset(b.out, 0, sizeof(float) * width * nRays))) return PVOL_E_NO_DEVICE;
+    rc = pvol_launch_batch(c, b);
     if (rc == PVOL_OK && !ok(hipStreamSynchronize(0))) rc = PVOL_E_NO_DEVICE;
     if (rc == PVOL_OK) rc = check_errors(c);
+    if (rc == PVOL_OK) rc = st.download();
     if (rc != PVOL_OK) return rc;
-    if (transOnly) {
-        // kernel wrote [Lv(30) | T(30)] rows; the ABI returns T only
-        std::vector<float> tmp(width * nRays);
-        good = ok(hipMemcpy(tmp.data(), dOut.get(), sizeof(float) * width * nRays, hipMemcpyDeviceToHost));
-        if (good) for (uint32_t i = 0; i < nRays; ++i) memcpy(out + (size_t)i * 30, tmp.data() + (size_t)i * 60 + 30, sizeof(float) * 30);
-    } else {
-        good = ok(hipMemcpy(out, dOut.get(), sizeof(float) * width * nRays, hipMemcpyDeviceToHost));
-    }
-    good = good && ok(hipMemcpy(streams, dStreams.get(), sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyDeviceToHost));
-    if (good && draws) good = ok(hipMemcpy(draws, dDraws.get(), sizeof(uint32_t) * (size_t)nRays, hipMemcpyDeviceToHost));
-    if (good && mtState) good = ok(hipMemcpy(mtState, dState.get(), sizeof(uint32_t) * 625 * (size_t)nStreams, hipMemcpyDeviceToHost));
-    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+    for (size_t i = 0; i < rows.size() / 60; ++i) memcpy(out + i * 30, rows.data() + i * 60 + 30, sizeof(float) * 30);
+    return PVOL_OK;
 }
 
 int pvol_li_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, pvol_stream *streams, uint32_t nStreams, int outputKind,

@@ -22,8 +22,6 @@
 
 static_assert(sizeof(pvol_gather_ray) == 32 && sizeof(pvol_gather_sample) == 32, "one record is two float4");
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 // One slice of queries.  Passed by value: nothing in it is indexed at run time but the grid's three-element arrays inside loops of
 // three, which unroll; what is indexed by lane (sigma_a, sigma_s) is read from the scene in device memory.
 struct FgArgs {
@@ -141,11 +139,7 @@ int pvol_check_final_gather(int haveCtx, const FinalGatherCheck *a, int haveScen
 
 uint32_t pvol_final_gather_slice(int32_t nSamples, uint64_t bound) {
     // the header's bound is the largest: a slice then holds at most 2^22 gather rays, so ray and block numbers fit 32 bits
-    if (!bound || bound > PVOL_FINAL_GATHER_SCRATCH_BYTES) bound = PVOL_FINAL_GATHER_SCRATCH_BYTES;
-    const uint64_t perQuery = 2ull * FG_RAY_SCRATCH * (uint64_t)std::max(nSamples, 1);
-    uint64_t n = bound / perQuery;
-    if (n >= LANES) n -= n % LANES;
-    return (uint32_t)std::max<uint64_t>(n, 1);
+    return pvol_slice_items(bound, PVOL_FINAL_GATHER_SCRATCH_BYTES, 2ull * FG_RAY_SCRATCH * (uint64_t)std::max(nSamples, 1));
 }
 
 int pvol_final_gather_set_scratch_bound(pvol_ctx *c, uint64_t bytes) {
@@ -174,6 +168,8 @@ int pvol_final_gather_device(pvol_ctx *c, const float *dP, const float *dFrames,
     const uint32_t slice = std::min(count, pvol_final_gather_slice(nSamples, c->fgScratchBound));
     const size_t sliceRecs = (size_t)slice * nSamples;   // records of one loop
     const bool ownRays = !dRaysBsdf || !dRaysPhoton;
+    // an earlier call's kernels, on whatever stream, may still read the slices' scratch
+    if (!c->fgFence.wait(stream)) return PVOL_E_NO_DEVICE;
     if (!pvol_reserve(c->buf[PVOL_BUF_FG_DIRS], 2 * sliceRecs * sizeof(pvol_gather_sample), stream) ||
         (ownRays && !pvol_reserve(c->buf[PVOL_BUF_FG_RAYS], 2 * sliceRecs * sizeof(pvol_gather_ray), stream)))
         return PVOL_E_NO_MEMORY;
@@ -205,7 +201,7 @@ int pvol_final_gather_device(pvol_ctx *c, const float *dP, const float *dFrames,
         hipLaunchKernelGGL(final_gather_sum_kernel, dim3((n + 7) / 8), dim3(256), 0, stream, A);
         if (!ok(hipGetLastError())) return PVOL_E_NO_DEVICE;
     }
-    return PVOL_OK;
+    return c->fgFence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 int pvol_final_gather(pvol_ctx *c, const float *p, const float *frames, const float *wo, const float *kd, const float *rayEps, uint32_t count,
@@ -218,31 +214,18 @@ int pvol_final_gather(pvol_ctx *c, const float *p, const float *frames, const fl
     if (rc != PVOL_OK) return rc;
     if (!count) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    const size_t nO = (size_t)count * nSamples, nU = 3 * nO;
-    DevPtr<float> dP, dFrames, dWo, dKd, dEps, dUB, dUP, dL;
-    DevPtr<uint32_t> dDraws;
-    DevPtr<pvol_gather_ray> dRB, dRP;
-    if (!dP.alloc(3 * (size_t)count) || !dFrames.alloc(9 * (size_t)count) || !dWo.alloc(3 * (size_t)count) || !dKd.alloc(30 * (size_t)count) ||
-        !dEps.alloc(count) || !dUB.alloc(nU) || !dUP.alloc(nU) || !dL.alloc(30 * (size_t)count) || !dDraws.alloc(count) ||
-        (raysBsdf && !dRB.alloc(nO)) || (raysPhoton && !dRP.alloc(nO)))
-        return PVOL_E_NO_MEMORY;
-    if (!ok(hipMemcpy(dP.get(), p, sizeof(float) * 3 * (size_t)count, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dFrames.get(), frames, sizeof(float) * 9 * (size_t)count, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dWo.get(), wo, sizeof(float) * 3 * (size_t)count, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dKd.get(), kd, sizeof(float) * 30 * (size_t)count, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dEps.get(), rayEps, sizeof(float) * (size_t)count, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dUB.get(), uBsdf, sizeof(float) * nU, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dUP.get(), uPhoton, sizeof(float) * nU, hipMemcpyHostToDevice)))
-        return PVOL_E_NO_DEVICE;
-    rc = pvol_final_gather_device(c, dP.get(), dFrames.get(), dWo.get(), dKd.get(), dEps.get(), count, maxDist, nSamples, cosGatherAngle, dUB.get(),
-                                  dUP.get(), dL.get(), dDraws.get(), dRB.get(), dRP.get(), 0);
+    const size_t n = count, nO = n * nSamples, nU = 3 * nO;
+    HostStage st;
+    const float *dP = st.in(p, 3 * n), *dFrames = st.in(frames, 9 * n), *dWo = st.in(wo, 3 * n), *dKd = st.in(kd, 30 * n), *dEps = st.in(rayEps, n);
+    const float *dUB = st.in(uBsdf, nU), *dUP = st.in(uPhoton, nU);
+    float *dL = st.out(L, 30 * n);
+    uint32_t *dDraws = st.out(draws, n);
+    pvol_gather_ray *dRB = st.out(raysBsdf, nO), *dRP = st.out(raysPhoton, nO);
+    if ((rc = st.upload()) != PVOL_OK) return rc;
+    rc = pvol_final_gather_device(c, dP, dFrames, dWo, dKd, dEps, count, maxDist, nSamples, cosGatherAngle, dUB, dUP, dL, dDraws, dRB, dRP, 0);
     if (rc != PVOL_OK) return rc;
     if (!ok(hipDeviceSynchronize())) return PVOL_E_NO_DEVICE;   // nothing is written unless all of it ran
-    const bool good = ok(hipMemcpy(L, dL.get(), sizeof(float) * 30 * (size_t)count, hipMemcpyDeviceToHost)) &&
-                      ok(hipMemcpy(draws, dDraws.get(), sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost)) &&
-                      (!raysBsdf || ok(hipMemcpy(raysBsdf, dRB.get(), sizeof(pvol_gather_ray) * nO, hipMemcpyDeviceToHost))) &&
-                      (!raysPhoton || ok(hipMemcpy(raysPhoton, dRP.get(), sizeof(pvol_gather_ray) * nO, hipMemcpyDeviceToHost)));
-    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return st.download();
 }
 
 }  // extern "C"

@@ -20,8 +20,6 @@
 #define GATHER_INV_PI 0.31830988618379067154f /* core/pbrt.h:192 */
 #define GATHER_NONE 0xffffffffu
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 struct GatherArgs {
     const float4 *nodes4;   // GatherNode as two float4: {p, splitPos}, {splitAxis, hasLeftChild, rightChild, index} (bit patterns)
     const float *wi;        // [n][3] Photon::wi in the store's order
@@ -403,19 +401,14 @@ int pvol_gather_photons(pvol_ctx *c, const float *p, uint32_t count, float maxDi
     if (!c->gather.have) return PVOL_E_INVALID;
     if (!count) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    DevPtr<float> dP, dD2;
-    DevPtr<uint32_t> dIndex, dFound, dRounds;
-    if (!dP.alloc(3 * (size_t)count) || !dD2.alloc(GATHER_K * (size_t)count) || !dIndex.alloc(GATHER_K * (size_t)count) || !dFound.alloc(count) ||
-        !dRounds.alloc(count))
-        return PVOL_E_NO_MEMORY;
-    if (!ok(hipMemcpy(dP.get(), p, sizeof(float) * 3 * (size_t)count, hipMemcpyHostToDevice))) return PVOL_E_NO_DEVICE;
-    rc = pvol_gather_photons_device(c, dP.get(), count, maxDist, dIndex.get(), dD2.get(), dFound.get(), dRounds.get(), 0);
-    if (rc != PVOL_OK) return rc;
-    const bool good = ok(hipMemcpy(index, dIndex.get(), sizeof(uint32_t) * GATHER_K * (size_t)count, hipMemcpyDeviceToHost)) &&
-                      ok(hipMemcpy(d2, dD2.get(), sizeof(float) * GATHER_K * (size_t)count, hipMemcpyDeviceToHost)) &&
-                      ok(hipMemcpy(found, dFound.get(), sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost)) &&
-                      ok(hipMemcpy(rounds, dRounds.get(), sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost));
-    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+    HostStage st;
+    const float *dP = st.in(p, 3 * (size_t)count);
+    uint32_t *dIndex = st.out(index, GATHER_K * (size_t)count);
+    float *dD2 = st.out(d2, GATHER_K * (size_t)count);
+    uint32_t *dFound = st.out(found, count), *dRounds = st.out(rounds, count);
+    if ((rc = st.upload()) != PVOL_OK) return rc;
+    rc = pvol_gather_photons_device(c, dP, count, maxDist, dIndex, dD2, dFound, dRounds, 0);
+    return rc != PVOL_OK ? rc : st.download();   // the copy-back on the null stream waits for the kernel
 }
 
 int pvol_gather_directions_device(pvol_ctx *c, const float *dP, const float *dFrames, const float *dWo, uint32_t count, float maxDist, int32_t nSamples,
@@ -451,23 +444,13 @@ int pvol_gather_directions(pvol_ctx *c, const float *p, const float *frames, con
     if (!count) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
     const size_t nU = 3 * (size_t)count * nSamples, nO = (size_t)count * nSamples;
-    DevPtr<float> dP, dFrames, dWo, dUB, dUP;
-    DevPtr<pvol_gather_sample> dOB, dOP;
-    if (!dP.alloc(3 * (size_t)count) || !dFrames.alloc(9 * (size_t)count) || !dWo.alloc(3 * (size_t)count) || !dUB.alloc(nU) || !dUP.alloc(nU) ||
-        !dOB.alloc(nO) || !dOP.alloc(nO))
-        return PVOL_E_NO_MEMORY;
-    if (!ok(hipMemcpy(dP.get(), p, sizeof(float) * 3 * (size_t)count, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dFrames.get(), frames, sizeof(float) * 9 * (size_t)count, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dWo.get(), wo, sizeof(float) * 3 * (size_t)count, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dUB.get(), uBsdf, sizeof(float) * nU, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dUP.get(), uPhoton, sizeof(float) * nU, hipMemcpyHostToDevice)))
-        return PVOL_E_NO_DEVICE;
-    rc = pvol_gather_directions_device(c, dP.get(), dFrames.get(), dWo.get(), count, maxDist, nSamples, cosGatherAngle, dUB.get(), dUP.get(), dOB.get(),
-                                       dOP.get(), 0);
-    if (rc != PVOL_OK) return rc;
-    const bool good = ok(hipMemcpy(outBsdf, dOB.get(), sizeof(pvol_gather_sample) * nO, hipMemcpyDeviceToHost)) &&
-                      ok(hipMemcpy(outPhoton, dOP.get(), sizeof(pvol_gather_sample) * nO, hipMemcpyDeviceToHost));
-    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+    HostStage st;
+    const float *dP = st.in(p, 3 * (size_t)count), *dFrames = st.in(frames, 9 * (size_t)count), *dWo = st.in(wo, 3 * (size_t)count);
+    const float *dUB = st.in(uBsdf, nU), *dUP = st.in(uPhoton, nU);
+    pvol_gather_sample *dOB = st.out(outBsdf, nO), *dOP = st.out(outPhoton, nO);
+    if ((rc = st.upload()) != PVOL_OK) return rc;
+    rc = pvol_gather_directions_device(c, dP, dFrames, dWo, count, maxDist, nSamples, cosGatherAngle, dUB, dUP, dOB, dOP, 0);
+    return rc != PVOL_OK ? rc : st.download();   // the copy-back on the null stream waits for the kernel
 }
 
 }  // extern "C"

@@ -12,8 +12,6 @@
 
 #include "pvol_host.h"
 
-static inline bool ok(hipError_t e) { return e == hipSuccess; }
-
 #define PVOL_GROUP_MAX_CTX 64u
 
 // dst[i] += staged[0][i] + ... + staged[nStaged-1][i], added in that order whatever the schedule, so the sum is a pure function of
@@ -189,11 +187,11 @@ extern "C" int pvol_render_frame_group_window(pvol_ctx *const *ctxs, uint32_t n,
         if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
         const hipStream_t s = streamOf(i);
         // the root's last reduce (stage copies, sum, resolve) may still be reading this film
-        if (root->groupStageEv && !ok(hipStreamWaitEvent(s, root->groupStageEv, 0))) return PVOL_E_NO_DEVICE;
+        if (root->groupStageEv.get() && !ok(hipStreamWaitEvent(s, root->groupStageEv.get(), 0))) return PVOL_E_NO_DEVICE;
         const int r = render_share(c, camera, film, window, smp, i, n, dPixels[i], s);
         if (r != PVOL_OK || i == 0) return r;
-        if (!c->groupFilmEv && !ok(hipEventCreateWithFlags(&c->groupFilmEv, hipEventDisableTiming))) { c->groupFilmEv = 0; return PVOL_E_NO_DEVICE; }
-        return ok(hipEventRecord(c->groupFilmEv, s)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+        if (!c->groupFilmEv.create()) return PVOL_E_NO_DEVICE;
+        return ok(hipEventRecord(c->groupFilmEv.get(), s)) ? PVOL_OK : PVOL_E_NO_DEVICE;
     }, [](uint32_t) {});
     for (uint32_t i = 0; i < n; ++i) if (rc[i] != PVOL_OK) return rc[i];
 
@@ -204,13 +202,13 @@ extern "C" int pvol_render_frame_group_window(pvol_ctx *const *ctxs, uint32_t n,
     if (n > 1) {
         DevBuf &stage = root->buf[PVOL_BUF_GROUP_STAGE];
         const size_t need = filmBytes * (n - 1);
-        if (need > stage.bytes && root->groupStageEv && !ok(hipEventSynchronize(root->groupStageEv))) return PVOL_E_NO_DEVICE;   // the last sum read it
+        if (need > stage.bytes && root->groupStageEv.get() && !ok(hipEventSynchronize(root->groupStageEv.get()))) return PVOL_E_NO_DEVICE;   // the last sum read it
         if (!pvol_reserve(stage, need, s0)) return PVOL_E_NO_MEMORY;
         float4 *const dStage = (float4 *)stage.p.get();
-        if (!root->groupStageEv && !ok(hipEventCreateWithFlags(&root->groupStageEv, hipEventDisableTiming))) { root->groupStageEv = 0; return PVOL_E_NO_DEVICE; }
+        if (!root->groupStageEv.create()) return PVOL_E_NO_DEVICE;
         const int dev0 = root->params.device;
         for (uint32_t i = 1; i < n; ++i) {
-            if (!ok(hipStreamWaitEvent(s0, ctxs[i]->groupFilmEv, 0)) ||
+            if (!ok(hipStreamWaitEvent(s0, ctxs[i]->groupFilmEv.get(), 0)) ||
                 !ok(hipMemcpyPeerAsync(dStage + (size_t)(i - 1) * nPix, dev0, dPixels[i], ctxs[i]->params.device, filmBytes, s0)))
                 return PVOL_E_NO_DEVICE;
         }
@@ -220,7 +218,7 @@ extern "C" int pvol_render_frame_group_window(pvol_ctx *const *ctxs, uint32_t n,
         if (!ok(hipGetLastError())) return PVOL_E_NO_DEVICE;
     }
     int rc0 = dRgb ? pvol_film_resolve_window_device(root, film, window, dPixels[0], dRgb, s0) : PVOL_OK;
-    if (n > 1 && rc0 == PVOL_OK && !ok(hipEventRecord(root->groupStageEv, s0))) rc0 = PVOL_E_NO_DEVICE;
+    if (n > 1 && rc0 == PVOL_OK && !ok(hipEventRecord(root->groupStageEv.get(), s0))) rc0 = PVOL_E_NO_DEVICE;
     return rc0;
 }
 extern "C" int pvol_render_frame_group(pvol_ctx *const *ctxs, uint32_t n, const pvol_camera *camera, const pvol_film *film,

@@ -1,5 +1,5 @@
-// pvol_host.h -- host-side internals shared by the host units (pvol_api.hip, pvol_scene_host.hip, pvol_map_host.hip, pvol_shoot_host.hip, pvol_probe.hip,
-// pvol_render_host.hip)
+// pvol_host.h -- host-side internals shared by every unit with host code: the owners of device memory and events, the context, the
+// kernels' launchers, the plans and the test entries that are no part of include/pvol.h
 #ifndef PVOL_HOST_H
 #define PVOL_HOST_H
 #include <hip/hip_runtime.h>
@@ -10,6 +10,9 @@
 #include <mutex>
 #include <vector>
 #include "pvol_dev.h"
+#include "pvol_rays_plan.h"
+
+static bool ok(hipError_t e) { return e == hipSuccess; }
 
 #define PVOL_LOCAL __attribute__((visibility("hidden")))   // shared by the host units, not an export of the library
 
@@ -34,6 +37,80 @@ template <class T> struct PVOL_LOCAL DevPtr {
 private:
     T *p = 0;
 };
+
+// An event with an owner: move-only, created on first use (for ordering only, no timing), destroyed by its destructor.
+struct PVOL_LOCAL DevEvent {
+    DevEvent() {}
+    DevEvent(DevEvent &&o) : e(o.e) { o.e = 0; }
+    DevEvent &operator=(DevEvent &&o) { std::swap(e, o.e); return *this; }
+    DevEvent(const DevEvent &) = delete;
+    DevEvent &operator=(const DevEvent &) = delete;
+    ~DevEvent() { if (e) hipEventDestroy(e); }
+    bool create() {
+        if (e || ok(hipEventCreateWithFlags(&e, hipEventDisableTiming))) return true;
+        e = 0;
+        return false;
+    }
+    hipEvent_t get() const { return e; }   // 0 before the first create()
+private:
+    hipEvent_t e = 0;
+};
+
+// What lets a call on any stream reuse scratch of the context behind the previous call's kernels: wait() in front of
+// the first reserve, record() behind the last launch.  Both false on a HIP error.
+struct PVOL_LOCAL ScratchFence {
+    bool wait(hipStream_t stream) { return ev.get() ? ok(hipStreamWaitEvent(stream, ev.get(), 0)) : ev.create(); }
+    bool record(hipStream_t stream) { return ok(hipEventRecord(ev.get(), stream)); }
+private:
+    DevEvent ev;
+};
+
+// The device copies of one host-array call: move-only, freed by its destructor.  in / out / inout allocate the copy of
+// `count` items and register its upload / copy-back / both, scratch only allocates; a NULL host array gives a NULL device pointer and
+// nothing to copy.  upload(): PVOL_E_NO_MEMORY if any allocation failed, before anything is uploaded; either copy loop runs in the
+// order of registration and returns PVOL_E_NO_DEVICE at the first failure.  download() is the only place the caller's arrays are
+// written: the entry point calls it once everything ran.
+struct PVOL_LOCAL HostStage {
+    HostStage() {}
+    HostStage(HostStage &&) = default;
+    HostStage &operator=(HostStage &&) = default;
+    HostStage(const HostStage &) = delete;
+    HostStage &operator=(const HostStage &) = delete;
+    template <class T> T *in(const T *host, size_t count) { return host ? (T *)add((void *)host, sizeof(T) * count, UP) : 0; }
+    template <class T> T *out(T *host, size_t count) { return host ? (T *)add(host, sizeof(T) * count, DOWN) : 0; }
+    template <class T> T *inout(T *host, size_t count) { return host ? (T *)add(host, sizeof(T) * count, UP | DOWN) : 0; }
+    template <class T> T *scratch(size_t count) { return (T *)add(0, sizeof(T) * count, 0); }
+    int upload() const { return noMemory ? PVOL_E_NO_MEMORY : copy(UP); }
+    int download() const { return copy(DOWN); }
+private:
+    enum { UP = 1, DOWN = 2 };
+    struct Item { DevPtr<unsigned char> d; void *host; size_t bytes; int dir; };
+    std::vector<Item> items;
+    bool noMemory = false;
+    void *add(void *host, size_t bytes, int dir) {
+        Item it;
+        if (!it.d.alloc(bytes)) { noMemory = true; return 0; }
+        it.host = host; it.bytes = bytes; it.dir = dir;
+        items.push_back(std::move(it));
+        return items.back().d.get();
+    }
+    int copy(int dir) const {
+        for (const Item &it : items)
+            if ((it.dir & dir) && !ok(dir == UP ? hipMemcpy(it.d.get(), it.host, it.bytes, hipMemcpyHostToDevice)
+                                                : hipMemcpy(it.host, it.d.get(), it.bytes, hipMemcpyDeviceToHost)))
+                return PVOL_E_NO_DEVICE;
+        return PVOL_OK;
+    }
+};
+
+// Items per slice of a sliced entry point: as many as keep `bytesPerItem` each within `bound` bytes (0 or more than `cap`: that),
+// whole runs of 64 where that many fit, never fewer than one.
+static inline uint32_t pvol_slice_items(uint64_t bound, uint64_t cap, uint64_t bytesPerItem) {
+    if (!bound || bound > cap) bound = cap;
+    uint64_t n = bound / bytesPerItem;
+    if (n >= 64) n -= n % 64;
+    return (uint32_t)std::max<uint64_t>(n, 1);
+}
 
 // ---- kernels' host entry points (pvol_march.hip, pvol_grid.hip)
 #include "pvol_liargs.h"
@@ -238,13 +315,14 @@ struct pvol_ctx {
     RadianceResult rad;    // pvol_compute_radiance*: dropped by every shoot and by pvol_free_surface_stores
     GatherMap gather;      // pvol_build_gather_map*: dropped wherever `rad` is
     uint64_t fgScratchBound = 0;   // pvol_final_gather_set_scratch_bound (tests): bytes of scratch a slice may take, 0 = PVOL_FINAL_GATHER_SCRATCH_BYTES
+    ScratchFence fgFence;          // pvol_final_gather_device: as lpFence, for PVOL_BUF_FG_DIRS and PVOL_BUF_FG_RAYS
     // pvol_lphoton_batch* (pvol_lphoton.hip)
     bool lpNoSort = false;         // PVOL_LPHOTON_NO_SORT=1: the points are served in the caller's order (testing; the results are the same bytes)
     uint64_t lpScratchBound = 0;   // pvol_lphoton_set_scratch_bound (tests): bytes of ordering scratch a slice may take, 0 = PVOL_LPHOTON_SCRATCH_BYTES
-    hipEvent_t lpEv = 0;           // the end of the last call's kernels: the next call, on whatever stream, reuses their scratch behind it
+    ScratchFence lpFence;          // the end of the last call's kernels: the next call, on whatever stream, reuses their scratch behind it
     // pvol_radiance_batch* (pvol_rays.hip)
     uint64_t rrScratchBound = 0;   // pvol_radiance_set_scratch_bound (tests): bytes of scratch a slice may take, 0 = PVOL_RADIANCE_SCRATCH_BYTES
-    hipEvent_t rrEv = 0;           // the end of the last call's kernels: the next call, on whatever stream, reuses their scratch behind it
+    ScratchFence rrFence;          // as lpFence
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     PhotonGrid causticMap;
     // ... and its indirect map (pvol_set_surface_integrator_maps: LPhoton(indirectMap) without the final gather), built by the same builder
@@ -271,7 +349,7 @@ struct pvol_ctx {
     uint32_t coCap = 0;
     // pvol_render_frame_group (pvol_group.hip): the event marking this context's film done; as the root, the event after the sum
     // that last read the other films' staging (PVOL_BUF_GROUP_STAGE)
-    hipEvent_t groupFilmEv = 0, groupStageEv = 0;
+    DevEvent groupFilmEv, groupStageEv;
 };
 
 // One per-sample call of a coalesced batch: the caller's buffers, written only when rc ends PVOL_OK.
@@ -406,7 +484,7 @@ struct FinalGatherCheck {
 };
 int pvol_check_final_gather(int haveCtx, const FinalGatherCheck *args, int haveScene, int volKind, int haveGather, int haveRad, uint32_t radN);
 // queries per slice of pvol_final_gather*: as many as keep a slice's scratch (64 bytes per gather ray, 2 n_samples rays per query)
-// within `bound` bytes (0 or more than PVOL_FINAL_GATHER_SCRATCH_BYTES: that), whole blocks of 64 where that many fit, never fewer than one
+// within `bound` bytes (pvol_slice_items under PVOL_FINAL_GATHER_SCRATCH_BYTES)
 uint32_t pvol_final_gather_slice(int32_t nSamples, uint64_t bound);
 // lowers (or, with 0, restores) the scratch bound of this context's pvol_final_gather* calls, for the tests
 int pvol_final_gather_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
@@ -415,7 +493,7 @@ int pvol_final_gather_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
 struct LPhotonCheck { const float *p, *w; uint32_t n; int32_t outputKind; const void *out; };
 int pvol_check_lphoton(int haveCtx, const LPhotonCheck *args, int haveScene, float g);
 // points per slice of pvol_lphoton_batch*: as many as keep a slice's ordering scratch (PVOL_LPHOTON_POINT_SCRATCH bytes per point)
-// within `bound` bytes (0 or more than PVOL_LPHOTON_SCRATCH_BYTES: that), whole runs of 64 where that many fit, never fewer than one
+// within `bound` bytes (pvol_slice_items under PVOL_LPHOTON_SCRATCH_BYTES)
 #define PVOL_LPHOTON_POINT_SCRATCH 16u
 uint32_t pvol_lphoton_slice(uint64_t bound);
 // lowers (or, with 0, restores) the scratch bound of this context's pvol_lphoton_batch* calls, for the tests
@@ -425,14 +503,18 @@ int pvol_lphoton_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
 // (pvol_check_radiance is the radiance photons' check above; this one carries the entry point's full name.)
 struct RadianceBatchCheck { const void *rays, *streams; uint32_t nRays, nStreams; int32_t outputKind; const pvol_radiance_out *out; };
 int pvol_radiance_batch_check(int haveCtx, const RadianceBatchCheck *args, int haveScene, int volKind, int surfOn);
-// caller rays per slice of pvol_radiance_batch*: as many as keep a slice's scratch within `bound` bytes (0 or more than
-// PVOL_RADIANCE_SCRATCH_BYTES: that) when every ray spawns maxSegments rays -- PVOL_RADIANCE_RAY_SCRATCH bytes per expanded ray (48 of
-// ray, 32 of SegInfo, 240 of output, 4 of draw count), PVOL_RADIANCE_CALLER_SCRATCH per caller ray (its stashed row, block size and
-// offset) -- whole runs of 64 where that many fit, never fewer than one.  maxSegments: pvol_radiance_max_segments for the worst case; the
+// caller rays per slice of pvol_radiance_batch*: as many as keep a slice's scratch within `bound` bytes (pvol_slice_items under
+// PVOL_RADIANCE_SCRATCH_BYTES) when every ray spawns maxSegments rays -- PVOL_RADIANCE_RAY_SCRATCH bytes per expanded ray and
+// PVOL_RADIANCE_CALLER_SCRATCH per caller ray (pvol_rays_plan.h).  maxSegments: pvol_radiance_max_segments for the worst case; the
 // entry point asks with 0 (nobody spawns), counts, and cuts the slice back to the longest run of its rays whose blocks fit
-#define PVOL_RADIANCE_RAY_SCRATCH 324u
-#define PVOL_RADIANCE_CALLER_SCRATCH 248u
 uint32_t pvol_radiance_slice(uint32_t maxSegments, uint64_t bound);
+// rays_slice_cut and rays_slice_streams (pvol_rays_plan.h) for the tests.  The second: the table of the slice [r0, r1) of a call of
+// nRays rays over `streams`, from stream *s on: table (room for nStreams entries) gets the slice's entries, out3 = {s0, entries,
+// continued}, *s the next slice's first stream, *maxRays what streams_partition reports.  PVOL_E_INVALID: a NULL pointer, streams
+// that do not partition [0, nRays), *s > nStreams, or not r0 < r1 <= nRays
+uint32_t pvol_radiance_slice_cut(const uint32_t *offset, uint32_t n, uint64_t budget);
+int pvol_radiance_slice_streams(const pvol_stream *streams, uint32_t nStreams, uint32_t nRays, uint32_t r0, uint32_t r1, uint32_t *s,
+                                pvol_stream *table, uint32_t *out3, uint32_t *maxRays);
 // rays the specular recursion can spawn for one ray: 2 + 4 + ... + 2^(maxSpecularDepth - 1), 0 unless specOn (glass in the scene, the
 // surface integrator on, maxspeculardepth > 1)
 uint32_t pvol_radiance_max_segments(int specOn, int32_t maxSpecularDepth);

@@ -16,8 +16,6 @@
 
 #include "pvol_host.h"
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 // Staging of one batch of n calls (offsets in bytes, sections packed by n so that one copy moves each direction):
 //   in : rays [n] | streams [n] | states [n][625]
 //   out: Lv,T [n][60] | states [n][625] | status [n] | the gate word of the backups (one uint32)

@@ -11,8 +11,6 @@
 
 #include "pvol_host.h"
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 extern "C" {
 
 int pvol_check_lphoton(int haveCtx, const LPhotonCheck *a, int haveScene, float g) {
@@ -26,10 +24,7 @@ int pvol_check_lphoton(int haveCtx, const LPhotonCheck *a, int haveScene, float 
 
 uint32_t pvol_lphoton_slice(uint64_t bound) {
     // the header's bound is the largest: a slice then holds at most 2^22 points, well inside the sort's int count
-    if (!bound || bound > PVOL_LPHOTON_SCRATCH_BYTES) bound = PVOL_LPHOTON_SCRATCH_BYTES;
-    uint64_t n = bound / PVOL_LPHOTON_POINT_SCRATCH;
-    if (n >= 64) n -= n % 64;
-    return (uint32_t)std::max<uint64_t>(n, 1);
+    return pvol_slice_items(bound, PVOL_LPHOTON_SCRATCH_BYTES, PVOL_LPHOTON_POINT_SCRATCH);
 }
 
 int pvol_lphoton_set_scratch_bound(pvol_ctx *c, uint64_t bytes) {
@@ -63,8 +58,7 @@ int pvol_lphoton_batch_device(pvol_ctx *c, const float *dP, const float *dW, uin
         return PVOL_OK;
     }
     // an earlier call's kernels, on whatever stream, may still read the ordering scratch
-    if (c->lpEv) { if (!ok(hipStreamWaitEvent(stream, c->lpEv, 0))) return PVOL_E_NO_DEVICE; }
-    else if (!ok(hipEventCreateWithFlags(&c->lpEv, hipEventDisableTiming))) { c->lpEv = 0; return PVOL_E_NO_DEVICE; }
+    if (!c->lpFence.wait(stream)) return PVOL_E_NO_DEVICE;
     const uint32_t slice = std::min(n, pvol_lphoton_slice(c->lpScratchBound));
     const bool sort = !c->lpNoSort;
     size_t tempBytes = 0;
@@ -96,8 +90,7 @@ int pvol_lphoton_batch_device(pvol_ctx *c, const float *dP, const float *dW, uin
         const uint32_t nWaves = std::min(maxWaves, (nRuns + 7u) / 8u);
         if (!ok(launch.lphotonPoints(&A, c->hs.candCap, nWaves, stream))) return PVOL_E_NO_DEVICE;
     }
-    if (!ok(hipEventRecord(c->lpEv, stream))) return PVOL_E_NO_DEVICE;
-    return PVOL_OK;
+    return c->lpFence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 int pvol_lphoton_batch(pvol_ctx *c, const float *p, const float *w, uint32_t n, int outputKind, float *out, uint32_t *nFound, float *radius2) {
@@ -108,21 +101,16 @@ int pvol_lphoton_batch(pvol_ctx *c, const float *p, const float *w, uint32_t n, 
     if (rc != PVOL_OK) return rc;
     if (!n) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    const size_t nOut = (size_t)(outputKind == PVOL_OUT_SPECTRAL ? 30 : 4) * n;
-    DevPtr<float> dP, dW, dOut, dR2;
-    DevPtr<uint32_t> dNF;
-    if (!dP.alloc(3 * (size_t)n) || (w && !dW.alloc(3 * (size_t)n)) || !dOut.alloc(nOut) || (nFound && !dNF.alloc(n)) || (radius2 && !dR2.alloc(n)))
-        return PVOL_E_NO_MEMORY;
-    if (!ok(hipMemcpy(dP.get(), p, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice)) ||
-        (w && !ok(hipMemcpy(dW.get(), w, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice))))
-        return PVOL_E_NO_DEVICE;
-    rc = pvol_lphoton_batch_device(c, dP.get(), dW.get(), n, outputKind, dOut.get(), dNF.get(), dR2.get(), 0);
+    HostStage st;
+    const float *dP = st.in(p, 3 * (size_t)n), *dW = st.in(w, 3 * (size_t)n);
+    float *dOut = st.out(out, (size_t)(outputKind == PVOL_OUT_SPECTRAL ? 30 : 4) * n);
+    uint32_t *dNF = st.out(nFound, n);
+    float *dR2 = st.out(radius2, n);
+    if ((rc = st.upload()) != PVOL_OK) return rc;
+    rc = pvol_lphoton_batch_device(c, dP, dW, n, outputKind, dOut, dNF, dR2, 0);
     if (rc != PVOL_OK) return rc;
     if (!ok(hipDeviceSynchronize())) return PVOL_E_NO_DEVICE;   // nothing is written unless all of it ran
-    const bool good = ok(hipMemcpy(out, dOut.get(), sizeof(float) * nOut, hipMemcpyDeviceToHost)) &&
-                      (!nFound || ok(hipMemcpy(nFound, dNF.get(), sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost))) &&
-                      (!radius2 || ok(hipMemcpy(radius2, dR2.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost)));
-    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return st.download();
 }
 
 }  // extern "C"

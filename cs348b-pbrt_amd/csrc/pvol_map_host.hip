@@ -13,8 +13,6 @@
 
 #include "pvol_host.h"
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 static GridBuildArgs grid_args(const PhotonGrid &G, const float *const raw[3], const MapFilter &f, int sub) {
     GridBuildArgs g;
     memset(&g, 0, sizeof(g));

@@ -18,8 +18,6 @@
 #define RAD_MAX_LOOKUP 576   // the project's nused bound
 #define RAD_INV_PI 0.31830988618379067154f   /* core/pbrt.h:192 */
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 // One surface map as radiance_lo_kernel reads it
 struct RadMap {
     GridView g;
@@ -381,15 +379,13 @@ int pvol_radiance_lookup(pvol_ctx *c, const float *p, const float *n, uint32_t c
     if (!c->rad.have) return PVOL_E_INVALID;
     if (!count) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
-    DevPtr<float> dP, dN, dLo;
-    DevPtr<uint32_t> dFound;
-    if (!dP.alloc(3 * (size_t)count) || !dN.alloc(3 * (size_t)count) || !dLo.alloc(30 * (size_t)count) || !dFound.alloc(count)) return PVOL_E_NO_MEMORY;
-    const bool good = ok(hipMemcpy(dP.get(), p, sizeof(float) * 3 * (size_t)count, hipMemcpyHostToDevice)) &&
-                      ok(hipMemcpy(dN.get(), n, sizeof(float) * 3 * (size_t)count, hipMemcpyHostToDevice)) &&
-                      ok(launch_nearest(c, dP.get(), dN.get(), count, dLo.get(), dFound.get(), 0)) &&
-                      ok(hipMemcpy(lo, dLo.get(), sizeof(float) * 30 * (size_t)count, hipMemcpyDeviceToHost)) &&
-                      ok(hipMemcpy(found, dFound.get(), sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost));
-    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+    HostStage st;
+    const float *dP = st.in(p, 3 * (size_t)count), *dN = st.in(n, 3 * (size_t)count);
+    float *dLo = st.out(lo, 30 * (size_t)count);
+    uint32_t *dFound = st.out(found, count);
+    if ((rc = st.upload()) != PVOL_OK) return rc;
+    if (!ok(launch_nearest(c, dP, dN, count, dLo, dFound, 0))) return PVOL_E_NO_DEVICE;
+    return st.download();   // the copy-back on the null stream waits for the kernel
 }
 
 int pvol_radiance_lookup_device(pvol_ctx *c, const float *dP, const float *dN, uint32_t count, float *dLo, uint32_t *dFound, void *hipStream) {

@@ -13,8 +13,6 @@
 
 #include "pvol_host.h"
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 extern "C" {
 
 int pvol_radiance_batch_check(int haveCtx, const RadianceBatchCheck *a, int haveScene, int volKind, int surfOn) {
@@ -33,11 +31,20 @@ uint32_t pvol_radiance_max_segments(int specOn, int32_t maxSpecularDepth) {
 }
 
 uint32_t pvol_radiance_slice(uint32_t maxSegments, uint64_t bound) {
-    if (!bound || bound > PVOL_RADIANCE_SCRATCH_BYTES) bound = PVOL_RADIANCE_SCRATCH_BYTES;
-    const uint64_t perRay = ((uint64_t)maxSegments + 1u) * PVOL_RADIANCE_RAY_SCRATCH + PVOL_RADIANCE_CALLER_SCRATCH;
-    uint64_t n = bound / perRay;
-    if (n >= 64) n -= n % 64;
-    return (uint32_t)std::max<uint64_t>(n, 1);
+    return pvol_slice_items(bound, PVOL_RADIANCE_SCRATCH_BYTES, ((uint64_t)maxSegments + 1u) * PVOL_RADIANCE_RAY_SCRATCH + PVOL_RADIANCE_CALLER_SCRATCH);
+}
+
+uint32_t pvol_radiance_slice_cut(const uint32_t *offset, uint32_t n, uint64_t budget) { return offset ? rays_slice_cut(offset, n, budget) : 0u; }
+
+int pvol_radiance_slice_streams(const pvol_stream *streams, uint32_t nStreams, uint32_t nRays, uint32_t r0, uint32_t r1, uint32_t *s,
+                                pvol_stream *table, uint32_t *out3, uint32_t *maxRays) {
+    if (!streams || !s || !table || !out3 || !maxRays || *s > nStreams || !(r0 < r1 && r1 <= nRays)) return PVOL_E_INVALID;
+    if (!streams_partition(streams, nStreams, nRays, maxRays)) return PVOL_E_INVALID;
+    std::vector<pvol_stream> t;
+    const RaysSliceStreams w = rays_slice_streams(streams, nStreams, r0, r1, nRays, *s, t);
+    std::copy(t.begin(), t.end(), table);
+    out3[0] = w.s0; out3[1] = w.n; out3[2] = w.continued;
+    return PVOL_OK;
 }
 
 int pvol_radiance_set_scratch_bound(pvol_ctx *c, uint64_t bytes) {
@@ -53,16 +60,6 @@ static int check_ctx(const pvol_ctx *c, const RadianceBatchCheck *a) {
     return pvol_radiance_batch_check(c != 0, a, c && c->haveScene, c ? c->hs.volKind : 0, c && c->hs.surf.enabled != 0);
 }
 
-// the streams partition the ray array in order, as host_batch asks (pvol_api.hip)
-static bool streams_partition(const pvol_stream *st, uint32_t nStreams, uint32_t nRays) {
-    uint64_t next = 0;
-    for (uint32_t s = 0; s < nStreams; ++s) {
-        if (st[s].first_ray != next) return false;
-        next += st[s].n_rays;
-    }
-    return next == nRays;
-}
-
 // The call, slice by slice, on device arrays.  hs: host copy of the caller's stream table (already checked).  Caller holds apiMu and has
 // the device set.
 static int radiance_slices(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, pvol_stream *dStreams, const std::vector<pvol_stream> &hs,
@@ -75,8 +72,7 @@ static int radiance_slices(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, p
     const uint64_t budget = c->rrScratchBound ? c->rrScratchBound : PVOL_RADIANCE_SCRATCH_BYTES;
     const uint32_t slice = std::min(nRays, pvol_radiance_slice(0, budget));
     // an earlier call's kernels, on whatever stream, may still read the scratch
-    if (c->rrEv) { if (!ok(hipStreamWaitEvent(stream, c->rrEv, 0))) return PVOL_E_NO_DEVICE; }
-    else if (!ok(hipEventCreateWithFlags(&c->rrEv, hipEventDisableTiming))) { c->rrEv = 0; return PVOL_E_NO_DEVICE; }
+    if (!c->rrFence.wait(stream)) return PVOL_E_NO_DEVICE;
     size_t tempBytes = 0;
     if (!ok(hipcub::DeviceScan::ExclusiveSum((void *)0, tempBytes, (const uint32_t *)0, (uint32_t *)0, (int)(slice + 1u), stream))) return PVOL_E_NO_DEVICE;
     if (!pvol_reserve(c->buf[PVOL_BUF_RR_COUNT], sizeof(uint32_t) * 2 * ((size_t)slice + 1), stream) ||
@@ -101,36 +97,17 @@ static int radiance_slices(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, p
             !ok(hipcub::DeviceScan::ExclusiveSum(pvol_buf<unsigned char>(c, PVOL_BUF_RR_TEMP), tb, (const uint32_t *)A.count, (uint32_t *)A.offset, (int)(n + 1u), stream)) ||
             !ok(hipMemcpyAsync(&total, A.offset + n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream)))
             return PVOL_E_NO_DEVICE;
-        if (n > 1 && (uint64_t)total * PVOL_RADIANCE_RAY_SCRATCH + (uint64_t)n * PVOL_RADIANCE_CALLER_SCRATCH > budget) {
-            // the longest run of the candidate's rays that fits (never fewer than one ray, whole runs of 64 where that many fit): the offsets
-            // of a run do not depend on what follows it, so the scan stands
+        if (n > 1 && !rays_slice_fits(total, n, budget)) {   // cut: the scan comes back only where the candidate does not fit
             hostOffset.resize((size_t)n + 1);
             if (!ok(hipMemcpy(hostOffset.data(), A.offset, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost))) return PVOL_E_NO_DEVICE;
-            uint32_t lo = 1, hi = n;   // fits(lo) is taken for granted, fits(hi) is false
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + (hi - lo) / 2;
-                if ((uint64_t)hostOffset[mid] * PVOL_RADIANCE_RAY_SCRATCH + (uint64_t)mid * PVOL_RADIANCE_CALLER_SCRATCH <= budget) lo = mid; else hi = mid;
-            }
-            n = lo >= 64 ? lo - lo % 64 : lo;
+            A.n = n = rays_slice_cut(hostOffset.data(), n, budget);
             total = hostOffset[n];
-            A.n = n;
         }
         const uint32_t r1 = r0 + n;
-        const bool last = r1 == nRays;
-        // the slice's streams: those with rays in [r0, r1), and the empty ones that stand there (at the very end: in the last slice)
         table.clear();
-        const uint32_t s0 = s;
-        for (; s < nStreams; ++s) {
-            const pvol_stream &h = hs[s];
-            const uint32_t end = h.first_ray + h.n_rays;
-            if (h.first_ray >= r1 && !(last && !h.n_rays)) break;
-            pvol_stream t = h;
-            t.first_ray = std::max(h.first_ray, r0) - r0; t.n_rays = std::min(end, r1) - std::max(h.first_ray, r0); t.end_draw = 0;
-            table.push_back(t);
-            if (end > r1) break;   // the boundary cuts this stream: the next slice begins with the rest of it
-        }
-        const uint32_t ns = (uint32_t)table.size();
-        const bool continued = ns && hs[s0].first_ray < r0;
+        const RaysSliceStreams w = rays_slice_streams(hs.data(), nStreams, r0, r1, nRays, s, table);
+        const uint32_t s0 = w.s0, ns = w.n;
+        const bool continued = w.continued;
         if (!pvol_reserve(c->buf[PVOL_BUF_RR_STREAMS], sizeof(pvol_stream) * std::max<size_t>(ns, 1), stream)) return PVOL_E_NO_MEMORY;
         pvol_stream *dTable = pvol_buf<pvol_stream>(c, PVOL_BUF_RR_STREAMS);
         // the table is read from pageable memory that the next slice rewrites: wait for the copy
@@ -167,7 +144,7 @@ static int radiance_slices(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, p
         if (!ok(pvol_launch_rays_compose(&A, dTable, ns, dStreams + s0, stream))) return PVOL_E_NO_DEVICE;
         r0 = r1;
     }
-    return ok(hipEventRecord(c->rrEv, stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return c->rrFence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 extern "C" {
@@ -185,7 +162,7 @@ int pvol_radiance_batch_device(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRay
     std::vector<pvol_stream> hs(nStreams);   // read on the caller's stream: ordered behind whatever produced the table
     if (!ok(hipMemcpyAsync(hs.data(), dStreams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyDeviceToHost, stream)) ||
         !ok(hipStreamSynchronize(stream))) return PVOL_E_NO_DEVICE;
-    if (!streams_partition(hs.data(), nStreams, nRays)) return PVOL_E_INVALID;
+    if (!streams_partition(hs.data(), nStreams, nRays, 0)) return PVOL_E_INVALID;
     return radiance_slices(c, dRays, nRays, dStreams, hs, outputKind, *out, stream);
 }
 
@@ -197,29 +174,19 @@ int pvol_radiance_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, pvol_
     int rc = check_ctx(c, &a);
     if (rc != PVOL_OK) return rc;
     if (!nRays || !nStreams) return PVOL_OK;
-    if (!streams_partition(streams, nStreams, nRays)) return PVOL_E_INVALID;
+    if (!streams_partition(streams, nStreams, nRays, 0)) return PVOL_E_INVALID;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
     const size_t width = outputKind == PVOL_OUT_SPECTRAL ? 60 : 4, n = nRays;
-    DevPtr<pvol_ray> dRays; DevPtr<pvol_stream> dStreams; DevPtr<float> dL, dSurf, dT; DevPtr<uint32_t> dDraws, dSurfDraws, dSeg;
-    if (!dRays.alloc(n) || !dStreams.alloc(nStreams) || !dL.alloc(width * n) || (out->surf_xyz && !dSurf.alloc(3 * n)) || (out->t_hit && !dT.alloc(n)) ||
-        (out->draws && !dDraws.alloc(n)) || (out->surf_draws && !dSurfDraws.alloc(n)) || (out->n_segments && !dSeg.alloc(n)))
-        return PVOL_E_NO_MEMORY;
-    if (!ok(hipMemcpy(dRays.get(), rays, sizeof(pvol_ray) * n, hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(dStreams.get(), streams, sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyHostToDevice)))
-        return PVOL_E_NO_DEVICE;
-    const pvol_radiance_out d = {dL.get(), dSurf.get(), dT.get(), dDraws.get(), dSurfDraws.get(), dSeg.get()};
-    rc = radiance_slices(c, dRays.get(), nRays, dStreams.get(), std::vector<pvol_stream>(streams, streams + nStreams), outputKind, d, 0);
+    HostStage st;
+    const pvol_ray *dRays = st.in(rays, n);
+    const pvol_radiance_out d = {st.out(out->L, width * n), st.out(out->surf_xyz, 3 * n), st.out(out->t_hit, n), st.out(out->draws, n),
+                                 st.out(out->surf_draws, n), st.out(out->n_segments, n)};
+    pvol_stream *dStreams = st.inout(streams, nStreams);
+    if ((rc = st.upload()) != PVOL_OK) return rc;
+    rc = radiance_slices(c, dRays, nRays, dStreams, std::vector<pvol_stream>(streams, streams + nStreams), outputKind, d, 0);
     if (rc == PVOL_OK && !ok(hipDeviceSynchronize())) rc = PVOL_E_NO_DEVICE;
     if (rc == PVOL_OK) rc = pvol_check_errors(c);
-    if (rc != PVOL_OK) return rc;   // nothing is written unless all of it ran
-    const bool good = ok(hipMemcpy(out->L, dL.get(), sizeof(float) * width * n, hipMemcpyDeviceToHost)) &&
-                      (!out->surf_xyz || ok(hipMemcpy(out->surf_xyz, dSurf.get(), sizeof(float) * 3 * n, hipMemcpyDeviceToHost))) &&
-                      (!out->t_hit || ok(hipMemcpy(out->t_hit, dT.get(), sizeof(float) * n, hipMemcpyDeviceToHost))) &&
-                      (!out->draws || ok(hipMemcpy(out->draws, dDraws.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost))) &&
-                      (!out->surf_draws || ok(hipMemcpy(out->surf_draws, dSurfDraws.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost))) &&
-                      (!out->n_segments || ok(hipMemcpy(out->n_segments, dSeg.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost))) &&
-                      ok(hipMemcpy(streams, dStreams.get(), sizeof(pvol_stream) * (size_t)nStreams, hipMemcpyDeviceToHost));
-    return good ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return rc != PVOL_OK ? rc : st.download();   // nothing is written unless all of it ran
 }
 
 }  // extern "C"

@@ -12,8 +12,6 @@
 
 #include "pvol_host.h"
 
-static inline bool ok(hipError_t e) { return e == hipSuccess; }
-
 // ------------------------------------------------------------------------------------------ the plan
 // The sampler carries the sample extent (the window's own, pvol_film_sample_extent, or any other): every size below -- the tasks'
 // sub-windows, the batches, the work buffers, the debug records -- comes from it, and only the splat reads the window.

@@ -11,7 +11,6 @@
 
 #include "pvol_host.h"
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
 static bool finite_f(float x) { return x == x && fabsf(x) != INFINITY; }
 
 // ---- host evaluation of the light-power CDF (ComputeLightSamplingCDF core/integrator.cpp:261-268,

@@ -12,8 +12,6 @@
 #include "pvol_shoot_args.h"
 #include "pvol_shoot_merge.h"
 
-static bool ok(hipError_t e) { return e == hipSuccess; }
-
 namespace {
 struct DevArr {   // device array of floats that grows geometrically, keeping the `used` floats it holds
     DevPtr<float> d;

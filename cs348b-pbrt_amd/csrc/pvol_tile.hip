@@ -15,8 +15,6 @@
 #include "pvol_host.h"
 #include "pvol_math.h"
 
-static inline bool ok(hipError_t e) { return e == hipSuccess; }
-
 // ------------------------------------------------------------------------------------------ host restatements
 extern "C" void pvol_gaussian_filter_table(float xw, float yw, float alpha, float *table) {
     // filters/gaussian.h:44-58 (expX, expY, Gaussian()), film/image.cpp:57-68 (table at cell centres)

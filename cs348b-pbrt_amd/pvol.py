@@ -179,6 +179,9 @@ def lib():
         L.pvol_radiance_batch_check.argtypes = [C.c_int, C.POINTER(abi.RadianceBatchCheck), C.c_int, C.c_int, C.c_int]
         L.pvol_radiance_slice.argtypes = [C.c_uint32, C.c_uint64]
         L.pvol_radiance_slice.restype = C.c_uint32
+        L.pvol_radiance_slice_cut.argtypes = [_u32p, C.c_uint32, C.c_uint64]
+        L.pvol_radiance_slice_cut.restype = C.c_uint32
+        L.pvol_radiance_slice_streams.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_void_p, _u32p, _u32p]
         L.pvol_radiance_max_segments.argtypes = [C.c_int, C.c_int32]
         L.pvol_radiance_max_segments.restype = C.c_uint32
         L.pvol_radiance_set_scratch_bound.argtypes = [C.c_void_p, C.c_uint64]

@@ -543,6 +543,43 @@ def test_forms_are_byte_equal(pvol, closed_case, shape_queries):
             assert t.cpu().numpy().tobytes() == (r.tobytes() if with_rays else np.full((count, ns, 8), 7, np.int32).tobytes())
 
 
+def test_two_streams_share_the_scratch_in_turn(pvol, closed_case, shape_queries):
+    """Two device calls over disjoint halves of the queries, enqueued back to back on two streams of their own, with the scratch
+    bound at one run of 64 queries so that both walk the same direction and ray scratch in two slices each.  The second call is
+    ordered behind the first one's kernels (the context's fence), so L and draws are the bytes one call on one stream gives."""
+    import torch
+    c = closed_case
+    Q, frames, wo, kd, eps = shape_queries
+    count, ns, half = len(Q), 16, len(Q) // 2
+    assert count == 210
+    u_b, u_p = _draws(np.random.default_rng(73), count, ns)
+    cos_g = pvol.gather_cos_angle(10.0)
+    bound = 2 * ns * 64 * 64
+    assert pvol.lib().pvol_final_gather_slice(ns, bound) == 64 < half
+
+    def run(parts, streams):
+        """one call per part [a, b) of the queries on its stream; the records stay in the context's scratch"""
+        dL = torch.full((count, 30), -1.0, dtype=torch.float32, device="cuda")
+        dD = torch.full((count,), 7, dtype=torch.int32, device="cuda")
+        d_in = [[torch.from_numpy(np.ascontiguousarray(x[a:b], F)).cuda() for x in (Q, frames, wo, kd, eps, u_b, u_p)] for a, b in parts]
+        torch.cuda.synchronize()   # the streams below do not wait for the null stream's copies
+        for (a, b), t, s in zip(parts, d_in, streams):
+            c.pv.final_gather_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), t[4].data_ptr(), b - a, 0.3, ns, cos_g,
+                                     t[5].data_ptr(), t[6].data_ptr(), dL[a:b].data_ptr(), dD[a:b].data_ptr(), 0, 0, s.cuda_stream)
+        torch.cuda.synchronize()   # once, behind both calls
+        return dL.cpu().numpy(), dD.cpu().numpy()
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    assert s1.cuda_stream != 0 and s2.cuda_stream != 0 and s1.cuda_stream != s2.cuda_stream
+    try:
+        c.pv.final_gather_set_scratch_bound(bound)
+        one = run([(0, count)], [s1])
+        two = run([(0, half), (half, count)], [s1, s2])
+    finally:
+        c.pv.final_gather_set_scratch_bound(0)
+    assert (one[0] != 0).any() and (one[1] > 0).any() and (one[0] != -1).all()
+    assert two[0].tobytes() == one[0].tobytes() and two[1].tobytes() == one[1].tobytes()
+
+
 def test_rejected_calls_and_life_cycle(pvol, closed_case, shape_queries):
     c = closed_case
     Q, frames, wo, kd, eps = (x[:16] for x in shape_queries)
