@@ -201,8 +201,8 @@ static int tile_waves_per_task_plain(uint32_t nStreams, int nCU, int tileWaves) 
 void plan_size(const PlanIn &in, BatchPlan &p) {
     typedef unsigned long long ull;
     const bool slicedPath = p.path == PVOL_PATH_SLICED;
-    // LDS plans of the kernels (pvol_march.hip)
-    p.ldsPar = (size_t)in.candCap * 8 + 256 * 4 + 1024 * 4; p.ldsResolve = 624 * 4 + (size_t)in.maxSteps * 4;
+    // LDS plans of the kernels (march_lds, pvol_march.hip)
+    p.ldsPar = (size_t)in.candCap * 8 + PVOL_MARCH_LDS_FIXED; p.ldsResolve = 624 * 4 + (size_t)in.maxSteps * 4;
     p.ldsSeq = p.ldsResolve + p.ldsPar; p.ldsGroup = pvol_group_lds_bytes(in.candCap);
     if (p.tile == PVOL_TILE_FUSED) { p.ldsTile = pvol_tile_lds_bytes(in.maxSteps, in.spp, true, in.nTris, false); p.tileWavesPerTask = 1; }
     else if (p.tile != PVOL_TILE_NONE) { p.ldsTile = pvol_tile_lds_bytes(0, in.spp, false, in.nTris, in.distant != 0); p.tileWavesPerTask = tile_waves_per_task(in); }

@@ -528,32 +528,10 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                 bool lit = false, distant = true;
                 const int ln = REPLAY ? (act ? (int)(rec.stepByte[j] & 7u) : 0) : 0;   // the light this step samples (photonvolume.cpp:181-183)
                 if (inP && !blackS1 && nLights > 0) {
-                    const DevLight &light = S.lights[ln];
-                    RayD vis;
-                    V3 wo;
-                    distant = light.kind == PVOL_LIGHT_DISTANT;
-                    if (distant) {
-                        wo = v3(light.dir[0], light.dir[1], light.dir[2]);
-                        vis.o = p; vis.d = wo; vis.mint = 0.f; vis.maxt = INFINITY;
-                    } else {
-                        V3 lp = v3(light.pos[0], light.pos[1], light.pos[2]);
-                        wo = normalize(lp - p);
-                        float dist = len(p - lp);
-                        vis.o = p; vis.d = vdiv(lp - p, dist); vis.mint = 0.f; vis.maxt = dist * (1.f - 0.f);
-                        d2Reg = len_sq(lp - p);
-                        if (light.kind == PVOL_LIGHT_SPOT) {
-                            V3 wl = normalize(v3(light.w2l[0] * -wo.x + light.w2l[1] * -wo.y + light.w2l[2] * -wo.z,
-                                                 light.w2l[4] * -wo.x + light.w2l[5] * -wo.y + light.w2l[6] * -wo.z,
-                                                 light.w2l[8] * -wo.x + light.w2l[9] * -wo.y + light.w2l[10] * -wo.z));
-                            float costheta = wl.z;
-                            if (costheta < light.cosTotalWidth) fallReg = 0.f;
-                            else if (costheta > light.cosFalloffStart) fallReg = 1.f;
-                            else {
-                                float delta = (costheta - light.cosTotalWidth) / (light.cosFalloffStart - light.cosTotalWidth);
-                                fallReg = delta * delta * delta * delta;
-                            }
-                        }
-                    }
+                    const LightSample ls = light_sample(S.lights[ln], p, 0.f);
+                    const RayD vis = ls.vis;
+                    const V3 wo = ls.wo;
+                    distant = ls.distant; d2Reg = ls.d2; fallReg = ls.fall;
                     const bool black = (fallReg == 0.f) || ((lightBlackMask >> ln) & 1u);
                     if (!black && !(rowsOK ? tri_rows_occluded(L.trows, S.nTris, vis.o, vis.d, vis.mint, vis.maxt) : lane_occluded(S, vis))) {
                         lit = true;

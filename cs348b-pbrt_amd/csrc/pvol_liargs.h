@@ -3,6 +3,26 @@
 #ifndef PVOL_LIARGS_H
 #define PVOL_LIARGS_H
 #include "pvol_dev.h"
+// The fixed tail of the marching kernels' LDS, prevRk | paint (march_lds, pvol_march.hip), sized here for the kernels and for plan_size
+#define PREV_N 256     // march steps for which the previous ray's k-th distance^2 is remembered
+#define PAINT_ROW 16   // rows up to this many photons go through the painted index list
+#define PAINT_CAP (64 * PAINT_ROW)
+constexpr size_t PVOL_MARCH_LDS_FIXED = PREV_N * 4 + PAINT_CAP * 4;
+static_assert(PVOL_MARCH_LDS_FIXED == 256 * 4 + 1024 * 4, "the LDS byte counts of the plan are pinned (tests/test_launch_plan.py)");
+
+// One launch of a kernel template by the batch: NREG = candidate registers per lane in select_k (4 covers nused <= 64, 12 covers
+// nused <= 576), STATS = the work counters.  `kernel` is written with the names NREG (and STATS) in its template arguments and is
+// instantiated for exactly the values the ladder can choose.
+#define PVOL_LAUNCH_NREG(candCap, kernel, grid, block, ldsBytes, stream, ...)                                                      \
+    do {                                                                                                                           \
+        if ((candCap) <= 4 * 64) { constexpr int NREG = 4; hipLaunchKernelGGL(kernel, grid, block, ldsBytes, stream, __VA_ARGS__); } \
+        else { constexpr int NREG = 12; hipLaunchKernelGGL(kernel, grid, block, ldsBytes, stream, __VA_ARGS__); }                   \
+    } while (0)
+#define PVOL_LAUNCH_STATS_NREG(stats, candCap, kernel, grid, block, ldsBytes, stream, ...)                                         \
+    do {                                                                                                                           \
+        if (stats) { constexpr bool STATS = true; PVOL_LAUNCH_NREG(candCap, kernel, grid, block, ldsBytes, stream, __VA_ARGS__); } \
+        else { constexpr bool STATS = false; PVOL_LAUNCH_NREG(candCap, kernel, grid, block, ldsBytes, stream, __VA_ARGS__); }      \
+    } while (0)
 struct LiArgs {
     const DevScene *scene;
     const pvol_ray *rays;

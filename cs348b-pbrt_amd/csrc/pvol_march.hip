@@ -26,14 +26,13 @@
 // hits) is taken on the fp32 values the CPU reference computes.
 #include "pvol_math.h"
 
+#include "pvol_liargs.h"   // PREV_N, PAINT_ROW, PAINT_CAP, the launch ladder
+
 #define NCH 4        // chunks of 64 candidate loads in flight
-#define PREV_N 256   // march steps for which the previous ray's k-th distance^2 is remembered
 #define CHUNK_RAYS 64
 #ifndef PVOL_GUESS_SCALE
 #define PVOL_GUESS_SCALE 1.3f   // first search radius^2 = this x the neighbouring k-th distance^2
 #endif
-#define PAINT_ROW 16   // rows up to this many photons go through the painted index list
-#define PAINT_CAP (64 * PAINT_ROW)
 #ifndef PVOL_WPE
 #ifndef PVOL_WPE_BIG
 #define PVOL_WPE_BIG 2   // k > 64 instantiations (NREG 12): 2 waves/SIMD measured best on a C3-like load (0.129 vs 0.124 at 1, 0.079 Msamples/s at 3)
@@ -42,6 +41,7 @@
 #endif
 
 #include "pvol_rng_dev.h"
+#include "pvol_light_dev.h"
 #include "pvol_gridrows_dev.h"
 
 // ------------------------------------------------------------------------------------------ k-NN gather
@@ -397,6 +397,23 @@ struct MarchLds {
     float *lightNum;   // SEQ with > 1 light: LDShuffleScrambled1D output
     float *prevRk;     // k-th distance^2 per march step of the previous ray handled by this wave
 };
+// The marching kernels' LDS, in bytes and in this order:
+//   [MT19937 state MT_N*4] | cand d2 cap*4 | cand idx cap*4 | [lightNum maxSteps*4] | prevRk PREV_N*4 | paint PAINT_CAP*4
+// The bracketed parts belong to a kernel whose wave owns a stream: mtWords = MT_N and lightNumSteps = S.maxSteps there, both 0 in the
+// ray-parallel kernels (which never read lightNum).  The host's mirror is plan_size (pvol_api.hip): ldsPar = the parts without brackets,
+// ldsResolve = the bracketed ones alone (march_lds_none: a pre-pass gathers nothing), ldsSeq = both.
+__device__ __forceinline__ MarchLds march_lds(unsigned char *lds, int candCap, int mtWords, int lightNumSteps, int lane) {
+    MarchLds M;
+    M.G.cap = candCap;
+    M.G.cd = reinterpret_cast<float *>(lds + mtWords * 4);
+    M.G.ci = reinterpret_cast<uint32_t *>(lds + mtWords * 4 + (size_t)M.G.cap * 4);
+    M.lightNum = reinterpret_cast<float *>(lds + mtWords * 4 + (size_t)M.G.cap * 8);
+    M.prevRk = M.lightNum + lightNumSteps;
+    M.G.paint = reinterpret_cast<uint32_t *>(M.prevRk + PREV_N);
+    for (int i = lane; i < PREV_N; i += LANES) M.prevRk[i] = 0.f;
+    __syncthreads();
+    return M;
+}
 
 // One call of PhotonVolumeIntegrator::Li (or Transmittance).  Returns false only in !SEQ mode when the ray
 // needs a drawn VALUE (Russian roulette): the caller must redo the batch sequentially.
@@ -407,6 +424,14 @@ struct MarchLds {
 //                 outcome, tau() offsets) and skips gather and radiance: the cheap sequential pre-pass
 //   MODE_REPLAY   no RNG: reads the records, so rays are independent and run one wave each
 #define MODE_SEQ 0
+// The all-null form of a pre-pass, which gathers nothing: only lightNum, behind the stream's MT19937 state
+__device__ __forceinline__ MarchLds march_lds_none(float *lightNum) {
+    MarchLds M;
+    M.G.cap = 0; M.G.cd = 0; M.G.ci = 0; M.G.paint = 0;
+    M.lightNum = lightNum;
+    M.prevRk = 0;
+    return M;
+}
 #define MODE_PAR 1
 #define MODE_RESOLVE 2
 #define MODE_REPLAY 3
@@ -585,7 +610,8 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
                 if (MODE == MODE_REPLAY) ln = (int)(recByte & 7u);
                 recByte |= (unsigned int)ln;
                 const DevLight &light = S.lights[ln];
-                // Light::Sample_L(p, 0, ...): distant.cpp:48-55, point.cpp:50-57, spot.cpp:50-57
+                // Light::Sample_L(p, 0, ...): distant.cpp:48-55, point.cpp:50-57, spot.cpp:50-57.  light_sample's text but for the cone:
+                // calling it here costs li_seq_kernel and li_resolve_kernel spills
                 V3 wo;
                 RayD vis;
                 f4 L = ld4(light.intensity, q);
@@ -600,16 +626,7 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
                     float d2 = len_sq(lp - p);
                     if (light.kind == PVOL_LIGHT_SPOT) {
                         // SpotLight::Falloff(-wi), spot.cpp:60-69
-                        V3 wl = normalize(v3(light.w2l[0] * -wo.x + light.w2l[1] * -wo.y + light.w2l[2] * -wo.z,
-                                             light.w2l[4] * -wo.x + light.w2l[5] * -wo.y + light.w2l[6] * -wo.z,
-                                             light.w2l[8] * -wo.x + light.w2l[9] * -wo.y + light.w2l[10] * -wo.z));
-                        float costheta = wl.z, fall;
-                        if (costheta < light.cosTotalWidth) fall = 0.f;
-                        else if (costheta > light.cosFalloffStart) fall = 1.f;
-                        else {
-                            float delta = (costheta - light.cosTotalWidth) / (light.cosFalloffStart - light.cosTotalWidth);
-                            fall = delta * delta * delta * delta;
-                        }
+                        const float fall = spot_falloff(spot_costheta<4>(light.w2l, -wo), light.cosTotalWidth, light.cosFalloffStart);
                         L = L * fall / d2;
                     } else {
                         L = L / d2;
@@ -775,30 +792,9 @@ __device__ int march_ray_blocked(const DevScene &S, const LiArgs &A, const pvol_
             V3 wo = v3(0.f, 0.f, 0.f);
             bool lit = false;
             if (on && inP && !blackS1 && nLights > 0) {   // dens == 1 inside, 0 outside: sigma_s is black outside
-                const DevLight &light = S.lights[ln];
-                RayD vis;
-                if (light.kind == PVOL_LIGHT_DISTANT) {   // distant.cpp:48-55
-                    wo = v3(light.dir[0], light.dir[1], light.dir[2]);
-                    vis.o = p; vis.d = wo; vis.mint = 0.f; vis.maxt = INFINITY;
-                } else {                                  // point.cpp:50-57, spot.cpp:50-57
-                    V3 lp = v3(light.pos[0], light.pos[1], light.pos[2]);
-                    wo = normalize(lp - p);
-                    float dist = len(p - lp);
-                    vis.o = p; vis.d = vdiv(lp - p, dist); vis.mint = 0.f; vis.maxt = dist * (1.f - 0.f);
-                    d2Reg = len_sq(lp - p);
-                    if (light.kind == PVOL_LIGHT_SPOT) {  // SpotLight::Falloff(-wi), spot.cpp:60-69
-                        V3 wl = normalize(v3(light.w2l[0] * -wo.x + light.w2l[1] * -wo.y + light.w2l[2] * -wo.z,
-                                             light.w2l[4] * -wo.x + light.w2l[5] * -wo.y + light.w2l[6] * -wo.z,
-                                             light.w2l[8] * -wo.x + light.w2l[9] * -wo.y + light.w2l[10] * -wo.z));
-                        float costheta = wl.z;
-                        if (costheta < light.cosTotalWidth) fallReg = 0.f;
-                        else if (costheta > light.cosFalloffStart) fallReg = 1.f;
-                        else {
-                            float delta = (costheta - light.cosTotalWidth) / (light.cosFalloffStart - light.cosTotalWidth);
-                            fallReg = delta * delta * delta * delta;
-                        }
-                    }
-                }
+                const LightSample ls = light_sample(S.lights[ln], p, 0.f);
+                const RayD vis = ls.vis;
+                wo = ls.wo; d2Reg = ls.d2; fallReg = ls.fall;
                 // L.IsBlack(): I * fall / d2 has no non-zero bin
                 const bool black = (fallReg == 0.f) || ((lightBlackMask >> ln) & 1u);
                 if (!black && !lane_occluded(S, vis)) {
@@ -908,7 +904,6 @@ __device__ __forceinline__ void flush_counters(DevCounters *c, const WaveCounter
     }
 }
 
-// LDS plan (bytes): [MT 2496 (SEQ)] | cand d2 cap*4 | cand idx cap*4 | lightNum maxSteps*4 (SEQ) | prevRk PREV_N*4 | paint PAINT_CAP*4
 template <bool STATS, int NREG>
 __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void li_seq_kernel(LiArgs A) {
     extern __shared__ __align__(16) unsigned char lds[];
@@ -917,18 +912,9 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
     const uint32_t sidx = blockIdx.x;
     if (sidx >= A.nStreams) return;
     if (A.gated && *A.needSeq == 0u) return;
-    uint32_t *mt = reinterpret_cast<uint32_t *>(lds);
-    MarchLds M;
-    M.G.cap = S.candCap;
-    M.G.cd = reinterpret_cast<float *>(lds + MT_N * 4);
-    M.G.ci = reinterpret_cast<uint32_t *>(lds + MT_N * 4 + (size_t)M.G.cap * 4);
-    M.lightNum = reinterpret_cast<float *>(lds + MT_N * 4 + (size_t)M.G.cap * 8);
-    M.prevRk = M.lightNum + S.maxSteps;
-    M.G.paint = reinterpret_cast<uint32_t *>(M.prevRk + PREV_N);
-    for (int i = lane; i < PREV_N; i += LANES) M.prevRk[i] = 0.f;
-    __syncthreads();
-
+    MarchLds M = march_lds(lds, S.candCap, MT_N, S.maxSteps, lane);
     pvol_stream st = A.streams[sidx];
+    uint32_t *mt = reinterpret_cast<uint32_t *>(lds);
     Rng rng;
     rng.mt = mt;
     rng.draws = 0;
@@ -988,15 +974,7 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
     extern __shared__ __align__(16) unsigned char lds[];
     const DevScene &S = *A.scene;
     const int lane = threadIdx.x;
-    MarchLds M;
-    M.G.cap = S.candCap;
-    M.G.cd = reinterpret_cast<float *>(lds);
-    M.G.ci = reinterpret_cast<uint32_t *>(lds + (size_t)M.G.cap * 4);
-    M.lightNum = 0;
-    M.prevRk = reinterpret_cast<float *>(lds + (size_t)M.G.cap * 8);
-    M.G.paint = reinterpret_cast<uint32_t *>(M.prevRk + PREV_N);
-    for (int i = lane; i < PREV_N; i += LANES) M.prevRk[i] = 0.f;
-    __syncthreads();
+    MarchLds M = march_lds(lds, S.candCap, 0, 0, lane);
     Rng rng;
     rng.mt = 0;
     rng.mti = 0;
@@ -1051,10 +1029,7 @@ __global__ __launch_bounds__(LANES, PVOL_WPE) void li_resolve_kernel(LiArgs A) {
     const uint32_t sidx = blockIdx.x;
     if (sidx >= A.nStreams) return;
     uint32_t *mt = reinterpret_cast<uint32_t *>(lds);
-    MarchLds M;
-    M.G.cap = 0; M.G.cd = 0; M.G.ci = 0; M.G.paint = 0;
-    M.lightNum = reinterpret_cast<float *>(lds + MT_N * 4);
-    M.prevRk = 0;
+    MarchLds M = march_lds_none(reinterpret_cast<float *>(lds + MT_N * 4));
     pvol_stream st = A.streams[sidx];
     const uint32_t begin = A.sliceK * A.sliceM;
     if (begin >= st.n_rays && !(A.sliceK == 0)) return;
@@ -1105,15 +1080,7 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
     const DevScene &S = *A.scene;
     const int lane = threadIdx.x;
     if (A.gated && *A.needSeq == 0u) return;   // backup of li_group_kernel's replay form: runs only if its hand-over list overflowed
-    MarchLds M;
-    M.G.cap = S.candCap;
-    M.G.cd = reinterpret_cast<float *>(lds);
-    M.G.ci = reinterpret_cast<uint32_t *>(lds + (size_t)M.G.cap * 4);
-    M.lightNum = 0;
-    M.prevRk = reinterpret_cast<float *>(lds + (size_t)M.G.cap * 8);
-    M.G.paint = reinterpret_cast<uint32_t *>(M.prevRk + PREV_N);
-    for (int i = lane; i < PREV_N; i += LANES) M.prevRk[i] = 0.f;
-    __syncthreads();
+    MarchLds M = march_lds(lds, S.candCap, 0, 0, lane);
     Rng rng;
     rng.mt = 0;
     rng.mti = 0;
@@ -1189,7 +1156,7 @@ __device__ int geo_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr, R
         if (on && dens != 0.f && !blackS1 && S.nLights > 0) {   // sigma_s * dens is black iff dens == 0 or sigma_s is
             mask = 0x80u;
             for (int ln = 0; ln < S.nLights; ++ln) {
-                const DevLight &light = S.lights[ln];
+                const DevLight &light = S.lights[ln];   // light_sample's text but for the cone: calling it costs the FUSED tile_kernel spills
                 RayD vis;
                 float fall = 1.f;
                 if (light.kind == PVOL_LIGHT_DISTANT) {
@@ -1200,16 +1167,7 @@ __device__ int geo_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr, R
                     float dist = len(p - lp);
                     vis.o = p; vis.d = vdiv(lp - p, dist); vis.mint = 0.f; vis.maxt = dist * (1.f - 0.f);
                     if (light.kind == PVOL_LIGHT_SPOT) {
-                        V3 wl = normalize(v3(light.w2l[0] * -wo.x + light.w2l[1] * -wo.y + light.w2l[2] * -wo.z,
-                                             light.w2l[4] * -wo.x + light.w2l[5] * -wo.y + light.w2l[6] * -wo.z,
-                                             light.w2l[8] * -wo.x + light.w2l[9] * -wo.y + light.w2l[10] * -wo.z));
-                        float costheta = wl.z;
-                        if (costheta < light.cosTotalWidth) fall = 0.f;
-                        else if (costheta > light.cosFalloffStart) fall = 1.f;
-                        else {
-                            float delta = (costheta - light.cosTotalWidth) / (light.cosFalloffStart - light.cosTotalWidth);
-                            fall = delta * delta * delta * delta;
-                        }
+                        fall = spot_falloff(spot_costheta<4>(light.w2l, -wo), light.cosTotalWidth, light.cosFalloffStart);
                     }
                 }
                 const bool black = (fall == 0.f) || ((lightBlackMask >> ln) & 1u);
@@ -1370,28 +1328,13 @@ __global__ __launch_bounds__(LANES) void li_resolve_lite_kernel(LiArgs A) {
 }
 
 extern "C" hipError_t pvol_launch_li_seq(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, hipStream_t stream) {
-    dim3 grid(args->nStreams), block(LANES);
-    // NREG = candidate registers per lane in select_k: 4 covers nused <= 64, 12 covers nused <= 576
-    if (candCap <= 4 * LANES) {
-        if (stats) hipLaunchKernelGGL((li_seq_kernel<true, 4>), grid, block, ldsBytes, stream, *args);
-        else hipLaunchKernelGGL((li_seq_kernel<false, 4>), grid, block, ldsBytes, stream, *args);
-    } else {
-        if (stats) hipLaunchKernelGGL((li_seq_kernel<true, 12>), grid, block, ldsBytes, stream, *args);
-        else hipLaunchKernelGGL((li_seq_kernel<false, 12>), grid, block, ldsBytes, stream, *args);
-    }
+    PVOL_LAUNCH_STATS_NREG(stats, candCap, (li_seq_kernel<STATS, NREG>), dim3(args->nStreams), dim3(LANES), ldsBytes, stream, *args);
     return hipGetLastError();
 }
 
 extern "C" hipError_t pvol_launch_li_par(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, uint32_t nWaves, hipStream_t stream) {
     hipLaunchKernelGGL(stream_begin_kernel, dim3((args->nStreams + 255) / 256), dim3(256), 0, stream, args->streams, args->nStreams);
-    dim3 grid(nWaves), block(LANES);
-    if (candCap <= 4 * LANES) {
-        if (stats) hipLaunchKernelGGL((li_par_kernel<true, 4>), grid, block, ldsBytes, stream, *args);
-        else hipLaunchKernelGGL((li_par_kernel<false, 4>), grid, block, ldsBytes, stream, *args);
-    } else {
-        if (stats) hipLaunchKernelGGL((li_par_kernel<true, 12>), grid, block, ldsBytes, stream, *args);
-        else hipLaunchKernelGGL((li_par_kernel<false, 12>), grid, block, ldsBytes, stream, *args);
-    }
+    PVOL_LAUNCH_STATS_NREG(stats, candCap, (li_par_kernel<STATS, NREG>), dim3(nWaves), dim3(LANES), ldsBytes, stream, *args);
     return hipGetLastError();
 }
 
@@ -1409,23 +1352,14 @@ extern "C" hipError_t pvol_launch_li_slice(const LiArgs *args, size_t ldsResolve
         hipLaunchKernelGGL((li_resolve_lite_kernel<4>), dim3(args->nStreams), block, ldsResolve, stream, *args);
         resolve = false;
     }
-    if (resolve) {
-        if (candCap <= 4 * LANES) hipLaunchKernelGGL((li_resolve_kernel<false, 4>), dim3(args->nStreams), block, ldsResolve, stream, *args);
-        else hipLaunchKernelGGL((li_resolve_kernel<false, 12>), dim3(args->nStreams), block, ldsResolve, stream, *args);
-    }
+    if (resolve) PVOL_LAUNCH_NREG(candCap, (li_resolve_kernel<false, NREG>), dim3(args->nStreams), block, ldsResolve, stream, *args);
     LiArgs a2 = *args;
     if (groupForm) {
         hipError_t e = pvol_launch_li_group(args, ldsGroup, candCap, false, nGroupWaves, nFixWaves, groupForm, stream);
         if (e != hipSuccess) return e;
         a2.gated = 1;
     }
-    if (candCap <= 4 * LANES) {
-        if (stats) hipLaunchKernelGGL((li_replay_kernel<true, 4>), dim3(nWaves), block, ldsReplay, stream, a2);
-        else hipLaunchKernelGGL((li_replay_kernel<false, 4>), dim3(nWaves), block, ldsReplay, stream, a2);
-    } else {
-        if (stats) hipLaunchKernelGGL((li_replay_kernel<true, 12>), dim3(nWaves), block, ldsReplay, stream, a2);
-        else hipLaunchKernelGGL((li_replay_kernel<false, 12>), dim3(nWaves), block, ldsReplay, stream, a2);
-    }
+    PVOL_LAUNCH_STATS_NREG(stats, candCap, (li_replay_kernel<STATS, NREG>), dim3(nWaves), block, ldsReplay, stream, a2);
     return hipGetLastError();
 }
 
@@ -1433,8 +1367,7 @@ extern "C" hipError_t pvol_launch_li_slice(const LiArgs *args, size_t ldsResolve
 extern "C" hipError_t pvol_launch_li_replay(const LiArgs *args, size_t ldsReplay, int candCap, uint32_t nWaves, hipStream_t stream) {
     LiArgs a = *args;
     a.gated = 0;
-    if (candCap <= 4 * LANES) hipLaunchKernelGGL((li_replay_kernel<false, 4>), dim3(nWaves), dim3(LANES), ldsReplay, stream, a);
-    else hipLaunchKernelGGL((li_replay_kernel<false, 12>), dim3(nWaves), dim3(LANES), ldsReplay, stream, a);
+    PVOL_LAUNCH_NREG(candCap, (li_replay_kernel<false, NREG>), dim3(nWaves), dim3(LANES), ldsReplay, stream, a);
     return hipGetLastError();
 }
 

@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "pvol_rng_dev.h"
+#include "pvol_light_dev.h"
 #include "pvol_shoot_args.h"
 #include "pvol_shading_dev.h"
 
@@ -284,14 +285,7 @@ __device__ __forceinline__ float light_emit(const DevScene &S, const DevShootSce
         *o = v3(l.pos[0], l.pos[1], l.pos[2]);
         *d = v3(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z);
         *pdf = 1.f / (2.f * K_PI * (1.f - l.cosTotalWidth));
-        // Falloff(ray->d), spot.cpp:60-69
-        V3 wl = normalize(v3(l.w2l[0] * d->x + l.w2l[1] * d->y + l.w2l[2] * d->z, l.w2l[4] * d->x + l.w2l[5] * d->y + l.w2l[6] * d->z,
-                             l.w2l[8] * d->x + l.w2l[9] * d->y + l.w2l[10] * d->z));
-        float ct = wl.z;
-        if (ct < l.cosTotalWidth) return 0.f;
-        if (ct > l.cosFalloffStart) return 1.f;
-        float delta = (ct - l.cosTotalWidth) / (l.cosFalloffStart - l.cosTotalWidth);
-        return delta * delta * delta * delta;
+        return spot_falloff(spot_costheta<4>(l.w2l, *d), l.cosTotalWidth, l.cosFalloffStart);   // Falloff(ray->d)
     }
     if (l.kind == PVOL_LIGHT_POINT) {
         float z = 1.f - 2.f * u0;   // UniformSampleSphere, montecarlo.cpp:283-290

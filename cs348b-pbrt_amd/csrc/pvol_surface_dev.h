@@ -17,7 +17,8 @@
                        // scene's surface integrator on: 2048 -> 1 509 ms, 1024 -> 1 104 ms, 512 -> 3 580 ms; 640 with SRF_AIM 1.35: 1 278 ms: occupancy (LDS) against overflows
 
 // One delta light seen from a surface point: Light::Sample_L(p, eps, ...) (spot.cpp:50-57, point.cpp:50-57, distant.cpp:48-55),
-// the shadow ray of its VisibilityTester (core/light.h:85-101) and whether EstimateDirect would take the sample.
+// the shadow ray of its VisibilityTester (core/light.h:85-101) and whether EstimateDirect would take the sample.  light_sample's text
+// (pvol_light_dev.h) with mint = eps, kept here: the helper, and its cone alone, cost the tile and rays pre-passes registers.
 struct SurfLight { bool take; V3 wi; float scale; RayD vis; };   // radiance = intensity * scale
 __device__ __forceinline__ SurfLight surf_light(const DevScene &S, int ln, V3 p, float eps, V3 ng, V3 wo, bool lambert, unsigned blackMask) {
     SurfLight r;

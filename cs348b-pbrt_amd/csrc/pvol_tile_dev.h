@@ -214,7 +214,7 @@ __device__ uint32_t tile_count_draws(const DevScene &S, const CountConsts &C, co
             const V3 pv = xform_point(C.w2v, p);
             // sigma_s(p) black: outside a homogeneous extent, or zero density of a VolumeGrid (volumegrid.cpp:39-57)
             if (is_region(C.volKind) ? region_density(S, pv) == 0.f : !box_inside(C.lo, C.hi, pv)) continue;
-            RayD vis;
+            RayD vis;   // light_sample's text over the register copy of light 0: the helper grows tile_kernel<false, 4, true>
             if (C.lightKind == PVOL_LIGHT_DISTANT) {
                 vis.o = p; vis.d = v3(C.ldir[0], C.ldir[1], C.ldir[2]); vis.mint = 0.f; vis.maxt = INFINITY;
             } else {
@@ -362,10 +362,7 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
     const uint32_t sidx = blockIdx.x;
     if (sidx >= A.nStreams) return;
     uint32_t *mt = reinterpret_cast<uint32_t *>(lds);
-    MarchLds M;
-    M.G.cap = 0; M.G.cd = 0; M.G.ci = 0; M.G.paint = 0;
-    M.lightNum = reinterpret_cast<float *>(lds + MT_N * 4);
-    M.prevRk = 0;
+    MarchLds M = march_lds_none(reinterpret_cast<float *>(lds + MT_N * 4));
     TileLds L;
     L.image = M.lightNum + (FUSED ? ((S.maxSteps + 1) & ~1) : 0);   // 8-byte aligned: the image samples are swapped as float2
     L.time = L.image + 2 * T.spp;
@@ -674,8 +671,7 @@ static hipError_t launch_tile_t(const LiArgs *args, const TileArgs *tile, bool f
     *form = fused ? "tile_kernel<fused>" : "tile_kernel<count>";
     if (!fused) hipLaunchKernelGGL((tile_kernel<false, 4, SPEC, PLAIN>), grid, block, ldsBytes, stream, *args, *tile);
     else if constexpr (PLAIN) return hipErrorInvalidValue;   // PLAIN is a form of COUNT mode
-    else if (candCap <= 4 * LANES) hipLaunchKernelGGL((tile_kernel<true, 4, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
-    else hipLaunchKernelGGL((tile_kernel<true, 12, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
+    else PVOL_LAUNCH_NREG(candCap, (tile_kernel<true, NREG, SPEC>), grid, block, ldsBytes, stream, *args, *tile);
     return hipGetLastError();
 }
 // wavesPerTask (COUNT mode, whole batch in one launch): 1 = the one-wave kernel; 2 / 4 / 8 / 16 = tile_mw_kernel, chosen by the host when

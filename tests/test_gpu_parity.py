@@ -46,6 +46,54 @@ def test_li_matches_reference_records(pvol, name):
     pv.close()
 
 
+def test_li_replay_kernel_matches_reference_records_with_spot_and_point_light(pvol, monkeypatch):
+    """pinkfloyd's spot + point light through march_ray_blocked<MODE_REPLAY> (light_sample, pvol_light_dev.h): with the bucket kernel
+    off the sliced path's heavy pass is li_replay_kernel, one wave per ray.  Same records, same exactness as the test above."""
+    monkeypatch.setenv("PVOL_NO_GROUP", "1")   # read when the context is created
+    s, p, rays, streams, c = load_li_case("pf_k50")
+    assert [int(k) for k in s["lights.kind"]] == [1, 0]   # PVOL_LIGHT_SPOT, PVOL_LIGHT_POINT
+    pv = _ctx(pvol, s, p, load_photons("pf"))
+    out, draws = pv.li(rays, streams)
+    assert pv.march_kernel_name() == "li_replay_kernel"
+    Lr, Tr = c["ref.Lv"].reshape(-1, 30), c["ref.T"].reshape(-1, 30)
+    floor = 1e-6 * max(1e-30, float(np.abs(Lr).max()))
+    assert rel_l2(out[:, :30], Lr, floor=floor).max() <= TOL
+    assert rel_l2(out[:, 30:], Tr).max() <= TOL
+    assert (draws == c["ref.draws"]).all()
+    assert (streams["end_draw"] == c["ref.streams.end"]).all()
+    pv.close()
+
+
+@pytest.mark.parametrize("keep,kind", [(0, "spot"), (1, "point")])
+def test_li_par_kernel_matches_oracle_with_one_non_distant_light(pvol, orc, monkeypatch, keep, kind):
+    """march_ray_blocked<MODE_PAR> with a spot or a point light: pinkfloyd with one of its two lights kept is a one-light homogeneous
+    scene, the ray-parallel path, and with the bucket kernel off that is li_par_kernel.  Against the oracle as the other oracle
+    comparisons here (TOL on radiance and transmittance, draw counts and stream ends exact)."""
+    monkeypatch.setenv("PVOL_NO_GROUP", "1")
+    s, p, rays, streams, c = load_li_case("pf_k50")
+    n_lights = len(s["lights.kind"])
+    assert n_lights == 2 and [int(k) for k in s["lights.kind"]] == [1, 0]   # PVOL_LIGHT_SPOT, PVOL_LIGHT_POINT
+    s = dict(s)
+    for k in ("lights.kind", "lights.pos", "lights.dir", "lights.l2w", "lights.w2l", "lights.intensity", "lights.cos"):
+        per = len(s[k]) // n_lights
+        s[k] = s[k][keep * per:(keep + 1) * per].copy()
+    ph = load_photons("pf")
+    pv = _ctx(pvol, s, p, ph)
+    st = streams.copy()
+    out, draws = pv.li(rays, st)
+    assert pv.march_kernel_name() == "li_par_kernel"
+    o = orc.Oracle(abi.SceneHolder(s), p)
+    o.set_photons(*ph)
+    rst = streams.copy()
+    ref, rdraws = o.li_batch(rays, rst)
+    floor = 1e-6 * max(1e-30, float(np.abs(ref[:, :30]).max()))
+    assert rel_l2(out[:, :30], ref[:, :30], floor=floor).max() <= TOL
+    assert rel_l2(out[:, 30:], ref[:, 30:]).max() <= TOL
+    assert (draws == rdraws).all()
+    assert (st["end_draw"] == rst["end_draw"]).all()
+    pv.close()
+
+
 @pytest.mark.parametrize("name", sorted(TRANS_CASES))
 def test_transmittance_matches_reference_records(pvol, name):
     s, p, rays, streams, c = load_li_case(name)
