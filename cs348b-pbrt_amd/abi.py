@@ -309,6 +309,27 @@ RADIANCE_CALLER_SCRATCH = 248        # ... and per caller ray
 RADIANCE_WANT = ("surf_xyz", "t_hit", "draws", "surf_draws", "n_segments")   # the optional outputs, by their field names
 
 
+class GatherParams(C.Structure):   # pvol_gather_params: the final gather's arguments of pvol_radiance_gather_batch* (u_*: host or device pointers)
+    _fields_ = [("max_dist", C.c_float), ("n_samples", C.c_int32), ("cos_gather_angle", C.c_float), ("u_bsdf", C.c_void_p), ("u_photon", C.c_void_p)]
+
+
+class RadianceGatherOut(C.Structure):   # pvol_radiance_gather_out: RadianceOut's members in their order, then gather_draws
+    _fields_ = RadianceOut._fields_ + [("gather_draws", C.c_void_p)]
+
+
+class RadianceGatherCheck(C.Structure):   # the arguments pvol_radiance_gather_check judges (csrc/pvol_host.h)
+    _fields_ = [("rays", C.c_void_p), ("streams", C.c_void_p), ("n_rays", C.c_uint32), ("n_streams", C.c_uint32), ("output_kind", C.c_int32),
+                ("out", C.POINTER(RadianceGatherOut)), ("gather", C.POINTER(GatherParams))]
+
+
+RADIANCE_GATHER_WANT = RADIANCE_WANT + ("gather_draws",)
+
+
+def radiance_gather_scratch(n_samples):
+    """PVOL_RADIANCE_GATHER_SCRATCH: bytes the gather adds per expanded ray of a slice (csrc/pvol_rays_plan.h)."""
+    return 308 + 24 * int(n_samples)
+
+
 def make_camera(raster_to_camera, camera_to_world, shutter_open=0.0, shutter_close=1.0, lens_radius=0.0, focal_distance=1e30):
     c = Camera()
     for i, v in enumerate(np.asarray(raster_to_camera, np.float32).reshape(16)):

@@ -211,6 +211,9 @@ enum {
     // pvol_radiance_batch* (pvol_rays.hip), one slice: the expanded rays, their SegInfo, 60-float rows and draw counts; per caller ray the block
     // sizes and their scan (2 x (n + 1) words) and the primaries' stashed rows; the slice's stream table; the scan's own scratch
     PVOL_BUF_RR_RAYS, PVOL_BUF_RR_INFO, PVOL_BUF_RR_ROWS, PVOL_BUF_RR_DRAWS, PVOL_BUF_RR_COUNT, PVOL_BUF_RR_STASH, PVOL_BUF_RR_STREAMS, PVOL_BUF_RR_TEMP,
+    // pvol_radiance_gather_batch* (pvol_rays.hip, pvol_rays_gather.hip), per expanded ray of a slice: its final-gather query (46 floats),
+    // its copy of the owner's sample rows (2 x n_samples x 3 floats), Lg (30 floats) and the gather's draws (one word)
+    PVOL_BUF_RG_QUERY, PVOL_BUF_RG_U, PVOL_BUF_RG_OUT,
     PVOL_N_BUFS
 };
 extern "C" bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream);
@@ -520,6 +523,37 @@ int pvol_radiance_slice_streams(const pvol_stream *streams, uint32_t nStreams, u
 uint32_t pvol_radiance_max_segments(int specOn, int32_t maxSpecularDepth);
 // lowers (or, with 0, restores) the scratch bound of this context's pvol_radiance_batch* calls, for the tests
 int pvol_radiance_set_scratch_bound(pvol_ctx *c, uint64_t bytes);
+// every status of pvol_radiance_gather_batch* in its one order (include/pvol.h), reachable without a device for the tests
+// (pvol_rays.hip); no HIP call.  args: the call's pointers and numbers; volKind: the scene's medium; surfOn: a surface integrator is
+// described and on; indirectN: photons of the indirect map it describes; haveGather: a gather map is built; haveRad / radN: a radiance
+// result exists / its radiance photons
+struct RadianceGatherCheck {
+    const void *rays, *streams; uint32_t nRays, nStreams; int32_t outputKind; const pvol_radiance_gather_out *out; const pvol_gather_params *gather;
+};
+int pvol_radiance_gather_check(int haveCtx, const RadianceGatherCheck *args, int haveScene, int volKind, int surfOn, uint32_t indirectN, int haveGather,
+                               int haveRad, uint32_t radN);
+// caller rays per slice of pvol_radiance_gather_batch* when nobody spawns: pvol_radiance_slice(0, bound) with the gather's
+// PVOL_RADIANCE_GATHER_SCRATCH(nSamples) bytes per expanded ray on top; the entry point counts and cuts as pvol_radiance_batch* does
+uint32_t pvol_radiance_gather_slice(int32_t nSamples, uint64_t bound);
+// the kernels of pvol_radiance_gather_batch* (pvol_rays_gather.hip), over the `total` expanded rays of a slice of n caller rays
+struct RaysGatherArgs {
+    const DevScene *scene;
+    pvol_ray *rays;                  // [total] expanded (rays_emit_kernel's); patch adds the gather's draws to rng_skip
+    const SegInfo *info;             // [total] sample = the owner, the caller ray's index in the slice
+    const uint32_t *offset;          // [n + 1] where every block starts
+    uint32_t total, n;
+    int32_t nSamples;
+    const float *uBsdf, *uPhoton;    // [n][nSamples][3] the slice's rows of the caller's arrays
+    float *p, *frames, *wo, *kd, *rayEps;   // [total] x 3, 9, 3, 30, 1: the queries
+    float *mUBsdf, *mUPhoton;        // [total][nSamples][3] every member's copy of its owner's rows
+    float *Lg;                       // [total][30]
+    uint32_t *gDraws;                // [total]
+    float *rows;                     // [total][60] add: Lv += T (.) Lg
+    uint32_t *gatherDraws;           // [n] the caller's output (optional)
+};
+extern "C" hipError_t pvol_launch_rays_gather_query(const RaysGatherArgs *a, hipStream_t stream);   // the queries and the sample rows
+extern "C" hipError_t pvol_launch_rays_gather_patch(const RaysGatherArgs *a, hipStream_t stream);   // rng_skip += draws; gatherDraws
+extern "C" hipError_t pvol_launch_rays_gather_add(const RaysGatherArgs *a, hipStream_t stream);     // behind surface_kernel
 // the points [first, first + n) of d_p ordered by their cell of G (pvol_grid.hip)
 hipError_t pvol_order_points(const PhotonGrid *G, const float *d_p, uint32_t first, uint32_t n, uint32_t *work, void *temp, size_t *tempBytes,
                              hipStream_t stream);

@@ -12,20 +12,24 @@
 // stashed row, block size and offset)
 #define PVOL_RADIANCE_RAY_SCRATCH 324u
 #define PVOL_RADIANCE_CALLER_SCRATCH 248u
+// pvol_radiance_gather_batch* adds, per expanded ray, its final-gather query (p 12, frame 36, wo 12, kd 120, ray_eps 4), the result
+// (Lg 120, draws 4) and its copy of the owner's sample rows (2 x 12 per sample)
+#define PVOL_RADIANCE_GATHER_SCRATCH(nSamples) (308u + 24u * (uint32_t)(nSamples))
 
-static inline bool rays_slice_fits(uint64_t expanded, uint64_t callers, uint64_t budget) {
-    return expanded * PVOL_RADIANCE_RAY_SCRATCH + callers * PVOL_RADIANCE_CALLER_SCRATCH <= budget;
+// perExpanded: bytes per expanded ray -- PVOL_RADIANCE_RAY_SCRATCH, plus the gather's where the call gathers
+static inline bool rays_slice_fits(uint64_t expanded, uint64_t callers, uint64_t budget, uint64_t perExpanded = PVOL_RADIANCE_RAY_SCRATCH) {
+    return expanded * perExpanded + callers * PVOL_RADIANCE_CALLER_SCRATCH <= budget;
 }
 
 // How many of a candidate slice's n caller rays go: all of them when their blocks fit the budget, else the longest run that does --
 // whole runs of 64 where that many fit, never fewer than one ray.  offset: the exclusive scan over the n + 1 block sizes, so the
 // offsets of a run do not depend on what follows it and the scan stands for the run that is kept.
-static inline uint32_t rays_slice_cut(const uint32_t *offset, uint32_t n, uint64_t budget) {
-    if (n <= 1 || rays_slice_fits(offset[n], n, budget)) return n;
+static inline uint32_t rays_slice_cut(const uint32_t *offset, uint32_t n, uint64_t budget, uint64_t perExpanded = PVOL_RADIANCE_RAY_SCRATCH) {
+    if (n <= 1 || rays_slice_fits(offset[n], n, budget, perExpanded)) return n;
     uint32_t lo = 1, hi = n;   // fits(lo) is taken for granted (one ray always goes), fits(hi) is false
     while (hi - lo > 1) {
         const uint32_t mid = lo + (hi - lo) / 2;
-        if (rays_slice_fits(offset[mid], mid, budget)) lo = mid; else hi = mid;
+        if (rays_slice_fits(offset[mid], mid, budget, perExpanded)) lo = mid; else hi = mid;
     }
     return lo >= 64 ? lo - lo % 64 : lo;
 }

@@ -185,6 +185,14 @@ def lib():
         L.pvol_radiance_max_segments.argtypes = [C.c_int, C.c_int32]
         L.pvol_radiance_max_segments.restype = C.c_uint32
         L.pvol_radiance_set_scratch_bound.argtypes = [C.c_void_p, C.c_uint64]
+        L.pvol_radiance_gather_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(abi.GatherParams),
+                                                 C.POINTER(abi.RadianceGatherOut)]
+        L.pvol_radiance_gather_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(abi.GatherParams),
+                                                        C.POINTER(abi.RadianceGatherOut), C.c_void_p]
+        L.pvol_radiance_gather_check.argtypes = [C.c_int, C.POINTER(abi.RadianceGatherCheck), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int,
+                                                 C.c_uint32]
+        L.pvol_radiance_gather_slice.argtypes = [C.c_int32, C.c_uint64]
+        L.pvol_radiance_gather_slice.restype = C.c_uint32
         L.pvol_probe_hits.argtypes =[C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _f32p, C.POINTER(C.c_int32)]
         L.pvol_set_surface_integrator.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), _f32p, _f32p, _f32p, C.c_uint32]
         L.pvol_set_surface_integrator_maps.argtypes = [C.c_void_p, C.POINTER(abi.SurfaceParams), C.POINTER(abi.PhotonArray), C.POINTER(abi.PhotonArray)]
@@ -247,7 +255,7 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_build_gather_map", "pvol_build_gather_map_arrays", "pvol_gather_map_count", "pvol_gather_photons",
            "pvol_gather_photons_device", "pvol_gather_directions", "pvol_gather_directions_device", "pvol_final_gather",
            "pvol_final_gather_device", "pvol_lphoton_batch", "pvol_lphoton_batch_device", "pvol_radiance_batch",
-           "pvol_radiance_batch_device"]
+           "pvol_radiance_batch_device", "pvol_radiance_gather_batch", "pvol_radiance_gather_batch_device"]
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -652,6 +660,40 @@ class PhotonVolume:
         _check(lib().pvol_radiance_batch_device(self._h, d_rays, n_rays, d_streams, n_streams, int(output_kind), C.byref(out), hip_stream),
                "pvol_radiance_batch_device")
 
+    def radiance_gather_batch(self, rays, streams, max_dist, cos_gather_angle, u_bsdf, u_photon, output_kind=abi.OUT_SPECTRAL, want=()):
+        """radiance_batch() with the final gather (photonmap.cpp:183-296) at every Lambertian hit of every ray and spawned ray
+        (pvol_radiance_gather_batch).  u_bsdf, u_photon: [n, n_samples, 3] per CALLER ray, shared by the rays it spawns; max_dist,
+        cos_gather_angle as for final_gather().  Needs a gather map, a radiance result and a surface integrator without an indirect
+        map.  `want` may also name "gather_draws"[n] (abi.RADIANCE_GATHER_WANT)."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype == abi.RAY_DTYPE and streams.dtype == abi.STREAM_DTYPE and streams.flags["C_CONTIGUOUS"]
+        n = len(rays)
+        u_bsdf, u_photon = np.ascontiguousarray(u_bsdf, np.float32), np.ascontiguousarray(u_photon, np.float32)
+        if u_bsdf.ndim != 3 or u_bsdf.shape != u_photon.shape or u_bsdf.shape[0] != n or u_bsdf.shape[2] != 3:
+            raise ValueError("radiance_gather_batch: u_bsdf and u_photon are [n_rays, n_samples, 3]")
+        res = {"L": np.zeros((n, 60 if output_kind == abi.OUT_SPECTRAL else 4), np.float32)}
+        for k in want:
+            if k not in abi.RADIANCE_GATHER_WANT:
+                raise ValueError("radiance_gather_batch: unknown output %r" % (k,))
+            res[k] = np.zeros((n, 3), np.float32) if k == "surf_xyz" else np.zeros(n, np.float32 if k == "t_hit" else np.uint32)
+        out = abi.RadianceGatherOut(**{k: v.ctypes.data for k, v in res.items()})
+        g = abi.GatherParams(float(max_dist), int(u_bsdf.shape[1]), float(cos_gather_angle), u_bsdf.ctypes.data, u_photon.ctypes.data)
+        _check(lib().pvol_radiance_gather_batch(self._h, rays.ctypes.data, n, streams.ctypes.data, len(streams), int(output_kind), C.byref(g),
+                                                C.byref(out)), "pvol_radiance_gather_batch")
+        return res
+
+    def radiance_gather_batch_device(self, d_rays, n_rays, d_streams, n_streams, max_dist, n_samples, cos_gather_angle, d_u_bsdf, d_u_photon,
+                                     output_kind, d_L, hip_stream=0, **d_optional):
+        """Device-pointer variant (integers; d_optional: radiance_batch_device's and gather_draws=); synchronises hip_stream as
+        radiance_batch_device does."""
+        for k in d_optional:
+            if k not in abi.RADIANCE_GATHER_WANT:
+                raise ValueError("radiance_gather_batch_device: unknown output %r" % (k,))
+        out = abi.RadianceGatherOut(L=d_L or None, **{k: (v or None) for k, v in d_optional.items()})
+        g = abi.GatherParams(float(max_dist), int(n_samples), float(cos_gather_angle), d_u_bsdf or None, d_u_photon or None)
+        _check(lib().pvol_radiance_gather_batch_device(self._h, d_rays, n_rays, d_streams, n_streams, int(output_kind), C.byref(g), C.byref(out),
+                                                       hip_stream), "pvol_radiance_gather_batch_device")
+
     def radiance_set_scratch_bound(self, nbytes):
         """Test hook: the bytes of scratch a slice of radiance_batch() may take (0: the header's PVOL_RADIANCE_SCRATCH_BYTES)."""
         _check(lib().pvol_radiance_set_scratch_bound(self._h, int(nbytes)), "pvol_radiance_set_scratch_bound")
@@ -755,7 +797,8 @@ class PhotonVolume:
         """PhotonIntegrator with both maps of its LPhoton calls (pvol_set_surface_integrator_maps): the caustic estimate and,
         without the final gather, the same estimate over the indirect map.  Each map is None or (p[n,3], wi[n,3], alpha[n,30],
         n_paths); from_preprocess=True takes the caustic and the indirect store the last preprocess() kept instead.
-        final_gather=True with a non-empty indirect map raises PVOL_E_UNSUPPORTED: the final gather is not built."""
+        final_gather=True with a non-empty indirect map raises PVOL_E_UNSUPPORTED: the tile driver does not gather
+        (radiance_gather_batch() does, for the caller's own rays)."""
         sp = abi.SurfaceParams()
         sp.n_used, sp.max_dist, sp.max_specular_depth, sp.final_gather = int(n_used), float(max_dist), int(max_specular_depth), int(bool(final_gather))
         sp.use_preprocess_store = int(bool(from_preprocess))

@@ -396,8 +396,8 @@ int pvol_download_radiance_photons(pvol_ctx *ctx, float *p, float *n, float *rho
  * core/kdtree.h:180) over the direct, indirect and caustic maps, and the photons become radianceMap, which the final gather asks for
  * the nearest photon facing a point (RadiancePhotonProcess, photonshooter.h:63-78; integrators/photonmap.cpp:226-230).  Nothing
  * else calls these: pvol_preprocess* does not compute radiance, and the final gather that asks radianceMap exists as entry points
- * of its own (pvol_gather_* and pvol_final_gather* below), not yet inside the surface integrator: pvol_set_surface_integrator_maps
- * still refuses `finalgather` with an indirect map. */
+ * of its own (pvol_gather_* and pvol_final_gather* below) and inside pvol_radiance_gather_batch*, the caller-ray path; the tile
+ * driver does not gather: pvol_set_surface_integrator_maps still refuses `finalgather` with an indirect map. */
 typedef struct pvol_photon_array {   /* host arrays: p, wi 3 floats, alpha 30 floats per photon */
     const float *p, *wi, *alpha; uint32_t n; uint32_t n_paths;
 } pvol_photon_array;
@@ -501,8 +501,9 @@ int pvol_gather_directions_device(pvol_ctx *ctx, const float *d_p, const float *
  * (volumes/homogeneous.h:78-82).  Then
  *     L = sum_bsdf (Kd INV_PI) Lindir weight / n_samples + sum_photon (Kd INV_PI) Lindir weight / n_samples,
  * each loop summed in sample order; draws counts the RandomFloat calls.  A query whose Kd is black in every bin, or whose lookup
- * found fewer than 50 photons, gives L = 0 and zero draws with nothing traced.  Nothing is wired into the surface integrator yet:
- * pvol_set_surface_integrator_maps still refuses `finalgather` with an indirect map.
+ * found fewer than 50 photons, gives L = 0 and zero draws with nothing traced.  pvol_radiance_gather_batch* calls this at every
+ * Lambertian hit of the caller's rays; the tile driver does not: pvol_set_surface_integrator_maps still refuses `finalgather` with
+ * an indirect map.
  *
  * Statuses, decided in this one order (pvol_check_final_gather):
  *   1. PVOL_E_INVALID      NULL ctx
@@ -639,6 +640,59 @@ int pvol_radiance_batch(pvol_ctx *ctx, const pvol_ray *rays, uint32_t n_rays, pv
  * table goes up; pvol_li_batch_device synchronises it likewise where it sizes a slice); the kernels of the last slice are left in flight. */
 int pvol_radiance_batch_device(pvol_ctx *ctx, const pvol_ray *d_rays, uint32_t n_rays, pvol_stream *d_streams, uint32_t n_streams,
                                int output_kind, const pvol_radiance_out *out, void *hip_stream);
+
+/* ---- ... with the final gather
+ * pvol_radiance_batch* with the final-gather branch of PhotonIntegrator::Li (integrators/photonmap.cpp:183-296) at every Lambertian
+ * hit of every member of a ray's block -- the ray itself and every ray the specular recursion spawns for it, as the reference's
+ * recursion evaluates it.  Everything is as steps 1 to 4 above; at a matte hit with a non-black Kd, in addition:
+ *   query   p = the hit point, frame = the shading nn, dpdu and the geometric normal, wo = -d of the member, kd the material's,
+ *           ray_eps the hit's: one query of pvol_final_gather
+ *   samples u_bsdf, u_photon per CALLER ray and sample (uComponent, uDir[0], uDir[1]); every member of a ray's block reads its caller
+ *           ray's rows, because spawned rays see the same Sample (core/integrator.cpp:198, :243)
+ *   value   Lg and its draws are what pvol_final_gather_device returns for that query with max_dist, n_samples and cos_gather_angle
+ *           passed on unchanged
+ *   sum     Ls_matte becomes Ls_matte + Lg before T (.) Ls is formed; surf_xyz includes the gather
+ *   stream  the gather's draws (one per gather ray that hits, only under a medium) come after the hit's other surface draws and before
+ *           that member's own volume Li(); surf_draws includes them and streams[].end_draw moves accordingly
+ * The reference evaluates either the gather or LPhoton(indirectMap), never both (:183, :307): the surface integrator must be on and
+ * must describe NO indirect map (pvol_set_surface_integrator, or pvol_set_surface_integrator_maps with an empty indirect array), so
+ * no indirect LPhoton and none of its 2 x 72 rho draws happen.  A matte hit with a black Kd, a glass hit, a miss and a query whose
+ * lookup finds fewer than 50 photons add nothing and draw nothing.  pvol_set_surface_integrator_maps still refuses `finalgather`
+ * with an indirect map, and the tile driver (pvol_render_tasks*) does not gather.
+ *
+ * Statuses, decided in this one order (pvol_radiance_gather_check):
+ *   1. items 1 to 4 of pvol_radiance_batch's list, for the same arguments
+ *   2. PVOL_E_INVALID      NULL gather; the argument faults of pvol_gather_directions (max_dist, n_samples, cos_gather_angle; a NULL
+ *                          u_bsdf or u_photon with n_rays > 0)
+ *   3. PVOL_E_NO_SCENE
+ *   4. PVOL_E_UNSUPPORTED  the scene's medium is a density region
+ *   5. PVOL_E_INVALID      no surface integrator is on
+ *   6. PVOL_E_INVALID      the surface integrator describes a non-empty indirect map
+ *   7. PVOL_E_INVALID      no gather map built
+ *   8. PVOL_E_INVALID      no radiance result, or one with zero radiance photons
+ *   then the stream-partition fault and the device's own codes, as for pvol_radiance_batch.  A rejected call writes nothing; n_rays == 0
+ *   or n_streams == 0 does nothing and returns PVOL_OK.
+ * A slice's scratch, the queries included (308 + 24 n_samples bytes per ray and spawned ray on top of pvol_radiance_batch's), stays
+ * within PVOL_RADIANCE_SCRATCH_BYTES; pvol_final_gather_device's own bound and slices apply inside.  No atomics: two runs agree byte
+ * for byte. */
+typedef struct pvol_gather_params {
+    float max_dist;                  /* the gather lookup's first radius, as for pvol_gather_directions                      */
+    int32_t n_samples;               /* gatherSamples after RequestSamples has halved and rounded it, 1..256                */
+    float cos_gather_angle;          /* PhotonShooter's cosGatherAngle, inside (-1, 1)                                      */
+    const float *u_bsdf, *u_photon;  /* n_rays x n_samples x 3 floats each; host arrays in the host form, device in the other */
+} pvol_gather_params;
+typedef struct pvol_radiance_gather_out {   /* pvol_radiance_out's members in their order, then: */
+    float    *L, *surf_xyz, *t_hit;
+    uint32_t *draws, *surf_draws, *n_segments;
+    uint32_t *gather_draws;  /* per ray (optional): the gather's RandomFloat calls, summed over the ray's block; part of surf_draws */
+} pvol_radiance_gather_out;
+int pvol_radiance_gather_batch(pvol_ctx *ctx, const pvol_ray *rays, uint32_t n_rays, pvol_stream *streams, uint32_t n_streams,
+                               int output_kind, const pvol_gather_params *gather, const pvol_radiance_gather_out *out);
+/* Device arrays throughout (u_bsdf, u_photon and the members of *out too; *gather and *out themselves are host memory); synchronises
+ * `hip_stream` as pvol_radiance_batch_device does. */
+int pvol_radiance_gather_batch_device(pvol_ctx *ctx, const pvol_ray *d_rays, uint32_t n_rays, pvol_stream *d_streams, uint32_t n_streams,
+                                      int output_kind, const pvol_gather_params *gather, const pvol_radiance_gather_out *out,
+                                      void *hip_stream);
 
 /* Device-side error flags of the batches enqueued so far (pvol_li_batch_device, pvol_render_tasks_device): waits
  * for the device and returns PVOL_E_LIMIT if a ray needed more march steps than the kernels' record/LDS plan holds
