@@ -16,7 +16,6 @@
 #include "pvol_radwalk_dev.h"
 #include "pvol_host.h"
 
-#define FG_INV_PI 0.31830988618379067154f /* core/pbrt.h:192 */
 #define FG_NONE 0xffffffffu
 #define FG_RAY_SCRATCH 64u                /* bytes per gather ray: its pvol_gather_sample and its pvol_gather_ray */
 
@@ -64,10 +63,10 @@ __global__ __launch_bounds__(LANES) void final_gather_trace_kernel(FgArgs A) {
     const DevScene &S = *A.scene;
     const float4 d0 = d4[0];
     const V3 o = v3(A.p[3 * (size_t)q], A.p[3 * (size_t)q + 1], A.p[3 * (size_t)q + 2]), wi = v3(d0.x, d0.y, d0.z);
-    SurfHit h;
+    Hit h;
     if (!surf_closest(S, o, wi, A.rayEps[q], &h)) { put_ray(out, 0.f, v3(0.f, 0.f, 0.f), FG_NONE, 0, 0u, 0u); return; }
     // Faceforward(gatherIsect.dg.nn, -bounceRay.d) (geometry.h:520-522) with the geometric normal
-    V3 n = surf_ng(S, h);
+    V3 n = hit_ng(S, h);
     if (dot(n, -wi) < 0.f) n = -n;
     const float hp[3] = {h.p.x, h.p.y, h.p.z};
     const int64_t j = radiance_nearest(A.walk, hp, n.x, n.y, n.z);
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(256) void final_gather_sum_kernel(FgArgs A) {
     if (q >= A.count) return;
     const DevScene &S = *A.scene;
     const bool mine = bin < 30;
-    const float fr = mine ? A.kd[30 * (size_t)q + bin] * FG_INV_PI : 0.f;   // Lambertian::f, reflection.cpp:304-306
+    const float fr = mine ? A.kd[30 * (size_t)q + bin] * K_INV_PI : 0.f;   // Lambertian::f, reflection.cpp:304-306
     const bool medium = S.volKind != PVOL_VOLUME_NONE;
     const float sigT = (mine && medium) ? S.sigA[bin] + S.sigS[bin] : 0.f;
     const V3 o = v3(A.p[3 * (size_t)q], A.p[3 * (size_t)q + 1], A.p[3 * (size_t)q + 2]);

@@ -11,13 +11,13 @@
 #include <vector>
 
 #include "pvol_math.h"
+#include "pvol_bsdf_dev.h"
 #include "pvol_host.h"
 #include "pvol_gather_tree.h"
 
 #define GATHER_K 50                           // nIndirSamplePhotons (photonmap.cpp:190)
 #define GATHER_STACK PVOL_GATHER_MAX_DEPTH    // one frame per node of the path from the root
 #define GATHER_MAX_ROUNDS 300u                // from the smallest positive fp32 to +inf are 277 doublings: never reached
-#define GATHER_INV_PI 0.31830988618379067154f /* core/pbrt.h:192 */
 #define GATHER_NONE 0xffffffffu
 
 struct GatherArgs {
@@ -73,28 +73,6 @@ __device__ __forceinline__ void heap_adjust(HeapKeys *hk, HeapIds *hn, int lane,
         hole = child - 1;
     }
     heap_push(hk, hn, lane, hole, top, vd, vn);
-}
-
-// cosf / sinf as the reference's C library gives them: correctly rounded.  The device's own cosf is good to an ulp or two, which
-// is not enough here: near the rim of the disk sqrt(1 - dx^2 - dy^2) turns one ulp of dx into 1e-3 of the pdf.
-__device__ __forceinline__ float cos_rounded(float x) { return (float)cos((double)x); }
-__device__ __forceinline__ float sin_rounded(float x) { return (float)sin((double)x); }
-
-// ConcentricSampleDisk, core/montecarlo.cpp:306-348
-__device__ __forceinline__ void gather_concentric_disk(float u0, float u1, float *dx, float *dy) {
-    float r, theta;
-    const float sx = 2 * u0 - 1, sy = 2 * u1 - 1;
-    if (sx == 0.f && sy == 0.f) { *dx = 0.f; *dy = 0.f; return; }
-    if (sx >= -sy) {
-        if (sx > sy) { r = sx; if (sy > 0.f) theta = sy / r; else theta = 8.0f + sy / r; }
-        else { r = sy; theta = 2.0f - sx / r; }
-    } else {
-        if (sx <= sy) { r = -sx; theta = 4.0f - sy / r; }
-        else { r = -sy; theta = 6.0f + sx / r; }
-    }
-    theta *= K_PI / 4.f;
-    *dx = r * cos_rounded(theta);
-    *dy = r * sin_rounded(theta);
 }
 
 __device__ __forceinline__ float power_heuristic(int nf, float fPdf, int ng, float gPdf) {   // core/montecarlo.h:262-265
@@ -207,8 +185,8 @@ template <bool DIRS> __global__ __launch_bounds__(LANES) void gather_lookup_kern
     }
     // the BSDF's frame (BSDF::BSDF, core/reflection.cpp:619-627)
     const float *fr = A.frames + 9 * (size_t)i;
-    const V3 nn = v3(fr[0], fr[1], fr[2]), sn = normalize(v3(fr[3], fr[4], fr[5])), ng = v3(fr[6], fr[7], fr[8]);
-    const V3 tn = cross(nn, sn);
+    const V3 nn = v3(fr[0], fr[1], fr[2]), ng = v3(fr[6], fr[7], fr[8]);
+    const BsdfFrame F = bsdf_frame(nn, v3(fr[3], fr[4], fr[5]));
     const V3 woW = v3(A.wo[3 * (size_t)i], A.wo[3 * (size_t)i + 1], A.wo[3 * (size_t)i + 2]);
     const float woZ = dot(woW, nn), woNg = dot(woW, ng);
     const float cosG = A.cosGather, thresh = .999f * cosG;
@@ -223,19 +201,19 @@ template <bool DIRS> __global__ __launch_bounds__(LANES) void gather_lookup_kern
             if (loop == 0) {
                 // BSDF::Sample_f over one Lambertian lobe (reflection.cpp:534-598; BxDF::Sample_f, :323-330)
                 float dx, dy;
-                gather_concentric_disk(u[1], u[2], &dx, &dy);
+                concentric_disk<true>(u[1], u[2], &dx, &dy);
                 V3 l = v3(dx, dy, sqrtf(fmaxf(0.f, 1.f - dx * dx - dy * dy)));
                 if (woZ < 0.f) l.z *= -1.f;
-                bsdfPdf = woZ * l.z > 0.f ? fabsf(l.z) * GATHER_INV_PI : 0.f;
+                bsdfPdf = woZ * l.z > 0.f ? fabsf(l.z) * K_INV_PI : 0.f;
                 valid = bsdfPdf != 0.f;
-                wi = v3(sn.x * l.x + tn.x * l.y + nn.x * l.z, sn.y * l.x + tn.y * l.y + nn.y * l.z, sn.z * l.x + tn.z * l.y + nn.z * l.z);
+                wi = to_world(F, l);
             } else {
                 // photonmap.cpp:253-260; a uComponent outside [0, 1) is clamped to a photon that exists
                 const int photonNum = min(GATHER_K - 1, max(0, (int)floorf(fminf(fmaxf(u[0], 0.f), 1.f) * (float)GATHER_K)));
                 chosen = hn[photonNum][lane];
                 const V3 z = v3(A.wi[3 * (size_t)chosen], A.wi[3 * (size_t)chosen + 1], A.wi[3 * (size_t)chosen + 2]);
                 V3 vx;
-                if (fabsf(z.x) > fabsf(z.y)) {   // CoordinateSystem, core/geometry.h:508-518
+                if (fabsf(z.x) > fabsf(z.y)) {   // CoordinateSystem written out: coordinate_system() here moves gather_lookup_kernel<true> from 82 to 80 VGPRs
                     const float invLen = 1.f / sqrtf(z.x * z.x + z.z * z.z);
                     vx = v3(-z.z * invLen, 0.f, z.x * invLen);
                 } else {
@@ -249,7 +227,7 @@ template <bool DIRS> __global__ __launch_bounds__(LANES) void gather_lookup_kern
                 const float phi = u[2] * 2.f * K_PI;
                 wi = (vx * (cos_rounded(phi) * sintheta) + vy * (sin_rounded(phi) * sintheta)) + z * costheta;
                 const float wiZ = dot(wi, nn);   // BSDF::Pdf (reflection.cpp:601-616)
-                bsdfPdf = woZ * wiZ > 0.f ? fabsf(wiZ) * GATHER_INV_PI : 0.f;
+                bsdfPdf = woZ * wiZ > 0.f ? fabsf(wiZ) * K_INV_PI : 0.f;
                 valid = true;
             }
             // f is black unless wi and wo lie on one side of the GEOMETRIC normal (reflection.cpp:585-591, :634-641)

@@ -580,7 +580,7 @@ int pvol_check_radiance(int what, int haveCtx, int haveState, int32_t nLookup, f
 int pvol_check_surface_maps(const pvol_surface_params *sp, int haveScene, int materials, int storesKept, const uint32_t *storeN,
                             const uint32_t *storePaths, const pvol_photon_array *caustic, const pvol_photon_array *indirect, int hostPointers);
 // the ray probe of the tests (pvol_probe.hip): n host rays through the device's own hit routines on the uploaded scene -- mode 0
-// surf_closest, 1 lane_occluded, 2 scene_occluded (one ray per wave); per ray out gets t, rayEps, p, nn, dpdu (11 floats) and outi the
+// surf_closest, 1 lane_occluded, 2 scene_occluded (one ray per wave), 3 scene_closest (one ray per wave); per ray out gets t, rayEps, p, nn, dpdu (11 floats) and outi the
 // hit flag, the primitive (triangle index in upload order, -1 - i for sphere i) and its material.  Synchronous; PVOL_E_INVALID for a
 // null pointer, no scene, n == 0 or an unknown mode
 int pvol_probe_hits(pvol_ctx *c, const pvol_ray *rays, uint32_t n, int mode, float *out, int32_t *outi);

@@ -43,6 +43,7 @@
 #include "pvol_rng_dev.h"
 #include "pvol_light_dev.h"
 #include "pvol_gridrows_dev.h"
+#include "pvol_closest_dev.h"   // scene_occluded, lane_occluded
 
 // ------------------------------------------------------------------------------------------ k-NN gather
 struct Gather {
@@ -696,8 +697,6 @@ __device__ bool march_ray(const DevScene &S, const LiArgs &A, const pvol_ray &pr
     if (tauRec) *tauRec = TauRec{tLen, tScale};
     return true;
 }
-
-#include "pvol_closest_dev.h"   // lane_occluded
 
 // ---- blocked march for the two ray-parallel modes over an analytic (homogeneous / rainbow) medium.
 // Everything about a march step that is SCALAR -- sample point, inside test, segment length, light

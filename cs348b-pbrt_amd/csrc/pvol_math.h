@@ -11,6 +11,7 @@
 #define MT_N 624
 #define MT_M 397
 #define K_PI 3.14159265358979323846f  /* core/pbrt.h:191: M_PI is a float literal */
+#define K_INV_PI 0.31830988618379067154f  /* core/pbrt.h:192 */
 
 typedef float4 f4;
 
@@ -207,18 +208,6 @@ __device__ __forceinline__ bool tri_closest(const DevTri &tr, V3 o, V3 d, float 
 }
 #include "pvol_bvh_dev.h"
 #include "pvol_sphere_dev.h"
-// Scene::IntersectP (core/scene.h:57-61): one triangle per lane; a large scene walks its hierarchy (wave-uniform ray)
-__device__ __forceinline__ bool scene_occluded(const DevScene &S, const RayD &ray, int lane) {
-    if (S.nSpheres && spheres_occluded(S, ray.o, ray.d, ray.mint, ray.maxt)) return true;
-    if (S.bvhNodes) return bvh_occluded(S, ray.o, ray.d, ray.mint, ray.maxt);
-    bool hit = false;
-    for (int base = 0; base < S.nTris; base += LANES) {
-        int t = base + lane;
-        bool h = (t < S.nTris) && tri_hit(S.tris[t], ray);
-        hit = hit || wave_any(h);
-    }
-    return hit;
-}
 
 // ------------------------------------------------------------------------------------------ volume
 __device__ __forceinline__ float lerpf(float t, float a, float b) { return (1.f - t) * a + t * b; }

@@ -16,7 +16,6 @@
 #include "pvol_host.h"
 
 #define RAD_MAX_LOOKUP 576   // the project's nused bound
-#define RAD_INV_PI 0.31830988618379067154f   /* core/pbrt.h:192 */
 
 // One surface map as radiance_lo_kernel reads it
 struct RadMap {
@@ -155,8 +154,8 @@ __global__ __launch_bounds__(256) void radiance_lo_kernel(const RadLoArgs *__res
     const float Et = __shfl(E, (lane & 31) + 32);
     if (lane < 30) {
         float Lo = 0.f;
-        if (doR) Lo += (rr * RAD_INV_PI) * E;
-        if (doT) Lo += (rt * RAD_INV_PI) * Et;
+        if (doR) Lo += (rr * K_INV_PI) * E;
+        if (doT) Lo += (rt * K_INV_PI) * Et;
         A.lo[30 * (size_t)w + lane] = Lo;
     }
 }

@@ -23,7 +23,7 @@
 #define PVOL_RAYS_DEV_H
 
 // Scene::Intersect over [mint, maxt] (samplerrenderer.cpp:236): surf_closest knows no upper bound, the caller's maxt is applied here
-__device__ __forceinline__ bool rays_clip(const DevScene &S, const pvol_ray &r, V3 *o, V3 *d, SurfHit *h) {
+__device__ __forceinline__ bool rays_clip(const DevScene &S, const pvol_ray &r, V3 *o, V3 *d, Hit *h) {
     *o = v3(r.o[0], r.o[1], r.o[2]); *d = v3(r.d[0], r.d[1], r.d[2]);
     h->tri = 0; h->mat = 0; h->t = 0.f; h->rayEps = 0.f; h->p = h->nn = h->dpdu = v3(0.f, 0.f, 0.f);
     return surf_closest(S, *o, *d, r.mint, h) && h->t <= r.maxt;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(LANES) void rays_count_kernel(RaysArgs A) {
     if (i < A.n && A.specOn) {   // only a glass hit spawns anything: a matte hit's draws are the emit pass's business
         const DevScene &S = *A.scene;
         V3 o, d;
-        SurfHit h;
+        Hit h;
         if (rays_clip(S, A.in[i], &o, &d, &h) && S.shootScene->mats[h.mat].kind != PVOL_MATERIAL_MATTE) {
             SpecCtx X;
             X.blackMask = 0u; X.pending = 0u; X.nSeg = 0u;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(LANES) void rays_emit_kernel(RaysArgs A) {
     const uint32_t base = A.offset[i], e = A.offset[i + 1] - 1u;
     pvol_ray r = A.in[i];
     V3 o, d;
-    SurfHit h;
+    Hit h;
     const bool hit = rays_clip(S, r, &o, &d, &h);
     uint32_t pending = 0u;
     if (hit) {

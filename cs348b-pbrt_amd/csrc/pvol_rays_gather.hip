@@ -28,7 +28,7 @@ __global__ __launch_bounds__(LANES) void rays_gather_query_kernel(RaysGatherArgs
     const bool owned = si.sample < A.n;   // always, unless the count and the emit pass disagreed and left a slot unwritten
     const bool primary = owned && m + 1u == A.offset[si.sample + 1u];
     const V3 o = v3(pr.o[0], pr.o[1], pr.o[2]), d = v3(pr.d[0], pr.d[1], pr.d[2]);
-    SurfHit h;
+    Hit h;
     h.tri = 0; h.mat = 0; h.t = 0.f; h.rayEps = 0.f; h.p = h.nn = h.dpdu = v3(0.f, 0.f, 0.f);
     const bool hit = owned && (!primary || si.pad[0]) && pr.maxt >= pr.mint && surf_closest(S, o, d, pr.mint, &h);
     const DevMaterial &mat = S.shootScene->mats[h.mat];
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(LANES) void rays_gather_query_kernel(RaysGatherArgs
     // a dead query still goes through the lookup: a finite point and a unit frame, and a black kd, which is what kills it
     V3 p = v3(0.f, 0.f, 0.f), nn = v3(0.f, 0.f, 1.f), dpdu = v3(1.f, 0.f, 0.f), ng = nn, wo = nn;
     float eps = 0.f;
-    if (lambert) { p = h.p; nn = h.nn; dpdu = h.dpdu; ng = surf_ng(S, h); wo = -d; eps = h.rayEps; }
+    if (lambert) { p = h.p; nn = h.nn; dpdu = h.dpdu; ng = hit_ng(S, h); wo = -d; eps = h.rayEps; }
     float *qp = A.p + 3 * (size_t)m, *qf = A.frames + 9 * (size_t)m, *qw = A.wo + 3 * (size_t)m, *qk = A.kd + 30 * (size_t)m;
     qp[0] = p.x; qp[1] = p.y; qp[2] = p.z;
     qf[0] = nn.x; qf[1] = nn.y; qf[2] = nn.z; qf[3] = dpdu.x; qf[4] = dpdu.y; qf[5] = dpdu.z; qf[6] = ng.x; qf[7] = ng.y; qf[8] = ng.z;

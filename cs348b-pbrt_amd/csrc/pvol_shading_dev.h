@@ -1,4 +1,4 @@
-// pvol_shading_dev.h -- included by pvol_math.h users that find closest hits (pvol_shoot.hip, pvol_surface_dev.h).
+// pvol_shading_dev.h -- included by pvol_closest_dev.h.
 //
 // Triangle::GetShadingGeometry (shapes/trianglemesh.cpp:293-368) for a mesh with per-vertex normals and neither "S" nor "uv": the
 // default uvs (0,0), (1,0), (1,1) of Triangle::GetUVs.  The vertex normals come from DevScene::triN, already in world space (the
@@ -9,6 +9,7 @@
 // every DifferentialGeometry (core/diffgeom.cpp:46-54) -- so a reversed mesh flips its SHADING normal too.  That is the reference.
 #ifndef PVOL_SHADING_DEV_H
 #define PVOL_SHADING_DEV_H
+#include "pvol_bsdf_dev.h"
 
 struct ShadingFrame { V3 dpdu, nn; bool any; };
 
@@ -40,7 +41,7 @@ __device__ __attribute__((noinline)) ShadingFrame shading_geometry(const float *
     if (len_sq(ts) > 0.f) {
         ts = normalize(ts);
         ss = cross(ts, ns);
-    } else if (fabsf(ns.x) > fabsf(ns.y)) {   // CoordinateSystem, core/geometry.h:508-518
+    } else if (fabsf(ns.x) > fabsf(ns.y)) {   // CoordinateSystem written out: coordinate_system() here costs tile_kernel / tile_mw_kernel 16 B of scratch
         const float invLen = 1.f / sqrtf(ns.x * ns.x + ns.z * ns.z);
         ss = v3(-ns.z * invLen, 0.f, ns.x * invLen);
         ts = cross(ns, ss);

@@ -15,7 +15,7 @@
 //     roulette are decisions and a different rounding would send the task down a different path;
 //   * the transmittance march (photonshooter.cpp:71-80: one draw + one tau() + one 30-bin exp per stepSize of path)
 //     runs 64 STEPS at a time for analytic media, one step per lane, then takes the first lane whose test fires;
-//   * closest hit: one triangle per lane, minimum by DPP, ties to the later triangle as the serial scan has them;
+//   * closest hit (scene_closest, pvol_closest_dev.h): one triangle per lane, minimum by DPP, ties to the later triangle as the serial scan has them;
 //   * followPhoton's recursion is an explicit frame stack in LDS (scalars by lane 0, alpha by the bin lanes);
 //   * the six Halton dimensions of a path are computed by six lanes.
 // The path is VALU/latency bound; the only compulsory HBM traffic is the 144-B photon record.
@@ -24,13 +24,12 @@
 #include "pvol_rng_dev.h"
 #include "pvol_light_dev.h"
 #include "pvol_shoot_args.h"
-#include "pvol_shading_dev.h"
+#include "pvol_closest_dev.h"   // Hit, scene_closest
+#include "pvol_bsdf_dev.h"
 
 #define SH_MAX_DEPTH 24   // frames; deeper recursion aborts the path and is counted
 #define NBIN 30
 #define SH_STATE_WORDS 640   // per task in global memory: mt[624], mti, totalPaths, pad
-
-// BxDFType bits, core/reflection.h:107-121
 
 // ------------------------------------------------------------------------------------------ spectra: lane b == bin b
 __device__ __forceinline__ float sp_y(float a, float cieYl) {   // core/spectrum.h:433-439, the serial sum
@@ -47,91 +46,7 @@ __device__ __forceinline__ int sp_lambda(float a, bool binLane) {   // extractLa
     return 400 + (__ffsll((unsigned long long)m) - 1) * 10;
 }
 
-// ------------------------------------------------------------------------------------------ scene queries
-struct Hit {
-    int tri, mat;     // tri: where the triangle's vertices lie -- scene index (linear scan) or hierarchy slot; -1 - i: sphere i
-    float t, rayEps;
-    V3 p, dpdu, nn;   // nn, dpdu: the SHADING geometry where the triangle carries vertex normals (pvol_shading_dev.h), else the geometric one
-};
-// photonIsect.dg.nn, the geometric normal (BSDF::f's side test, the radiance photon's normal): the hit's nn unless the scene has vertex normals
-__device__ __forceinline__ V3 hit_ng(const DevScene &S, const Hit &h) { return (S.triN && h.tri >= 0) ? geometric_normal(S, h.tri) : h.nn; }
-// Scene::Intersect (core/scene.h:50-56): closest hit.  The serial scan tightens maxt with `t > maxt` rejections, so of
-// several triangles at the same t the LATER one wins: one triangle per lane, minimum over the wave, highest lane of the tie.
-__device__ __forceinline__ bool scene_closest(const DevScene &S, const DevShootScene &H, V3 o, V3 d, float mint, float *maxt, Hit *hit, int lane) {
-    float tk = INFINITY;
-    bool any = false;
-    int best = -1, where = -1;
-    V3 p1, p2, p3;
-    bool flip;
-    if (S.bvhNodes) {   // large scene: every lane walks the hierarchy with the same ray (pvol_bvh_dev.h)
-        const int slot = bvh_closest(S, o, d, mint, *maxt, &tk);
-        if (slot < 0 && !S.nSpheres) return false;
-        if (slot < 0) tk = INFINITY;
-        else {
-        const float4 q1 = S.bvhTris[3 * slot], q2 = S.bvhTris[3 * slot + 1], q3 = S.bvhTris[3 * slot + 2];
-        p1 = v3(q1.x, q1.y, q1.z); p2 = v3(q2.x, q2.y, q2.z); p3 = v3(q3.x, q3.y, q3.z);
-        best = __float_as_int(q1.w);
-        where = slot;
-        hit->mat = __float_as_int(q2.w);
-        flip = __float_as_int(q3.w) != 0;
-        }
-    } else {
-        for (int base = 0; base < S.nTris; base += LANES) {   // at most PVOL_MAX_TRIS == 64: one pass
-            float t = 0.f;
-            const bool h = (base + lane < S.nTris) && tri_closest(S.tris[base + lane], o, d, mint, *maxt, &t);
-            const float tm = -wave_max(h ? -t : -INFINITY);
-            if (__ballot(h) && tm <= tk) {
-                const uint64_t m = __ballot(h && t == tm);
-                tk = tm;
-                best = base + 63 - __clzll((unsigned long long)m);
-                any = true;
-            }
-        }
-        if (!any && !S.nSpheres) return false;
-        if (any) {
-            const DevTri &tr = S.tris[best];
-            p1 = v3(tr.p1[0], tr.p1[1], tr.p1[2]); p2 = v3(tr.p2[0], tr.p2[1], tr.p2[2]); p3 = v3(tr.p3[0], tr.p3[1], tr.p3[2]);
-            hit->mat = H.triMat[best];
-            flip = H.triFlip[best] != 0;
-            where = best;
-        }
-    }
-    if (S.nSpheres) {   // Shape "sphere" (pvol_sphere_dev.h), tested after the triangles with the ray shortened to their hit
-        float ts = best >= 0 ? tk : *maxt;
-        V3 ph;
-        const int si = spheres_closest(S, o, d, mint, &ts, &ph);
-        if (si >= 0) {
-            *maxt = ts;
-            hit->tri = -1 - si;
-            hit->mat = S.spheres[si].mat;
-            hit->t = ts;
-            hit->rayEps = 5e-4f * ts;   // sphere.cpp:155
-            sphere_dg(S.spheres[si], ph, &hit->p, &hit->dpdu, &hit->nn);
-            return true;
-        }
-        if (best < 0) return false;
-    }
-    *maxt = tk;
-    // shapes/trianglemesh.cpp:163-181 with the default uvs (0,0),(1,0),(1,1)
-    float du1 = 0.f - 1.f, du2 = 1.f - 1.f, dv1 = 0.f - 1.f, dv2 = 0.f - 1.f;
-    V3 dp1 = p1 - p3, dp2 = p2 - p3;
-    float determinant = du1 * dv2 - dv1 * du2;
-    float invdet = 1.f / determinant;
-    hit->dpdu = (dp1 * dv2 - dp2 * dv1) * invdet;
-    V3 dpdv = (dp1 * (-du2) + dp2 * du1) * invdet;
-    hit->tri = where;
-    hit->t = tk;
-    hit->p = o + d * tk;
-    hit->rayEps = 1e-3f * tk;
-    hit->nn = normalize(cross(hit->dpdu, dpdv));   // core/diffgeom.cpp:46-54
-    if (flip) hit->nn = hit->nn * -1.f;
-    if (S.triN) {   // Triangle::GetShadingGeometry for a mesh with "normal N" (triN is in the scene's original order)
-        const ShadingFrame f = shading_geometry(S.triN + (size_t)best * 9, p1, p2, p3, o, d, hit->dpdu, flip);
-        if (f.any) { hit->dpdu = f.dpdu; hit->nn = f.nn; }
-    }
-    return true;
-}
-
+// ------------------------------------------------------------------------------------------ the path (closest hit: pvol_closest_dev.h)
 // PhotonVolumeIntegrator::Transmittance with sample == NULL (photonvolume.cpp:15-30): one draw, Exp(-tau), one bin per lane.
 // sigTl = sigma_a + sigma_s of the lane's bin (0 on the pad lanes, which therefore return 1).
 // (every function of the shooting path is forced inline: shoot_kernel is ONE body, as the inliner used to make it on its own until the
@@ -166,42 +81,10 @@ __device__ __forceinline__ float transmittance_bins(const DevScene &S, V3 o, V3 
     return expf(-(tau * step));
 }
 
-// core/reflection.cpp:60-67 + 115-135 with scalar indices
-__device__ __forceinline__ float fresnel_dielectric(float cosi, float eta_i, float eta_t) {
-    cosi = cosi < -1.f ? -1.f : (cosi > 1.f ? 1.f : cosi);
-    bool entering = cosi > 0.f;
-    float ei = eta_i, et = eta_t;
-    if (!entering) { float t = ei; ei = et; et = t; }
-    float sint = ei / et * sqrtf(fmaxf(0.f, 1.f - cosi * cosi));
-    if (sint >= 1.f) return 1.f;
-    float cost = sqrtf(fmaxf(0.f, 1.f - sint * sint));
-    float ac = fabsf(cosi);
-    float Rparl = ((et * ac) - (ei * cost)) / ((et * ac) + (ei * cost));
-    float Rperp = ((ei * ac) - (et * cost)) / ((ei * ac) + (et * cost));
-    return (Rparl * Rparl + Rperp * Rperp) / 2.f;
-}
-
 __device__ __forceinline__ int num_components(const DevMaterial &m, int flags) {
     int n = 0;
     for (int i = 0; i < m.nBxdf; ++i) if ((m.bxdfType[i] & flags) == m.bxdfType[i]) ++n;
     return n;
-}
-
-// ConcentricSampleDisk, core/montecarlo.cpp:306-348
-__device__ __forceinline__ void concentric_disk(float u0, float u1, float *dx, float *dy) {
-    float r, theta;
-    float sx = 2 * u0 - 1, sy = 2 * u1 - 1;
-    if (sx == 0.f && sy == 0.f) { *dx = 0.f; *dy = 0.f; return; }
-    if (sx >= -sy) {
-        if (sx > sy) { r = sx; if (sy > 0.f) theta = sy / r; else theta = 8.0f + sy / r; }
-        else { r = sy; theta = 2.0f - sx / r; }
-    } else {
-        if (sx <= sy) { r = -sx; theta = 4.0f - sy / r; }
-        else { r = -sy; theta = 6.0f + sx / r; }
-    }
-    theta *= K_PI / 4.f;
-    *dx = r * cosf(theta);
-    *dy = r * sinf(theta);
 }
 
 // BSDF::Sample_f with BSDF_ALL (core/reflection.cpp:534-598); `lambda` = extractLambda of the incoming alpha.  The sampled f
@@ -217,19 +100,17 @@ __device__ __forceinline__ void bsdf_sample(const DevScene &S, const DevMaterial
     if (matching == 0) return;
     int which = min((int)floorf(ucomp * matching), matching - 1);
     int type = m.bxdfType[which];
-    const V3 nn = h.nn;
-    V3 sn = normalize(h.dpdu);
-    V3 tn = cross(nn, sn);
-    V3 wo = v3(dot(woW, sn), dot(woW, tn), dot(woW, nn));
+    const BsdfFrame fr = bsdf_frame(h.nn, h.dpdu);
+    const V3 wo = to_local(fr, woW);
     V3 wi = v3(0.f, 0.f, 0.f);
     if (type == (BSDF_REFLECTION | BSDF_DIFFUSE)) {
         // BxDF::Sample_f (reflection.cpp:323-330): CosineSampleHemisphere
         float dx, dy;
-        concentric_disk(u0, u1, &dx, &dy);
+        concentric_disk<false>(u0, u1, &dx, &dy);
         wi = v3(dx, dy, sqrtf(fmaxf(0.f, 1.f - dx * dx - dy * dy)));
         if (wo.z < 0.f) wi.z *= -1.f;
-        *pdf = (wo.z * wi.z > 0.f) ? fabsf(wi.z) * 0.31830988618379067154f : 0.f;
-        *fWhich = 0; *fFac = 0.31830988618379067154f;
+        *pdf = (wo.z * wi.z > 0.f) ? fabsf(wi.z) * K_INV_PI : 0.f;
+        *fWhich = 0; *fFac = K_INV_PI;
     } else if (type == (BSDF_REFLECTION | BSDF_SPECULAR)) {
         wi = v3(-wo.x, -wo.y, wo.z);
         *pdf = 1.f;
@@ -244,6 +125,7 @@ __device__ __forceinline__ void bsdf_sample(const DevScene &S, const DevMaterial
             float A = (float)((double)et - ((double)B / 0.34522792));
             et = (float)((double)A + (double)B / pow((double)l, 2.0));
         }
+        // the refraction is spec_lobe's (pvol_spec_dev.h), written out: as a helper it moves shoot_kernel<4>'s spills (502 -> 500) and scratch
         if (!entering) { float t = ei; ei = et; et = t; }
         float sini2 = fmaxf(0.f, 1.f - wo.z * wo.z);
         float eta = ei / et;
@@ -258,7 +140,7 @@ __device__ __forceinline__ void bsdf_sample(const DevScene &S, const DevMaterial
     }
     if (*pdf == 0.f) { *fWhich = -1; return; }
     *sampledType = type;
-    *wiW = v3(sn.x * wi.x + tn.x * wi.y + nn.x * wi.z, sn.y * wi.x + tn.y * wi.y + nn.y * wi.z, sn.z * wi.x + tn.z * wi.y + nn.z * wi.z);
+    *wiW = to_world(fr, wi);
     if (matching > 1) *pdf /= matching;
     if (!(type & BSDF_SPECULAR)) {
         // reflection.cpp:583-592: f re-evaluated over the components on the sampled side; only the
@@ -298,16 +180,9 @@ __device__ __forceinline__ float light_emit(const DevScene &S, const DevShootSce
     }
     V3 ld = v3(l.dir[0], l.dir[1], l.dir[2]);
     V3 v1, v2;
-    if (fabsf(ld.x) > fabsf(ld.y)) {   // CoordinateSystem, geometry.h:508-519
-        float invLen = 1.f / sqrtf(ld.x * ld.x + ld.z * ld.z);
-        v1 = v3(-ld.z * invLen, 0.f, ld.x * invLen);
-    } else {
-        float invLen = 1.f / sqrtf(ld.y * ld.y + ld.z * ld.z);
-        v1 = v3(0.f, ld.z * invLen, -ld.y * invLen);
-    }
-    v2 = cross(ld, v1);
+    coordinate_system(ld, &v1, &v2);
     float dx, dy;
-    concentric_disk(u0, u1, &dx, &dy);
+    concentric_disk<false>(u0, u1, &dx, &dy);
     V3 wc = v3(H.worldCenter[0], H.worldCenter[1], H.worldCenter[2]);
     V3 Pdisk = wc + (v1 * dx + v2 * dy) * H.worldRadius;
     *o = Pdisk + ld * H.worldRadius;

@@ -20,39 +20,24 @@
 #ifndef PVOL_SPEC_DEV_H
 #define PVOL_SPEC_DEV_H
 
-
-__device__ __forceinline__ float spec_fresnel(float cosi, float eta_i, float eta_t) {   // FresnelDielectric::Evaluate, reflection.cpp:60-67,115-135
-    cosi = cosi < -1.f ? -1.f : (cosi > 1.f ? 1.f : cosi);
-    const bool entering = cosi > 0.f;
-    float ei = eta_i, et = eta_t;
-    if (!entering) { const float t = ei; ei = et; et = t; }
-    const float sint = ei / et * sqrtf(fmaxf(0.f, 1.f - cosi * cosi));
-    if (sint >= 1.f) return 1.f;
-    const float cost = sqrtf(fmaxf(0.f, 1.f - sint * sint));
-    const float ac = fabsf(cosi);
-    const float Rparl = ((et * ac) - (ei * cost)) / ((et * ac) + (ei * cost));
-    const float Rperp = ((ei * ac) - (et * cost)) / ((ei * ac) + (et * cost));
-    return (Rparl * Rparl + Rperp * Rperp) / 2.f;
-}
-
 struct SpecLobe { bool valid; V3 wi; float Fs, awz, g; };
 // BSDF::Sample_f(wo, &wi, BSDFSample, &pdf, lobe | BSDF_SPECULAR) on a glass hit and the test SpecularReflect / SpecularTransmit
 // make of the result (core/integrator.cpp:186,227: pdf > 0 && !f.IsBlack() && AbsDot(wi, n) != 0).  lobe: 1 reflection, 2 transmission.
-__device__ SpecLobe spec_lobe(const DevMaterial &m, const SurfHit &h, V3 woW, int lobe) {
+__device__ SpecLobe spec_lobe(const DevMaterial &m, const Hit &h, V3 woW, int lobe) {
     SpecLobe r;
     r.valid = false; r.wi = v3(0.f, 0.f, 0.f); r.Fs = 0.f; r.awz = 1.f; r.g = 0.f;
     const int want = (lobe == 1 ? BSDF_REFLECTION : BSDF_TRANSMISSION) | BSDF_SPECULAR;
     bool have = false;
     for (int i = 0; i < m.nBxdf; ++i) have = have || m.bxdfType[i] == want;   // GlassMaterial adds a lobe only for a non-black Kr / Kt (glass.cpp:52-57)
     if (!have) return r;
-    const V3 sn = normalize(h.dpdu);
-    const V3 tn = cross(h.nn, sn);
-    const V3 wo = v3(dot(woW, sn), dot(woW, tn), dot(woW, h.nn));
+    const BsdfFrame fr = bsdf_frame(h.nn, h.dpdu);
+    const V3 wo = to_local(fr, woW);
     V3 wi;
     if (lobe == 1) {
         wi = v3(-wo.x, -wo.y, wo.z);
-        r.Fs = spec_fresnel(wo.z, 1.f, m.ior);
+        r.Fs = fresnel_dielectric(wo.z, 1.f, m.ior);
     } else {
+        // the refraction of bsdf_sample (pvol_shoot.hip) at the plain index; written out on both sides, see there
         const bool entering = wo.z > 0.f;
         float ei = 1.f, et = m.ior;
         if (!entering) { const float t = ei; ei = et; et = t; }
@@ -63,10 +48,10 @@ __device__ SpecLobe spec_lobe(const DevMaterial &m, const SurfHit &h, V3 woW, in
         float cost = sqrtf(fmaxf(0.f, 1.f - sint2));
         if (entering) cost = -cost;
         wi = v3(eta * -wo.x, eta * -wo.y, cost);
-        r.Fs = 1.f - spec_fresnel(wo.z, 1.f, m.ior);
+        r.Fs = 1.f - fresnel_dielectric(wo.z, 1.f, m.ior);
     }
     r.awz = fabsf(wi.z);
-    r.wi = v3(sn.x * wi.x + tn.x * wi.y + h.nn.x * wi.z, sn.y * wi.x + tn.y * wi.y + h.nn.y * wi.z, sn.z * wi.x + tn.z * wi.y + h.nn.z * wi.z);
+    r.wi = to_world(fr, wi);
     const float ad = fabsf(dot(r.wi, h.nn));
     r.g = ad / 1.f;
     r.valid = r.Fs != 0.f && ad != 0.f;
@@ -83,7 +68,7 @@ struct SpecCtx {
 template <int D, class P> __device__ void spec_ray(const DevScene &S, SpecCtx &X, P &pol, V3 o, V3 d, float mint, int lobe, int mat, float Fs, float awz, float g);
 
 // PhotonIntegrator::Li at a hit of a ray of depth D: what it draws, and the rays it spawns
-template <int D, class P> __device__ void spec_surface(const DevScene &S, SpecCtx &X, P &pol, V3 d, const SurfHit &h) {
+template <int D, class P> __device__ void spec_surface(const DevScene &S, SpecCtx &X, P &pol, V3 d, const Hit &h) {
     const DevMaterial &m = S.shootScene->mats[h.mat];
     if (m.kind == PVOL_MATERIAL_MATTE) {
         X.pending += surf_count_draws(S, h, d, X.blackMask, D);
@@ -103,7 +88,7 @@ template <int D, class P> __device__ void spec_surface(const DevScene &S, SpecCt
 }
 
 template <int D, class P> __device__ void spec_ray(const DevScene &S, SpecCtx &X, P &pol, V3 o, V3 d, float mint, int lobe, int mat, float Fs, float awz, float g) {
-    SurfHit h;
+    Hit h;
     h.tri = 0; h.mat = 0; h.t = 0.f; h.rayEps = 0.f; h.p = h.nn = h.dpdu = v3(0.f, 0.f, 0.f);
     const bool hit = surf_closest(S, o, d, mint, &h);
     if (hit) spec_surface<D>(S, X, pol, d, h);

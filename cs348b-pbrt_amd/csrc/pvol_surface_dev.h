@@ -11,7 +11,7 @@
 //   sample = T * Lsurface + Lvi        (SamplerRenderer::Li, renderers/samplerrenderer.cpp:238-250)
 // Not covered (the host refuses such scenes when the surface integrator is on): specular BSDFs (the recursion of
 // SpecularReflect/Transmit), the final gather over an indirect map, VolumeGrid media (the shadow-ray tau() offset is a drawn value).
-#include "pvol_closest_dev.h"   // SurfHit, surf_closest, lane_occluded
+#include "pvol_closest_dev.h"   // Hit, surf_closest, lane_occluded
 #define SRF_AIM 1.6f    // the search ball is re-aimed at this multiple of nused photons for the sparsest sample of a cluster
 #define SRF_CAP 1024   // caustic bucket capacity (photons within the search ball + spread of a group's hit points).  Measured on the C2 frame with the
                        // scene's surface integrator on: 2048 -> 1 509 ms, 1024 -> 1 104 ms, 512 -> 3 580 ms; 640 with SRF_AIM 1.35: 1 278 ms: occupancy (LDS) against overflows
@@ -55,7 +55,7 @@ __device__ __forceinline__ SurfLight surf_light(const DevScene &S, int ln, V3 p,
 }
 
 // RandomUInt calls of PhotonIntegrator::Li for a ray of depth `depth` that hit h on a MATTE surface (in front of that ray's volume Li())
-__device__ uint32_t surf_count_draws(const DevScene &S, const SurfHit &h, V3 d, unsigned blackMask, int depth = 0) {
+__device__ uint32_t surf_count_draws(const DevScene &S, const Hit &h, V3 d, unsigned blackMask, int depth = 0) {
     const DevMaterial &m = S.shootScene->mats[h.mat];
     const bool lambert = m.kind == PVOL_MATERIAL_MATTE && m.nBxdf > 0;   // MatteMaterial::GetBSDF adds the Lambertian only for a non-black Kd
     const V3 wo = -d;
@@ -63,7 +63,7 @@ __device__ uint32_t surf_count_draws(const DevScene &S, const SurfHit &h, V3 d, 
     // one offset per unoccluded light sample, drawn by the shadow ray's Transmittance -- which returns 1 without drawing when the
     // scene has no volume region (photonvolume.cpp:18-26)
     if (S.volKind != PVOL_VOLUME_NONE) {
-        const V3 ng = surf_ng(S, h);
+        const V3 ng = hit_ng(S, h);
         for (int ln = 0; ln < S.nLights; ++ln) n += surf_light(S, ln, h.p, h.rayEps, ng, wo, lambert, blackMask).take ? 1u : 0u;
     }
     if (S.surf.map[SURF_MAP_CAUSTIC].nPhotons > 0u && lambert) n += 144u;    // LPhoton(causticMap): two BSDF::rho(wo, rng)
@@ -156,7 +156,7 @@ __device__ __attribute__((noinline)) void caustic_stream(const DevSurfMap &M, fl
                 const f4 wi4 = M.wi4[start + i];
                 if (Nf.x * wi4.x + Nf.y * wi4.y + Nf.z * wi4.z > 0.f) {
                     const float sW = 1.f - d2 / r2;
-                    const float wgt = (3.f * 0.31830988618379067154f * sW * sW) * norm;
+                    const float wgt = (3.f * K_INV_PI * sW * sW) * norm;
                     const float4 *row = M.alpha4 + (size_t)(start + i) * 8;
 #pragma unroll
                     for (int qq = 0; qq < 8; ++qq) {
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
         const bool have = ri < A.nRays;
         const pvol_ray pr = A.rays[have ? ri : 0];
         const V3 o = v3(pr.o[0], pr.o[1], pr.o[2]), d = v3(pr.d[0], pr.d[1], pr.d[2]);
-        SurfHit h;
+        Hit h;
         h.tri = 0; h.mat = 0; h.t = 0.f; h.rayEps = 0.f; h.p = h.nn = h.dpdu = v3(0.f, 0.f, 0.f);
         // (the ray's maxt is this very t: the tile pre-pass clipped it; an unused slot of the segment pool has maxt < mint)
         const bool hit = have && pr.maxt >= pr.mint && surf_closest(S, o, d, pr.mint, &h);
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
         const V3 wo = -d;
         // ---- direct lighting: Ld = f * Li * (AbsDot(wi, n) / pdf), Li = light radiance * Transmittance of the shadow ray
         if (lambert) {
-            const V3 ng = surf_ng(S, h);
+            const V3 ng = hit_ng(S, h);
             for (int ln = 0; ln < S.nLights; ++ln) {
                 const SurfLight sl = surf_light(S, ln, h.p, h.rayEps, ng, wo, true, blackMask);
                 if (!sl.take) continue;
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                 for (int b = 0; b < 30; ++b) {
                     const float sT = S.sigA[b] + S.sigS[b];
                     const float Li = (S.lights[ln].intensity[b] * sl.scale) * __builtin_amdgcn_exp2f(sT * kSh);
-                    Ls[b] += (mat.kd[b] * 0.31830988618379067154f) * Li * geo;
+                    Ls[b] += (mat.kd[b] * K_INV_PI) * Li * geo;
                 }
             }
         }
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                 caustic_stream(M, maxDistSq, cg, c, dot(lane_v3(h.nn, pivLane), lane_v3(wo, pivLane)) < 0.f ? lane_v3(h.nn, pivLane) * -1.f : lane_v3(h.nn, pivLane), k, lane, sa);
                 if (need) {
 #pragma unroll
-                    for (int b = 0; b < 30; ++b) Ls[b] += sa[b] * mat.kd[b] * 0.31830988618379067154f;
+                    for (int b = 0; b < 30; ++b) Ls[b] += sa[b] * mat.kd[b] * K_INV_PI;
                 }
             } else {
                 // pass A: how many photons lie inside maxdist (kdtree.h:180: dist2 < maxDistSquared), and -- when that is at least
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                                 if (served && bits == kth && tieQuota > 0) { mem = true; --tieQuota; }
                             }
                             const float sW = 1.f - d2 / r2;
-                            float wgt = (3.f * 0.31830988618379067154f * sW * sW) * norm;
+                            float wgt = (3.f * K_INV_PI * sW * sW) * norm;
                             if (!mem || !(Nf.x * wi4.x + Nf.y * wi4.y + Nf.z * wi4.z > 0.f)) wgt = 0.f;
                             if (u) w1[t] = wgt; else w0[t] = wgt;
                         }
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(LANES, 2) void surface_kernel(SurfArgs A) {   // 25
                     acc[8 * (b >> 2) + 4 + (b & 3)] = __uint_as_float(r[1]);
                 }
 #pragma unroll
-                for (int b = 0; b < 30; ++b) Ls[b] += acc[b] * mat.kd[b] * 0.31830988618379067154f;   // Lr * rho(wo) * INV_PI, rho == Kd
+                for (int b = 0; b < 30; ++b) Ls[b] += acc[b] * mat.kd[b] * K_INV_PI;   // Lr * rho(wo) * INV_PI, rho == Kd
             }
         }
         if (mi) RtryMap[1] = Rtry; else RtryMap[0] = Rtry;

@@ -288,7 +288,7 @@ struct SpecEmitPol {
 // What PhotonIntegrator::Li draws for a camera sample whose ray hit `sh` (in front of the sample's own volume Li()), the
 // segments of a specular hit laid out on the way.  Returns the draw count; *link = (first segment << 6) | count.
 template <bool SPEC>
-__device__ uint32_t tile_surface_draws(const DevScene &S, const TileArgs &T, const CountConsts &CC, const float *ltri, const float *trows, const SurfHit &sh,
+__device__ uint32_t tile_surface_draws(const DevScene &S, const TileArgs &T, const CountConsts &CC, const float *ltri, const float *trows, const Hit &sh,
                                        V3 d, float su, float tm, size_t ri, bool blackS, bool lightBlack, unsigned blackMask, DevCounters *counters, uint32_t *link) {
     *link = 0u;
     if (!SPEC || S.shootScene->mats[sh.mat].kind == PVOL_MATERIAL_MATTE || !T.specOn) return surf_count_draws(S, sh, d, blackMask);
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
                 if (!PLAIN && S.nSpheres) { V3 ph; spheres_closest(S, o, d, 0.f, &maxt, &ph); }
                 uint32_t link = 0u;
                 if (surfOn && maxt < INFINITY) {
-                    SurfHit sh;
+                    Hit sh;
                     if (surf_closest(S, o, d, 0.f, &sh)) {
                         if (!FUSED) surfDraws = tile_surface_draws<SPEC>(S, T, CC, ltri, trows, sh, d, su, tm, ri, blackS, lightBlack, blackMask, A.counters, &link);
                         else if (!SPEC || S.shootScene->mats[sh.mat].kind == PVOL_MATERIAL_MATTE || !T.specOn) surfDraws = surf_count_draws(S, sh, d, blackMask);
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(LANES, FUSED ? 2 : 4) void tile_kernel(LiArgs A, Ti
                             walked = true;
                             const unsigned long long t0 = rng.draws;
                             const V3 oj = v3(pr.o[0], pr.o[1], pr.o[2]), dj = v3(pr.d[0], pr.d[1], pr.d[2]);
-                            SurfHit shj;
+                            Hit shj;
                             shj.tri = 0; shj.mat = 0; shj.t = 0.f; shj.rayEps = 0.f; shj.p = shj.nn = shj.dpdu = v3(0.f, 0.f, 0.f);
                             surf_closest(S, oj, dj, 0.f, &shj);   // lane j found this hit above; every lane repeats it (wave-uniform)
                             SpecCtx X;
@@ -619,7 +619,7 @@ __global__ __launch_bounds__(LANES * NW, (NW >= 8 ? 4 : 2)) void tile_mw_kernel(
                 const size_t ri = (size_t)st.first_ray + k + i;
                 uint32_t link = 0u;
                 if (surfOn && maxt < INFINITY) {
-                    SurfHit sh;
+                    Hit sh;
                     if (surf_closest(S, o, d, 0.f, &sh)) surfDraws = tile_surface_draws<SPEC>(S, T, CC, ltri, trows, sh, d, su, tm, ri, blackS, lightBlack, blackMask, A.counters, &link);
                 }
                 if (!PLAIN && T.specLink) T.specLink[ri] = link;

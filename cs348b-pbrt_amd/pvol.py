@@ -437,8 +437,8 @@ class PhotonVolume:
 
     def probe_hits(self, rays, mode):
         """The tests' ray probe (csrc/pvol_probe.hip, not part of the ABI): rays (RAY_DTYPE) through the device's own hit routines on
-        the uploaded scene -- mode 0 surf_closest, 1 lane_occluded, 2 scene_occluded (one ray per wave).  Returns (f, i): f[n, 11] =
-        t, rayEps, p, nn, dpdu; i[n, 3] = hit flag, primitive (triangle index in upload order, -1 - k for sphere k), material."""
+        the uploaded scene -- mode 0 surf_closest, 1 lane_occluded, 2 scene_occluded (one ray per wave), 3 scene_closest (the photon
+        shooter's closest hit, one ray per wave, maxt = inf; the record of mode 0).  Returns (f, i): f[n, 11] = t, rayEps, p, nn, dpdu; i[n, 3] = hit flag, primitive (triangle index in upload order, -1 - k for sphere k), material."""
         assert rays.dtype == abi.RAY_DTYPE
         rays = np.ascontiguousarray(rays)
         f = np.zeros((len(rays), 11), np.float32)

@@ -1,6 +1,6 @@
 """The device's hit routines ray by ray.  pvol_probe_hits (csrc/pvol_probe.hip, a test entry outside the ABI) hands
-chosen rays to the very functions the kernels call -- surf_closest (mode 0), lane_occluded (1), scene_occluded (2) -- on the uploaded
-scene.  Every answer is held to the oracle's scan, which tests/test_hit_records.py holds bit for bit to the reference's records of the
+chosen rays to the very functions the kernels call -- surf_closest (mode 0), lane_occluded (1), scene_occluded (2), the shooter's
+scene_closest (3) -- on the uploaded scene.  Every answer is held to the oracle's scan, which tests/test_hit_records.py holds bit for bit to the reference's records of the
 same rays (tests/golden/hits_*.bin).  Bit-equal: flags, primitive, material, t, rayEps, p, dpdu and a triangle's nn -- all fp32
 + - x / sqrt under -ffp-contract=off.  A sphere's nn goes through acos / sin (rounded doubles on the device, acosf / sinf on the host):
 2e-5 per component, the project's bar for directions behind a sphere."""
@@ -71,6 +71,7 @@ def _keep(mask, rays, *records):
     return ({k: v[mask] for k, v in rays.items() if isinstance(v, np.ndarray)},) + tuple((f[mask], i[mask]) for f, i in records)
 
 
+ZERO_TIES = {"trizoo": 19}   # fixture rays on which scene_closest's scan reports t = -0 and surf_closest's +0 (see the mode 3 test)
 FAR_LIMIT = 32.0   # scene diagonals up to which no ray of the far-origin class is beyond the limit above (CPU model)
 
 
@@ -89,7 +90,7 @@ def _fixture_probe(pvol, scene_name, mode):
         pv = _context(pvol, load_scene(scene_name))
         try:
             assert (pv.accel_info()[0] > 0) == (scene_name == "trizoo_h")
-            for m in (0, 1, 2):
+            for m in (0, 1, 2, 3):
                 _PROBE[(scene_name, m)] = pv.probe_hits(_pvol_rays(rays), m)
         finally:
             pv.close()
@@ -120,15 +121,51 @@ def test_probe_equals_the_oracle_on_every_fixture_class(pvol, orc, scene_name):
         assert (gf == 0).all() and (gi[:, 1:] == 0).all()
 
 
-@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("scene_name", SCENES)
+def test_wave_closest_hit_equals_lane_closest_hit_on_every_fixture_ray(pvol, scene_name):
+    """Mode 3 (scene_closest, the photon shooter's: one ray per wave, a triangle per lane, minimum over the wave) against mode 0
+    (surf_closest, one ray per lane, serial scan): the 11 floats and 3 ints byte for byte on every ray of the fixture -- the tie class
+    (both take the later triangle), the axis-aligned and the far-origin classes, and the sphere hits (both go through the same
+    sphere_dg).  Mode 0 is held to the oracle above, so this holds mode 3 to it on the same rays.
+
+    One class is excluded from BYTE equality, found by this test and as old as the shooter (scene_closest is the parent's text): a
+    tie at t = 0 between zeros of opposite sign.  A ray that starts on a shared edge with mint = 0 gets t = +0 from one triangle and
+    -0 from another; the serial scan keeps the later triangle's own t, the wave scan's t is -max(-t) over the wave, which is -0 as soon
+    as any tied lane holds -0.  Same triangle, same material, p, nn, dpdu; t and rayEps = 1e-3 t carry the other zero.  19 of trizoo's
+    7 247 rays (0.26 %, classes 98 / 99), none in spherezoo, none in trizoo_h (the hierarchy walk has no wave minimum).  Those rays
+    must still be equal as numbers, hit at t == 0, and be exactly that many."""
+    rays, _, _ = load_hits(scene_name)
+    (wf, wi), (lf, li) = _fixture_probe(pvol, scene_name, 3), _fixture_probe(pvol, scene_name, 0)
+    assert wf.shape == lf.shape == (len(rays["mint"]), 11) and wi.shape == li.shape == (len(rays["mint"]), 3)
+    differ = (bits(wf) != bits(lf)).any(1) | (wi != li).any(1)
+    zero_tie = differ & (li[:, 0] > 0) & (lf[:, 0] == 0) & (wf == lf).all(1) & (wi == li).all(1)   # only the sign of a zero
+    bad = np.flatnonzero(differ & ~zero_tie)
+    print("%s: %d rays, %d hits (%d on spheres), %d differ, %d of them in the sign of zero of a tie at t = 0" % (
+        scene_name, len(li), (li[:, 0] > 0).sum(), ((li[:, 0] > 0) & (li[:, 1] < 0)).sum(), differ.sum(), zero_tie.sum()))
+    assert zero_tie.sum() == ZERO_TIES.get(scene_name, 0) <= len(li) // 100
+    assert np.isin(rays["cls"][zero_tie], (98, 99)).all()
+    assert len(bad) == 0, "%d rays; first: %s\n wave %r %r\n lane %r %r" % (
+        len(bad), first_ray(rays, bad[0]), wf[bad[0]].tolist(), wi[bad[0]].tolist(), lf[bad[0]].tolist(), li[bad[0]].tolist())
+    assert (li[:, 0] > 0).sum() >= 100   # the fixture does hit things
+    if scene_name == "spherezoo":
+        assert ((li[:, 0] > 0) & (li[:, 1] < 0)).sum() >= 100
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
 def test_hierarchy_equals_scan_on_the_device_itself(pvol, orc, mode):
     """trizoo_h is trizoo's 55 triangles, in the same order, plus far-away filler: the device walks its hierarchy there and scans
     here.  Bit for bit on every ray, the far-origin (3, 30, 300 diagonals) and the axis-aligned classes included -- but for the rays
-    of the stated limit (outside_own_box: 4 of the 100 at 300 diagonals, all `hits` of the sliver beside itself; none at 3 and 30)."""
+    of the stated limit (outside_own_box: 4 of the 100 at 300 diagonals, all `hits` of the sliver beside itself; none at 3 and 30).
+    Mode 3 (scene_closest): also but for the 19 zero ties of its scan (ZERO_TIES), equal as numbers and counted."""
     rays, _, _ = load_hits("trizoo")
     (hf, hi), (sf, si) = _fixture_probe(pvol, "trizoo_h", mode), _fixture_probe(pvol, "trizoo", mode)
     limit = _fixture_limit(orc, rays)
-    bad = np.flatnonzero(~limit & ((bits(hf) != bits(sf)).any(1) | (hi != si).any(1)))
+    differ = (bits(hf) != bits(sf)).any(1) | (hi != si).any(1)
+    if mode == 3:
+        zero_tie = differ & (hi[:, 0] > 0) & (hf[:, 0] == 0) & (hf == sf).all(1) & (hi == si).all(1)
+        assert zero_tie.sum() == ZERO_TIES["trizoo"]
+        differ &= ~zero_tie
+    bad = np.flatnonzero(~limit & differ)
     assert len(bad) == 0, "%d rays; first: %s hierarchy %r %r scan %r %r" % (
         len(bad), first_ray(rays, bad[0]), hf[bad[0]].tolist(), hi[bad[0]].tolist(), sf[bad[0]].tolist(), si[bad[0]].tolist())
     for c in (22, 25):
@@ -222,7 +259,7 @@ def test_two_thousand_rays_on_36k_triangles_equal_the_oracle(pvol, orc):
 # ------------------------------------------------------------------------------------------------ the shipped paths on the new scenes
 @pytest.mark.parametrize("scene_name", ["spherezoo", "trizoo_h"])
 def test_device_shooter_matches_oracle_shooter_on_the_zoos(pvol, orc, scene_name):
-    """scene_closest, the shooter's wave-cooperative closest hit, is the one routine the probe cannot call: 2 000 photons, photon for
+    """scene_closest, the shooter's wave-cooperative closest hit (probe mode 3), inside the shooter itself: 2 000 photons, photon for
     photon at the tolerances of test_device_shooter_matches_oracle_shooter, the integer counters exactly."""
     from test_gpu_shooter import _shoot_both
     ref, rst, got, gst, pv, o, s, p = _shoot_both(pvol, orc, scene_name, 2000, 8)
@@ -304,7 +341,7 @@ def test_probe_argument_checks(pvol):
         assert L.pvol_probe_hits(pv._h, rays.ctypes.data, 2, 0, None, ip) == abi.PVOL_E_INVALID
         assert L.pvol_probe_hits(pv._h, rays.ctypes.data, 2, 0, fp, None) == abi.PVOL_E_INVALID
         assert L.pvol_probe_hits(pv._h, rays.ctypes.data, 0, 0, fp, ip) == abi.PVOL_E_INVALID
-        for mode in (-1, 3):
+        for mode in (-1, 4):
             assert L.pvol_probe_hits(pv._h, rays.ctypes.data, 2, mode, fp, ip) == abi.PVOL_E_INVALID
         assert (f == 0).all() and (i == 0).all()
         assert L.pvol_probe_hits(pv._h, rays.ctypes.data, 2, 0, fp, ip) == 0
