@@ -14,6 +14,8 @@
 
 #include "pvol_host.h"
 
+const char *pvol_env_get(const char *name) { return getenv(name); }   // what every read point of pvol_env.h is given
+
 extern "C" {
 
 int pvol_abi_version(void) { return PVOL_ABI_VERSION; }
@@ -65,19 +67,8 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     pvol_ctx *c = new (std::nothrow) pvol_ctx();
     if (!c) return PVOL_E_NO_MEMORY;
     c->params = *params;
-    { const char *fs = getenv("PVOL_FORCE_SEQ"); c->forceSeq = fs && fs[0] == '1'; }
-    { const char *ng = getenv("PVOL_NO_GROUP"); c->noGroup = ng && ng[0] == '1'; }
-    { const char *nl = getenv("PVOL_NO_LITE"); c->noLite = nl && nl[0] == '1'; }
-    { const char *nm = getenv("PVOL_NO_MOMENTS"); c->noMoments = nm && nm[0] == '1'; }
-    { const char *ns = getenv("PVOL_LPHOTON_NO_SORT"); c->lpNoSort = ns && ns[0] == '1'; }
-    c->groupPrecore = pvol_precore_kappa(getenv("PVOL_GROUP_PRECORE"));
-    { const char *tg = getenv("PVOL_TILE_GENERAL"); c->tileGeneral = tg && tg[0] == '1'; }
-    { const char *gw = getenv("PVOL_GROUP_WAVES"); if (gw) c->groupWavesPerCU = std::max(1, atoi(gw)); }
-    { const char *tw = getenv("PVOL_TILE_WAVES"); if (tw) c->tileWaves = std::max(0, atoi(tw)); }
-    // li_fixup_kernel / li_fixup_group_kernel waves per CU (C3, 8 spp frame: 16.3 s at 8, 13.9 s at 16)
-    { const char *fw = getenv("PVOL_FIX_WAVES"); if (fw) c->fixWavesPerCU = std::max(1, atoi(fw)); }
-    // PVOL_LI_COALESCE=<max_batch>: the default of pvol_set_li_coalescing, for callers that cannot call it (an unchanged binding)
-    { const char *lc = getenv("PVOL_LI_COALESCE"); const long v = lc ? atol(lc) : 0; c->coMaxBatch = (v > 1 && v <= PVOL_LI_MAX_BATCH) ? (uint32_t)v : 0u; }
+    c->knobs = pvol_env_context(pvol_env_get);
+    c->co.maxBatch = pvol_env_li_coalesce(pvol_env_get);
     { hipDeviceProp_t prop; if (ok(hipGetDeviceProperties(&prop, params->device))) c->nCU = prop.multiProcessorCount; }
     if (!c->ds.alloc(1) || !c->dCounters.alloc(1) || !c->dWords.alloc(4) || !c->dsh.alloc(1) ||
         !ok(hipMemset(c->dCounters.get(), 0, sizeof(DevCounters)))) {
@@ -88,16 +79,12 @@ int pvol_create(const pvol_params *params, pvol_ctx **out) {
     return PVOL_OK;
 }
 
-// every device allocation of the context is held by an owner (pvol_host.h): deleting the context frees them
+// Every allocation, event and stream of the context is held by an owner (pvol_host.h): deleting the context frees them.  The order
+// of the members does not matter: after the device-wide synchronise nothing of the context is in flight.
 void pvol_destroy(pvol_ctx *c) {
     if (!c) return;
     hipSetDevice(c->params.device);
     hipDeviceSynchronize();
-    for (auto &p : c->pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-    for (auto &p : c->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-    for (auto &p : c->phaseMarks) hipEventDestroy(p.second);
-    for (auto &e : c->phasePool) hipEventDestroy(e);
-    pvol_free_li_staging(c);
     delete c;
 }
 
@@ -275,14 +262,7 @@ int pvol_moment_gate(const float *sigA, const float *sigS, double pathBound) {
 }
 
 float pvol_precore_bound(float theta, float rho) { return precore_bound(theta, rho); }
-// PVOL_GROUP_PRECORE: unset or unreadable = the default, 0 = the rule off; a kappa above 1 would put theta beyond the guess itself
-float pvol_precore_kappa(const char *env) {
-    if (!env || !env[0]) return PVOL_PRECORE_DEFAULT;
-    char *end = 0;
-    const float v = strtof(env, &end);
-    if (end == env || !(v >= 0.f)) return PVOL_PRECORE_DEFAULT;
-    return std::min(v, 1.f);
-}
+float pvol_precore_kappa(const char *env) { return env_precore_kappa(env); }
 
 // The longest main diagonal of the medium's extent in world space (the inverse of w2v's linear part applied to the box's edges): no
 // segment inside the medium is longer.  INFINITY where w2v is projective or singular.
@@ -346,16 +326,13 @@ int pvol_moment_scene(DevScene &h, MomentWeights *wts) {
     return terms;
 }
 
-LaunchKnobs pvol_read_knobs() {
-    auto num = [](const char *name) { const char *v = getenv(name); return v ? (int64_t)atoll(v) : (int64_t)0; };
-    auto real = [](const char *name) { const char *v = getenv(name); return v ? (float)atof(v) : 0.f; };
-    LaunchKnobs k;
-    k.sliceRays = num("PVOL_SLICE_RAYS"); k.specPool = num("PVOL_SPEC_POOL"); k.tileBatchRays = num("PVOL_TILE_BATCH_RAYS");
-    // li_group_kernel bucket radius^2 = this x the guessed k-th distance^2 (measured at 64 spp: 1.3 55.5, 1.2 57.5, 1.12 58.0,
-    // 1.06 56.6, 1.0 51.0 Msamples/s)
-    k.groupGuess = real("PVOL_GROUP_GUESS"); if (!(k.groupGuess >= 1.f)) k.groupGuess = 1.15f;
-    k.fxgWiden = real("PVOL_FXG_WIDEN"); k.fxgAim = real("PVOL_FXG_AIM"); k.fixExact = getenv("PVOL_FIX_EXACT") != 0;
-    return k;
+LaunchKnobs pvol_read_knobs() { return pvol_env_launch(pvol_env_get); }
+// every read point of pvol_env.h over the caller's table (a name that is not in it is unset) instead of the process environment
+void pvol_env_parse(const char *const *names, const char *const *values, uint32_t n, EnvKnobs *out) {
+    *out = pvol_env_all([&](const char *name) -> const char * {
+        for (uint32_t i = 0; i < n; ++i) if (!strcmp(names[i], name)) return values[i];
+        return 0;
+    });
 }
 
 // Whether a single march step can reach the Russian roulette (Tr.y() < 1e-3, photonvolume.cpp:156-161): Tr is
@@ -375,11 +352,12 @@ static PlanIn plan_input(const pvol_ctx *c, const BatchArgs &b) {
     PlanIn in = {};
     in.nLights = h.nLights; in.volKind = h.volKind; in.g = h.g; in.nPhotons = h.nPhotons; in.nUsed = h.nUsed; in.candCap = h.candCap;
     in.maxSteps = h.maxSteps; in.nTris = h.nTris; in.roulette = roulette_possible(c); in.distant = h.nLights > 0 && h.lights[0].kind == PVOL_LIGHT_DISTANT;
-    in.forceSeq = c->forceSeq; in.noGroup = c->noGroup; in.noLite = c->noLite; in.statsOn = c->statsOn;
-    in.nCU = c->nCU; in.groupWavesPerCU = c->groupWavesPerCU; in.fixWavesPerCU = c->fixWavesPerCU; in.tileWaves = c->tileWaves;
+    const CtxKnobs &k = c->knobs;
+    in.forceSeq = k.forceSeq; in.noGroup = k.noGroup; in.noLite = k.noLite; in.statsOn = c->statsOn;
+    in.nCU = c->nCU; in.groupWavesPerCU = k.groupWavesPerCU; in.fixWavesPerCU = k.fixWavesPerCU; in.tileWaves = k.tileWaves;
     in.nRays = b.nRays; in.nStreams = b.nStreams; in.maxRays = b.maxRaysPerStream; in.hasInit = b.initState != 0; in.transOnly = b.transOnly != 0; in.hasTile = b.tile != 0;
     in.spp = b.tile ? b.tile->spp : 0; in.specOn = b.tile && b.tile->specOn; in.hasTauOut = b.tauOut != 0;
-    in.momentTerms = (int16_t)(h.mom ? c->momentTerms : 0); in.outXYZ = b.outputKind == PVOL_OUT_XYZ; in.noMoments = c->noMoments;
+    in.momentTerms = (int16_t)(h.mom ? c->momentTerms : 0); in.outXYZ = b.outputKind == PVOL_OUT_XYZ; in.noMoments = k.noMoments;
     in.knobs = pvol_read_knobs();
     return in;
 }
@@ -395,49 +373,51 @@ bool pvol_reserve(DevBuf &b, size_t want, hipStream_t stream) {
 
 // Timing events: every batch records a pair on its launch stream.  Finished pairs are folded into the running sum and
 // recycled here, at the next launch and in pvol_kernel_time_ms, so the list stays short however many batches a caller
-// issues without ever asking for the time (the per-sample shim issues one per camera sample).  Caller holds c->mu.
-static bool harvest_events(pvol_ctx *c, bool wait) {
+// issues without ever asking for the time (the per-sample shim issues one per camera sample).  Caller holds t.mu.
+static bool harvest_events(BatchTimer &t, bool wait) {
     size_t keep = 0;
-    for (size_t i = 0; i < c->pending.size(); ++i) {
-        std::pair<hipEvent_t, hipEvent_t> p = c->pending[i];
+    for (size_t i = 0; i < t.pending.size(); ++i) {
+        BatchTimer::Pair &p = t.pending[i];
         // more than 64 batches in flight: wait for the oldest instead of growing
-        const bool block = wait || c->pending.size() - i > 64;
-        hipError_t q = block ? hipEventSynchronize(p.second) : hipEventQuery(p.second);
+        const bool block = wait || t.pending.size() - i > 64;
+        hipError_t q = block ? hipEventSynchronize(p.second.get()) : hipEventQuery(p.second.get());
         if (q == hipSuccess) {
             float ms = 0.f;
-            if (ok(hipEventElapsedTime(&ms, p.first, p.second))) { c->timeMs += ms; c->launches += 1; }
-            c->pool.push_back(p);
+            if (ok(hipEventElapsedTime(&ms, p.first.get(), p.second.get()))) { t.timeMs += ms; t.launches += 1; }
+            t.pool.push_back(std::move(p));
         } else if (q == hipErrorNotReady) {
-            c->pending[keep++] = p;
+            t.pending[keep++] = std::move(p);
         } else {
             (void)hipGetLastError();
-            c->pool.push_back(p);
-            if (wait) { c->pending.erase(c->pending.begin(), c->pending.begin() + (i + 1 - keep)); return false; }
+            t.pool.push_back(std::move(p));
+            if (wait) { t.pending.erase(t.pending.begin(), t.pending.begin() + (i + 1 - keep)); return false; }
         }
     }
-    c->pending.resize(keep);
+    t.pending.resize(keep);
     return true;
 }
 
 // Orders `stream` behind every batch of this context still running on another stream (their end events): the device entry
 // points return with their kernels in flight, and those kernels use the context's scratch (dWords and `buf`).
 int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream) {
-    std::lock_guard<std::mutex> g(c->mu);
-    harvest_events(c, false);
-    for (const auto &p : c->pending)
-        if (!ok(hipStreamWaitEvent(stream, p.second, 0))) return PVOL_E_NO_DEVICE;
+    std::lock_guard<std::mutex> g(c->timer.mu);
+    harvest_events(c->timer, false);
+    for (const auto &p : c->timer.pending)
+        if (!ok(hipStreamWaitEvent(stream, p.second.get(), 0))) return PVOL_E_NO_DEVICE;
     return PVOL_OK;
 }
 
-// Phase timing (off by default: two events per kernel group otherwise).  A mark is an event on the launch stream.
+// Phase timing (off by default: two events per kernel group otherwise).  A mark is an event on the launch stream; a mark whose
+// event cannot be created is dropped.
 void pvol_phase_mark(pvol_ctx *c, hipStream_t stream, int id) {
-    if (!c->phaseOn) return;
-    std::lock_guard<std::mutex> g(c->mu);
-    hipEvent_t e;
-    if (!c->phasePool.empty()) { e = c->phasePool.back(); c->phasePool.pop_back(); }
-    else if (!ok(hipEventCreate(&e))) return;
-    hipEventRecord(e, stream);
-    c->phaseMarks.push_back(std::make_pair(id, e));
+    PhaseTimer &ph = c->phases;
+    if (!ph.on) return;
+    std::lock_guard<std::mutex> g(c->timer.mu);
+    DevEvent e;
+    if (!ph.pool.empty()) { e = std::move(ph.pool.back()); ph.pool.pop_back(); }
+    else if (!e.create(true)) return;
+    hipEventRecord(e.get(), stream);
+    ph.marks.emplace_back(id, std::move(e));
 }
 
 // ---- specular recursion (pvol_spec_dev.h): the pool of segment rays of one batch (COUNT mode) or one slice (FUSED mode).
@@ -486,11 +466,11 @@ static int run_tile_count(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, c
     TilePlainIn g = {};
     g.tile = p.tile; g.volKind = h.volKind; g.nLights = h.nLights; g.light0Kind = h.nLights > 0 ? h.lights[0].kind : -1;
     g.hasBvh = h.bvhNodes != 0; g.nSpheres = h.nSpheres; g.nTris = h.nTris; g.surfOn = h.surf.enabled != 0;
-    g.specLink = tile->specOn || tile->specLink != 0; g.tileGeneral = c->tileGeneral;
+    g.specLink = tile->specOn || tile->specLink != 0; g.tileGeneral = c->knobs.tileGeneral;
     const bool plain = pvol_tile_plain_gate(&g) != 0;
     c->lastTileForm = plain ? "plain" : "general";
     // the plan's wave count is the general form's; PLAIN has its own optimum (the LDS plan, p.ldsTile, is the same for every wave count)
-    const int waves = plain ? tile_waves_per_task_plain(b.nStreams, c->nCU, c->tileWaves) : p.tileWavesPerTask;
+    const int waves = plain ? tile_waves_per_task_plain(b.nStreams, c->nCU, c->knobs.tileWaves) : p.tileWavesPerTask;
     return ok(pvol_launchers(h.volKind).tile(&t, tile, false, p.ldsTile, h.candCap, b.stream, waves, plain, &c->lastTileKernel)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 static int run_par(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a) {
@@ -554,18 +534,16 @@ int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
     BatchPlan p = plan_path(in);
     if (p.rc != PVOL_OK) return p.rc;
     const hipStream_t stream = b.stream;
-    std::pair<hipEvent_t, hipEvent_t> ev;
+    BatchTimer &timer = c->timer;
+    BatchTimer::Pair taken;
     {
-        std::lock_guard<std::mutex> g(c->mu);
-        harvest_events(c, false);
-        if (!c->pool.empty()) { ev = c->pool.back(); c->pool.pop_back(); }
-        else if (!ok(hipEventCreate(&ev.first)) || !ok(hipEventCreate(&ev.second))) return PVOL_E_NO_DEVICE;
+        std::lock_guard<std::mutex> g(timer.mu);
+        harvest_events(timer, false);
+        if (!timer.pool.empty()) { taken = std::move(timer.pool.back()); timer.pool.pop_back(); }
+        else if (!taken.first.create(true) || !taken.second.create(true)) return PVOL_E_NO_DEVICE;
     }
-    // the pair goes back to the pool on every early return below (a failed batch must not leak events)
-    struct EventReturn {
-        pvol_ctx *c; std::pair<hipEvent_t, hipEvent_t> ev; bool keep = false;
-        ~EventReturn() { if (!keep) { std::lock_guard<std::mutex> g(c->mu); c->pool.push_back(ev); } }
-    } evGuard{c, ev};
+    BatchTimer::Lease lease{timer, std::move(taken)};   // back to the pool on every early return below
+    const BatchTimer::Pair &ev = lease.ev;
     if (p.path == PVOL_PATH_SLICED && in.maxRays == 0) {   // device entry point: the stream table lives on the device
         std::vector<pvol_stream> hs(b.nStreams);   // read on the caller's stream: ordered behind whatever produced the table
         if (!ok(hipMemcpyAsync(hs.data(), b.streams, sizeof(pvol_stream) * (size_t)b.nStreams, hipMemcpyDeviceToHost, stream)) ||
@@ -583,7 +561,7 @@ int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
     a.out = b.out; a.draws = b.draws; a.initState = b.initState; a.finalState = b.finalState; a.counters = c->dCounters.get();
     a.transmittanceOnly = b.transOnly; a.chunkCounter = c->dWords.get(); a.needSeq = c->dWords.get() + 1; a.gated = 0;
     a.tauOut = b.tauOut; a.status = b.status; a.grpGuess = in.knobs.groupGuess; a.moments = p.groupForm == GRP_FORM_MOMENTS;
-    a.grpPrecore = c->groupPrecore;
+    a.grpPrecore = c->knobs.groupPrecore;
     if (p.groupForm) {
         a.defer = pvol_buf<DeferRec>(c, PVOL_BUF_DEFER); a.deferCount = c->dWords.get() + 2;
         a.deferCap = (uint32_t)std::min<size_t>(c->buf[PVOL_BUF_DEFER].bytes / sizeof(DeferRec), 0xffffffffu);
@@ -596,15 +574,13 @@ int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
         if (rc == PVOL_OK) rc = run_tile_count(c, b, p, a, &tile);
         if (rc != PVOL_OK) return rc;
     }
-    hipEventRecord(ev.first, stream);
+    hipEventRecord(ev.first.get(), stream);
     pvol_phase_mark(c, stream, PVOL_PHASE_MARCH);
     rc = p.path == PVOL_PATH_PAR ? run_par(c, b, p, a) : p.path == PVOL_PATH_SLICED ? run_sliced(c, b, p, a, &tile) : run_seq(c, b, p, a);
     if (rc != PVOL_OK) return rc;
-    hipEventRecord(ev.second, stream);
+    hipEventRecord(ev.second.get(), stream);
     pvol_phase_mark(c, stream, PVOL_PHASE_END);
-    std::lock_guard<std::mutex> g(c->mu);
-    c->pending.push_back(ev);
-    evGuard.keep = true;
+    lease.done = true;   // to `pending`
     return PVOL_OK;
 }
 
@@ -686,7 +662,7 @@ int pvol_transmittance_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, 
 int pvol_li(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T) {
     if (!c || !ray || !mt || !mti || !Lv || !T) return PVOL_E_INVALID;
     if (*mti < 0 || *mti > 624) return PVOL_E_INVALID;
-    if (c->coMaxBatch.load(std::memory_order_relaxed) > 1) return pvol_li_coalesced(c, ray, mt, mti, Lv, T);   // pvol_li_coalesce.hip
+    if (c->co.maxBatch.load(std::memory_order_relaxed) > 1) return pvol_li_coalesced(c, ray, mt, mti, Lv, T);   // pvol_li_coalesce.hip
     return pvol_li_lone(c, ray, mt, mti, Lv, T);
 }
 
@@ -736,33 +712,35 @@ const char *pvol_tile_form_name(pvol_ctx *c) { return c ? c->lastTileForm : ""; 
 
 int pvol_enable_phase_timing(pvol_ctx *c, int on) {
     if (!c) return PVOL_E_INVALID;
-    c->phaseOn = on != 0;
+    c->phases.on = on != 0;
     return PVOL_OK;
 }
 
 int pvol_get_phase_ms(pvol_ctx *c, double *out6, int reset) {
     if (!c || !out6) return PVOL_E_INVALID;
     if (!ok(hipSetDevice(c->params.device)) || !ok(hipDeviceSynchronize())) return PVOL_E_NO_DEVICE;
-    std::lock_guard<std::mutex> g(c->mu);
-    for (size_t i = 0; i + 1 < c->phaseMarks.size(); ++i) {
-        const int id = c->phaseMarks[i].first;
+    PhaseTimer &ph = c->phases;
+    std::lock_guard<std::mutex> g(c->timer.mu);
+    for (size_t i = 0; i + 1 < ph.marks.size(); ++i) {
+        const int id = ph.marks[i].first;
         float ms = 0.f;
-        if (id >= 0 && id < PVOL_N_PHASES && ok(hipEventElapsedTime(&ms, c->phaseMarks[i].second, c->phaseMarks[i + 1].second))) c->phaseMs[id] += ms;
+        if (id >= 0 && id < PVOL_N_PHASES && ok(hipEventElapsedTime(&ms, ph.marks[i].second.get(), ph.marks[i + 1].second.get()))) ph.ms[id] += ms;
     }
-    for (size_t i = 0; i < c->phaseMarks.size(); ++i) c->phasePool.push_back(c->phaseMarks[i].second);
-    c->phaseMarks.clear();
-    for (int i = 0; i < PVOL_N_PHASES; ++i) out6[i] = c->phaseMs[i];
-    if (reset) for (int i = 0; i < PVOL_N_PHASES; ++i) c->phaseMs[i] = 0.0;
+    for (size_t i = 0; i < ph.marks.size(); ++i) ph.pool.push_back(std::move(ph.marks[i].second));
+    ph.marks.clear();
+    for (int i = 0; i < PVOL_N_PHASES; ++i) out6[i] = ph.ms[i];
+    if (reset) for (int i = 0; i < PVOL_N_PHASES; ++i) ph.ms[i] = 0.0;
     return PVOL_OK;
 }
 
 int pvol_kernel_time_ms(pvol_ctx *c, double *avgMs, uint64_t *launches, int reset) {
     if (!c || !avgMs) return PVOL_E_INVALID;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!harvest_events(c, true)) return PVOL_E_NO_DEVICE;
-    *avgMs = c->launches ? c->timeMs / (double)c->launches : 0.0;
-    if (launches) *launches = c->launches;
-    if (reset) { c->timeMs = 0; c->launches = 0; }
+    BatchTimer &t = c->timer;
+    std::lock_guard<std::mutex> g(t.mu);
+    if (!harvest_events(t, true)) return PVOL_E_NO_DEVICE;
+    *avgMs = t.launches ? t.timeMs / (double)t.launches : 0.0;
+    if (launches) *launches = t.launches;
+    if (reset) { t.timeMs = 0; t.launches = 0; }
     return PVOL_OK;
 }
 

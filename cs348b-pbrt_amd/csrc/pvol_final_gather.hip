@@ -144,7 +144,7 @@ uint32_t pvol_final_gather_slice(int32_t nSamples, uint64_t bound) {
 int pvol_final_gather_set_scratch_bound(pvol_ctx *c, uint64_t bytes) {
     if (!c) return PVOL_E_INVALID;
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
-    c->fgScratchBound = std::min<uint64_t>(bytes, PVOL_FINAL_GATHER_SCRATCH_BYTES);   // the hook only lowers the bound
+    c->fg.bound = std::min<uint64_t>(bytes, PVOL_FINAL_GATHER_SCRATCH_BYTES);   // the hook only lowers the bound
     return PVOL_OK;
 }
 
@@ -164,11 +164,11 @@ int pvol_final_gather_device(pvol_ctx *c, const float *dP, const float *dFrames,
     if (!count) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
     hipStream_t stream = (hipStream_t)hipStream;
-    const uint32_t slice = std::min(count, pvol_final_gather_slice(nSamples, c->fgScratchBound));
+    const uint32_t slice = std::min(count, pvol_final_gather_slice(nSamples, c->fg.bound));
     const size_t sliceRecs = (size_t)slice * nSamples;   // records of one loop
     const bool ownRays = !dRaysBsdf || !dRaysPhoton;
     // an earlier call's kernels, on whatever stream, may still read the slices' scratch
-    if (!c->fgFence.wait(stream)) return PVOL_E_NO_DEVICE;
+    if (!c->fg.fence.wait(stream)) return PVOL_E_NO_DEVICE;
     if (!pvol_reserve(c->buf[PVOL_BUF_FG_DIRS], 2 * sliceRecs * sizeof(pvol_gather_sample), stream) ||
         (ownRays && !pvol_reserve(c->buf[PVOL_BUF_FG_RAYS], 2 * sliceRecs * sizeof(pvol_gather_ray), stream)))
         return PVOL_E_NO_MEMORY;
@@ -200,7 +200,7 @@ int pvol_final_gather_device(pvol_ctx *c, const float *dP, const float *dFrames,
         hipLaunchKernelGGL(final_gather_sum_kernel, dim3((n + 7) / 8), dim3(256), 0, stream, A);
         if (!ok(hipGetLastError())) return PVOL_E_NO_DEVICE;
     }
-    return c->fgFence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return c->fg.fence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 int pvol_final_gather(pvol_ctx *c, const float *p, const float *frames, const float *wo, const float *kd, const float *rayEps, uint32_t count,

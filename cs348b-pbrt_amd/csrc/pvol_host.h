@@ -1,4 +1,4 @@
-// pvol_host.h -- host-side internals shared by every unit with host code: the owners of device memory and events, the context, the
+// pvol_host.h -- host-side internals shared by every unit with host code: the owners of device memory, events, streams and pinned memory, the context, the
 // kernels' launchers, the plans and the test entries that are no part of include/pvol.h
 #ifndef PVOL_HOST_H
 #define PVOL_HOST_H
@@ -10,6 +10,7 @@
 #include <mutex>
 #include <vector>
 #include "pvol_dev.h"
+#include "pvol_env.h"
 #include "pvol_rays_plan.h"
 
 static bool ok(hipError_t e) { return e == hipSuccess; }
@@ -38,22 +39,44 @@ private:
     T *p = 0;
 };
 
-// An event with an owner: move-only, created on first use (for ordering only, no timing), destroyed by its destructor.
-struct PVOL_LOCAL DevEvent {
-    DevEvent() {}
-    DevEvent(DevEvent &&o) : e(o.e) { o.e = 0; }
-    DevEvent &operator=(DevEvent &&o) { std::swap(e, o.e); return *this; }
-    DevEvent(const DevEvent &) = delete;
-    DevEvent &operator=(const DevEvent &) = delete;
-    ~DevEvent() { if (e) hipEventDestroy(e); }
-    bool create() {
-        if (e || ok(hipEventCreateWithFlags(&e, hipEventDisableTiming))) return true;
-        e = 0;
+// The one owner of a HIP handle: move-only, 0 until the deriving owner makes it, given to Free by the destructor.
+template <class H, hipError_t (*Free)(H)> struct PVOL_LOCAL DevHandle {
+    DevHandle() {}
+    DevHandle(DevHandle &&o) : h(o.h) { o.h = 0; }
+    DevHandle &operator=(DevHandle &&o) { std::swap(h, o.h); return *this; }
+    DevHandle(const DevHandle &) = delete;
+    DevHandle &operator=(const DevHandle &) = delete;
+    ~DevHandle() { reset(); }
+    H get() const { return h; }
+    void reset() { if (h) Free(h); h = 0; }
+protected:
+    H h = 0;
+};
+// An event, created on first use: for ordering only, or (timing) one that hipEventElapsedTime accepts.
+struct PVOL_LOCAL DevEvent : DevHandle<hipEvent_t, hipEventDestroy> {
+    bool create(bool timing = false) {
+        if (h || ok(timing ? hipEventCreate(&h) : hipEventCreateWithFlags(&h, hipEventDisableTiming))) return true;
+        h = 0;
         return false;
     }
-    hipEvent_t get() const { return e; }   // 0 before the first create()
-private:
-    hipEvent_t e = 0;
+};
+// A blocking stream (ordered behind the null stream), created on first use.
+struct PVOL_LOCAL DevStream : DevHandle<hipStream_t, hipStreamDestroy> {
+    bool create() {
+        if (h || ok(hipStreamCreate(&h))) return true;
+        h = 0;
+        return false;
+    }
+};
+// Pinned host memory.  alloc() frees what it held; a failed hipHostMalloc leaves it empty and HIP's last error cleared.
+struct PVOL_LOCAL PinnedBuf : DevHandle<void *, hipHostFree> {
+    bool alloc(size_t bytes) {
+        reset();
+        if (hipHostMalloc(&h, bytes, hipHostMallocDefault) == hipSuccess) return true;
+        h = 0; (void)hipGetLastError();
+        return false;
+    }
+    unsigned char *get() const { return (unsigned char *)h; }
 };
 
 // What lets a call on any stream reuse scratch of the context behind the previous call's kernels: wait() in front of
@@ -257,12 +280,63 @@ struct PVOL_LOCAL GatherMap {
     DevPtr<float> wi;          // [n][3]
 };
 
+// ---- the parts of a context
+// Kernel timing: every batch records a pair of timing events on its launch stream (pvol_launch_batch, harvest_events in pvol_api.hip).
+struct PVOL_LOCAL BatchTimer {
+    typedef std::pair<DevEvent, DevEvent> Pair;
+    std::vector<Pair> pending, pool;   // recorded and not yet folded in; free for the next batch
+    double timeMs = 0.0;
+    uint64_t launches = 0;
+    std::mutex mu;                     // event lists only: these and the phase timer's
+    // The pair taken for one batch: to `pending` once the batch is enqueued (done), back to `pool` on every other way out.
+    struct Lease {
+        BatchTimer &t; Pair ev; bool done = false;
+        ~Lease() { std::lock_guard<std::mutex> g(t.mu); (done ? t.pending : t.pool).push_back(std::move(ev)); }
+    };
+};
+// Phase timing of the render driver (pvol_enable_phase_timing): marks on the launch stream, a mark opens phase `id` and closes the one
+// before it; PVOL_PHASE_END closes without opening.  Guarded by BatchTimer::mu.
+struct PVOL_LOCAL PhaseTimer {
+    bool on = false;
+    std::vector<std::pair<int, DevEvent> > marks;
+    std::vector<DevEvent> pool;
+    double ms[PVOL_N_PHASES] = {0, 0, 0, 0, 0, 0};
+};
+// Coalesced per-sample calls (pvol_li_coalesce.hip): concurrent pvol_li calls queue here, one of them (the leader) runs a batch of up
+// to maxBatch of them while the others wait; mu guards the queue, apiMu still guards the batch.
+struct PVOL_LOCAL LiCoalescer {
+    std::atomic<uint32_t> maxBatch{0};   // <= 1: every pvol_li is its own batch (pvol_li_lone)
+    uint32_t maxWaitUs = 0;
+    std::mutex mu;
+    std::condition_variable done, more;   // a batch finished / a caller joined the queue (an idle leader may wait for it)
+    std::deque<struct LiRequest *> queue;
+    bool busy = false;                    // a leader is running a batch
+    // calls served by coalesced batches, batches, largest batch, calls that queued behind a batch; then, for every batch of
+    // pvol_li_many and the coalescer: batches redone call by call (gated backup), calls that failed on their own
+    uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    // persistent staging of the batches (pinned host here, device in pvol_ctx::buf, grown to the largest batch) and the context's own stream
+    DevStream stream;
+    PinnedBuf hostIn, hostOut;
+    uint32_t cap = 0;
+};
+// What a sliced query path keeps between calls.  bound: its *_set_scratch_bound (tests), bytes of scratch a slice may
+// take, 0 = the path's PVOL_*_SCRATCH_BYTES; fence: the end of the last call's kernels, behind which the next call, on whatever stream,
+// reuses their scratch.
+struct PVOL_LOCAL SliceScratch { uint64_t bound = 0; ScratchFence fence; };
+
 struct pvol_ctx {
     pvol_params params = {};
+    CtxKnobs knobs;          // the environment as pvol_create found it (pvol_env.h)
+    int nCU = 256;
+    // One batch at a time per context: the launches of a batch share dWords / dCounters and the scratch in `buf`.  Host entry points hold it from upload to copy-back (VolumeIntegrator::Li is called from every
+    // SamplerRendererTask thread at once, samplerrenderer.cpp:247); device entry points hold it while they enqueue.
+    std::recursive_mutex apiMu;
+    // scene
     bool haveScene = false;
     DevScene hs = {};        // host copy
     DevPtr<DevScene> ds;     // device copy
     DevPtr<float> dDensity;
+    float maxDensity = 1.f;   // largest density factor of the medium (1 for analytic volumes, max of the grid values)
     // triangle hierarchy of a scene with more than PVOL_MAX_TRIS triangles (pvol_bvh.hip), else empty
     DevPtr<float4> dBvhNodes, dBvhTris;
     std::vector<int32_t> triMatHost;   // material of every triangle of the scene (host copy, any size)
@@ -272,44 +346,23 @@ struct pvol_ctx {
     // photon map
     DevPtr<float> dRawP, dRawWi, dRawAlpha;  // upload order (kept for pvol_download_photons)
     PhotonGrid volMap;
+    int momentTerms = 0;        // pvol_moment_scene's decision for the scene set last (0: no moment form, volMap.mom stays empty)
+    // what the launches of a batch share, and what they report
     DevPtr<DevCounters> dCounters;
     DevPtr<uint32_t> dWords;   // [0] chunk counter of the ray-parallel kernels, [1] needSeq flag, [2] length of the deferred-lookup list, [3] chunk counter of a gated backup kernel
-    int nCU = 256;
-    float maxDensity = 1.f;   // largest density factor of the medium (1 for analytic volumes, max of the grid values)
-    bool noLite = false;      // PVOL_NO_LITE=1: keep the geometry inside the sequential resolve pass (testing)
+    DevBuf buf[PVOL_N_BUFS];   // scratch grown on demand (pvol_reserve), freed with the context
+    bool statsOn = false;
     const char *lastKernel = "";
     const char *lastTileKernel = "";   // pvol_tile_kernel_name: set by the launch itself
     const char *lastTileForm = "";     // pvol_tile_form_name: "plain" / "general", the form of the last tile launch (pvol_tile_plain_gate)
-    bool tileGeneral = false;   // PVOL_TILE_GENERAL=1: the COUNT-mode tile pre-pass keeps its general form where the plan would take PLAIN
-    int fixWavesPerCU = 16;   // li_fixup_kernel waves per CU; PVOL_FIX_WAVES overrides
-    int groupWavesPerCU = 12; // resident li_group_kernel waves per CU (LDS plan: 8); PVOL_GROUP_WAVES overrides
-    bool noGroup = false;       // PVOL_NO_GROUP=1: keep li_par_kernel (one wave per ray) where li_group_kernel (one ray per lane) would run
-    bool forceSeq = false;      // PVOL_FORCE_SEQ=1: always take the stream-sequential kernel (testing)
-    bool noMoments = false;     // PVOL_NO_MOMENTS=1: li_group_kernel keeps summing 30 bins where it would sum XYZ moments
-    float groupPrecore = 0.f;   // PVOL_GROUP_PRECORE (pvol_precore_kappa): li_group_kernel settles the bucket's inner photons once per wave, 0 = off
-    int momentTerms = 0;        // pvol_moment_scene's decision for the scene set last (0: no moment form, volMap.mom stays empty)
-    bool statsOn = false;
-    // kernel timing (HIP events on the launch stream)
-    std::vector<std::pair<hipEvent_t, hipEvent_t> > pending;
-    std::vector<std::pair<hipEvent_t, hipEvent_t> > pool;
-    double timeMs = 0.0;
-    uint64_t launches = 0;
-    std::mutex mu;       // event lists only
-    // phase timing of the render driver (pvol_enable_phase_timing): marks on the launch stream, a mark opens phase `id` and
-    // closes the one before it; PVOL_PHASE_END closes without opening
-    int tileWaves = 0;       // PVOL_TILE_WAVES: waves per render task of the COUNT-mode tile pre-pass (0 = by tasks per CU)
-    bool phaseOn = false;
-    std::vector<std::pair<int, hipEvent_t> > phaseMarks;
-    std::vector<hipEvent_t> phasePool;
-    double phaseMs[PVOL_N_PHASES] = {0, 0, 0, 0, 0, 0};
-    // One batch at a time per context: the launches of a batch share dWords / dCounters and the scratch in `buf`.  Host entry points hold it from upload to copy-back (VolumeIntegrator::Li is called from every
-    // SamplerRendererTask thread at once, samplerrenderer.cpp:247); device entry points hold it while they enqueue.
-    std::recursive_mutex apiMu;
-    DevBuf buf[PVOL_N_BUFS];   // scratch grown on demand (pvol_reserve), freed with the context
+    BatchTimer timer;
+    PhaseTimer phases;
     // photon shooter
     DevShootScene hsh = {};
     DevPtr<DevShootScene> dsh;
     uint64_t shootStats[12] = {};
+    double exchangeSeconds = 0.0;   // last pvol_preprocess: time in its all-gathers (part of prepSeconds[0]; 0 after pvol_preprocess_blocks)
+    double prepSeconds[2] = {0.0, 0.0};   // last pvol_preprocess: shooting (all rounds + merges), search-structure build
     // surface stores of the last pvol_preprocess (kept only with params.keep_surface_photons): kind 0 caustic, 1 direct, 2 indirect
     struct PVOL_LOCAL SurfStore { DevPtr<float> p, wo, alpha; uint32_t n = 0, nPaths = 0; } surf[3];
     bool surfKept = false;   // the last pvol_preprocess ran with keep_surface_photons and left its stores here
@@ -317,15 +370,9 @@ struct pvol_ctx {
     uint32_t nRad = 0;
     RadianceResult rad;    // pvol_compute_radiance*: dropped by every shoot and by pvol_free_surface_stores
     GatherMap gather;      // pvol_build_gather_map*: dropped wherever `rad` is
-    uint64_t fgScratchBound = 0;   // pvol_final_gather_set_scratch_bound (tests): bytes of scratch a slice may take, 0 = PVOL_FINAL_GATHER_SCRATCH_BYTES
-    ScratchFence fgFence;          // pvol_final_gather_device: as lpFence, for PVOL_BUF_FG_DIRS and PVOL_BUF_FG_RAYS
-    // pvol_lphoton_batch* (pvol_lphoton.hip)
-    bool lpNoSort = false;         // PVOL_LPHOTON_NO_SORT=1: the points are served in the caller's order (testing; the results are the same bytes)
-    uint64_t lpScratchBound = 0;   // pvol_lphoton_set_scratch_bound (tests): bytes of ordering scratch a slice may take, 0 = PVOL_LPHOTON_SCRATCH_BYTES
-    ScratchFence lpFence;          // the end of the last call's kernels: the next call, on whatever stream, reuses their scratch behind it
-    // pvol_radiance_batch* (pvol_rays.hip)
-    uint64_t rrScratchBound = 0;   // pvol_radiance_set_scratch_bound (tests): bytes of scratch a slice may take, 0 = PVOL_RADIANCE_SCRATCH_BYTES
-    ScratchFence rrFence;          // as lpFence
+    // the sliced query paths: pvol_final_gather* (PVOL_BUF_FG_*), pvol_lphoton_batch* (PVOL_BUF_LP_*), pvol_radiance_batch* and
+    // pvol_radiance_gather_batch* (PVOL_BUF_RR_*, PVOL_BUF_RG_*)
+    SliceScratch fg, lp, rr;
     // caustic map of the surface integrator (pvol_set_surface_integrator), same cell layout as the volume map
     PhotonGrid causticMap;
     // ... and its indirect map (pvol_set_surface_integrator_maps: LPhoton(indirectMap) without the final gather), built by the same builder
@@ -333,23 +380,7 @@ struct pvol_ctx {
     // specular recursion of the surface integrator (pvol_spec_dev.h): segments of the camera samples that meet glass
     bool specOn = false;            // the scene holds a specular material and the surface integrator is on
     pvol_stream hSegStream = {};    // the segment pool seen as one stream of a ray batch (host copy of PVOL_BUF_SEG_STREAM)
-    double exchangeSeconds = 0.0;   // last pvol_preprocess: time in its all-gathers (part of prepSeconds[0]; 0 after pvol_preprocess_blocks)
-    double prepSeconds[2] = {0.0, 0.0};   // last pvol_preprocess: shooting (all rounds + merges), search-structure build
-    // coalesced per-sample calls (pvol_li_coalesce.hip): concurrent pvol_li calls queue here, one of them (the leader) runs
-    // a batch of up to coMaxBatch of them while the others wait; coMu guards the queue, apiMu still guards the batch
-    std::atomic<uint32_t> coMaxBatch{0};   // <= 1: every pvol_li is its own batch (pvol_li_lone)
-    uint32_t coMaxWaitUs = 0;
-    std::mutex coMu;
-    std::condition_variable coDone, coMore;   // a batch finished / a caller joined the queue (an idle leader may wait for it)
-    std::deque<struct LiRequest *> coQueue;
-    bool coBusy = false;                   // a leader is running a batch
-    // calls served by coalesced batches, batches, largest batch, calls that queued behind a batch; then, for every batch of
-    // pvol_li_many and the coalescer: batches redone call by call (gated backup), calls that failed on their own
-    uint64_t coStats[6] = {0, 0, 0, 0, 0, 0};
-    // persistent staging of the batches (pinned host here, device in `buf`, grown to the largest batch) and the context's own stream
-    hipStream_t coStream = 0;
-    unsigned char *coHostIn = 0, *coHostOut = 0;
-    uint32_t coCap = 0;
+    LiCoalescer co;
     // pvol_render_frame_group (pvol_group.hip): the event marking this context's film done; as the root, the event after the sum
     // that last read the other films' staging (PVOL_BUF_GROUP_STAGE)
     DevEvent groupFilmEv, groupStageEv;
@@ -364,7 +395,6 @@ struct LiRequest {
     int rc;
     bool done;
 };
-#define PVOL_LI_MAX_BATCH 4096u
 #define PVOL_LI_MAX_WAIT_US 1000u
 
 // Every input of one batch (pvol_launch_batch).  `tile` != 0: the rays do not exist yet -- the tile kernel (pvol_tile_dev.h) generates
@@ -380,14 +410,8 @@ struct BatchArgs {
 extern "C" int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b);
 template <class T> static inline T *pvol_buf(const pvol_ctx *c, int which) { return (T *)c->buf[which].p.get(); }
 
-// ---- the plan of a batch: which kernels it takes and every size they need, a pure function of PlanIn.  LaunchKnobs: the
-// environment knobs read once per launch (pvol_read_knobs); 0 = unset, the default applies.
-struct LaunchKnobs {
-    int64_t sliceRays, specPool, tileBatchRays;   // PVOL_SLICE_RAYS (>= 64: forced slice length), PVOL_SPEC_POOL, PVOL_TILE_BATCH_RAYS
-    float groupGuess;                             // PVOL_GROUP_GUESS, already defaulted: li_group_kernel's bucket radius^2 factor
-    float fxgWiden, fxgAim;                       // PVOL_FXG_WIDEN, PVOL_FXG_AIM (measurement knobs of li_fixup_group_kernel)
-    int32_t fixExact;                             // PVOL_FIX_EXACT set
-};
+// ---- the plan of a batch: which kernels it takes and every size they need, a pure function of PlanIn.  LaunchKnobs
+// (pvol_env.h): the environment knobs read once per launch (pvol_read_knobs).
 extern "C" LaunchKnobs pvol_read_knobs();
 struct PlanIn {
     int32_t nLights, volKind; float g; uint32_t nPhotons; int32_t nUsed, candCap, maxSteps, nTris;   // medium and map
@@ -435,8 +459,7 @@ extern "C" int pvol_tile_plain_gate(const TilePlainIn *in);
 // delta_b = sigma_t_b - the midrange of sigma_t; pathBound: a bound on the optical path length of a ray inside the medium.
 extern "C" int pvol_moment_gate(const float *sigA, const float *sigS, double pathBound);
 // li_group_kernel's settled class, pure: precore_bound (pvol_dev.h) for the host, and the knob's value.  The knob
-// lives in the context beside PVOL_NO_MOMENTS and not in LaunchKnobs, whose layout the plan's tests mirror.
-#define PVOL_PRECORE_DEFAULT 0.7f
+// lives in the context beside PVOL_NO_MOMENTS (CtxKnobs, pvol_env.h) and not in LaunchKnobs, whose layout the plan's tests mirror.
 extern "C" float pvol_precore_bound(float theta, float rho);
 extern "C" float pvol_precore_kappa(const char *env);
 // What the moment form reads besides the map: the gate's decision for the scene `h` (its extent's world-space diagonal bounds a ray's
@@ -457,12 +480,13 @@ int pvol_push_scene(pvol_ctx *c);
 // pvol_li without the coalescer (pvol_api.hip) and through it (pvol_li_coalesce.hip); arguments already validated
 int pvol_li_lone(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T);
 int pvol_li_coalesced(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T);
-void pvol_free_li_staging(pvol_ctx *c);
 int pvol_order_after_pending(pvol_ctx *c, hipStream_t stream);
 // an RCCL function by name, bound at run time once per process (pvol_tile.hip); 0 when no RCCL is in reach
 void *pvol_rccl_symbol(const char *name);
 // plan_size(plan_path(in)) for the tests; like pvol_rccl_symbol not part of include/pvol.h
 void pvol_plan_batch(const PlanIn *in, BatchPlan *out);
+// every environment knob (pvol_env.h) parsed from n (name, value) pairs instead of the process environment, for the tests
+void pvol_env_parse(const char *const *names, const char *const *values, uint32_t n, EnvKnobs *out);
 // the gather map's kd-tree (gather_tree_build, pvol_gather_tree.h) over n host positions p[n][3], for the tests (pvol_gather.hip):
 // nodes gets n GatherNode (32 bytes each), *depth the tree's depth.  No HIP call.  PVOL_E_INVALID: a NULL pointer or a non-finite
 // position; PVOL_E_UNSUPPORTED: n == 0 or n > 2^24

@@ -22,37 +22,27 @@
 static size_t in_bytes(size_t n) { return n * (sizeof(pvol_ray) + sizeof(pvol_stream) + 625 * 4); }
 static size_t out_bytes(size_t n) { return n * (60 * 4 + 625 * 4 + 4) + 16; }
 
-static void free_host_staging(pvol_ctx *c) {
-    if (c->coHostIn) hipHostFree(c->coHostIn);
-    if (c->coHostOut) hipHostFree(c->coHostOut);
-    c->coHostIn = c->coHostOut = 0; c->coCap = 0;
-}
-void pvol_free_li_staging(pvol_ctx *c) {   // the device halves (PVOL_BUF_LI_IN / _OUT) go with the context's other buffers
-    free_host_staging(c);
-    if (c->coStream) hipStreamDestroy(c->coStream);
-    c->coStream = 0;
-}
-
-// caller holds apiMu; nothing of an earlier batch is in flight (every batch waits for its stream)
+// caller holds apiMu; nothing of an earlier batch is in flight (every batch waits for its stream).  All or nothing: a failure leaves
+// no host staging and cap 0 (the device halves, PVOL_BUF_LI_IN / _OUT, go with the context's other buffers)
 static int reserve_staging(pvol_ctx *c, uint32_t n) {
-    if (!c->coStream && !ok(hipStreamCreate(&c->coStream))) { c->coStream = 0; return PVOL_E_NO_DEVICE; }   // blocking: behind the null stream
-    if (n <= c->coCap) return PVOL_OK;
-    const uint32_t cap = std::min(PVOL_LI_MAX_BATCH, std::max(n, 2 * c->coCap));
-    free_host_staging(c);
-    if (!ok(hipHostMalloc((void **)&c->coHostIn, in_bytes(cap), hipHostMallocDefault)) ||
-        !ok(hipHostMalloc((void **)&c->coHostOut, out_bytes(cap), hipHostMallocDefault)) ||
-        !pvol_reserve(c->buf[PVOL_BUF_LI_IN], in_bytes(cap), c->coStream) || !pvol_reserve(c->buf[PVOL_BUF_LI_OUT], out_bytes(cap), c->coStream)) {
+    LiCoalescer &co = c->co;
+    if (!co.stream.create()) return PVOL_E_NO_DEVICE;   // blocking: behind the null stream
+    if (n <= co.cap) return PVOL_OK;
+    const uint32_t cap = std::min(PVOL_LI_MAX_BATCH, std::max(n, 2 * co.cap));
+    co.hostIn.reset(); co.hostOut.reset(); co.cap = 0;
+    if (!co.hostIn.alloc(in_bytes(cap)) || !co.hostOut.alloc(out_bytes(cap)) ||
+        !pvol_reserve(c->buf[PVOL_BUF_LI_IN], in_bytes(cap), co.stream.get()) || !pvol_reserve(c->buf[PVOL_BUF_LI_OUT], out_bytes(cap), co.stream.get())) {
         (void)hipGetLastError();
-        free_host_staging(c);
+        co.hostIn.reset(); co.hostOut.reset();
         return PVOL_E_NO_MEMORY;
     }
-    c->coCap = cap;
+    co.cap = cap;
     return PVOL_OK;
 }
 
 static void count(pvol_ctx *c, int slot, uint64_t v) {
-    std::lock_guard<std::mutex> lk(c->coMu);
-    c->coStats[slot] += v;
+    std::lock_guard<std::mutex> lk(c->co.mu);
+    c->co.stats[slot] += v;
 }
 
 // One launch of n validated calls (caller holds apiMu, n within the staging and record limits).
@@ -60,11 +50,12 @@ static void run_piece(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
     auto failAll = [&](int rc) { for (uint32_t i = 0; i < n; ++i) req[i]->rc = rc; };
     int rc = reserve_staging(c, n);
     if (rc != PVOL_OK) return failAll(rc);
+    const LiCoalescer &co = c->co;
     const size_t oStreams = (size_t)n * sizeof(pvol_ray), oStatesIn = oStreams + (size_t)n * sizeof(pvol_stream);
     const size_t oStatesOut = (size_t)n * 60 * 4, oStatus = oStatesOut + (size_t)n * 625 * 4, oGate = oStatus + (size_t)n * 4;
-    pvol_ray *hRays = reinterpret_cast<pvol_ray *>(c->coHostIn);
-    pvol_stream *hStreams = reinterpret_cast<pvol_stream *>(c->coHostIn + oStreams);
-    uint32_t *hStates = reinterpret_cast<uint32_t *>(c->coHostIn + oStatesIn);
+    pvol_ray *hRays = reinterpret_cast<pvol_ray *>(co.hostIn.get());
+    pvol_stream *hStreams = reinterpret_cast<pvol_stream *>(co.hostIn.get() + oStreams);
+    uint32_t *hStates = reinterpret_cast<uint32_t *>(co.hostIn.get() + oStatesIn);
     for (uint32_t i = 0; i < n; ++i) {
         hRays[i] = *req[i]->ray;
         memset(&hStreams[i], 0, sizeof(pvol_stream));
@@ -73,11 +64,11 @@ static void run_piece(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
         memcpy(hStates + (size_t)i * 625, req[i]->mt, 624 * 4);
         hStates[(size_t)i * 625 + 624] = (uint32_t)*req[i]->mti;
     }
-    hipStream_t s = c->coStream;
+    hipStream_t s = co.stream.get();
     unsigned char *devIn = pvol_buf<unsigned char>(c, PVOL_BUF_LI_IN), *devOut = pvol_buf<unsigned char>(c, PVOL_BUF_LI_OUT);
     float *dOut = reinterpret_cast<float *>(devOut);
     int32_t *dStatus = reinterpret_cast<int32_t *>(devOut + oStatus);
-    bool good = pvol_order_after_pending(c, s) == PVOL_OK && ok(hipMemcpyAsync(devIn, c->coHostIn, in_bytes(n), hipMemcpyHostToDevice, s)) &&
+    bool good = pvol_order_after_pending(c, s) == PVOL_OK && ok(hipMemcpyAsync(devIn, co.hostIn.get(), in_bytes(n), hipMemcpyHostToDevice, s)) &&
                 ok(hipMemsetAsync(dOut, 0, oStatesOut, s)) && ok(hipMemsetAsync(dStatus, 0, (size_t)n * 4, s));
     rc = good ? PVOL_OK : PVOL_E_NO_DEVICE;
     if (rc == PVOL_OK) {
@@ -89,22 +80,22 @@ static void run_piece(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
     }
     // a PVOL_E_LIMIT of this batch is in its rays' status only (report_limit): the context's shared count is left alone
     if (rc == PVOL_OK)
-        good = ok(hipMemcpyAsync(c->coHostOut, devOut, oGate, hipMemcpyDeviceToHost, s)) &&
-               ok(hipMemcpyAsync(c->coHostOut + oGate, c->dWords.get() + 1, 4, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s));
+        good = ok(hipMemcpyAsync(co.hostOut.get(), devOut, oGate, hipMemcpyDeviceToHost, s)) &&
+               ok(hipMemcpyAsync(co.hostOut.get() + oGate, c->dWords.get() + 1, 4, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s));
     if (rc == PVOL_OK && !good) rc = PVOL_E_NO_DEVICE;
     if (rc != PVOL_OK) { (void)hipGetLastError(); hipStreamSynchronize(s); return failAll(rc); }
     // The gated backups (li_replay_kernel behind li_group_kernel's replay form) redo EVERY stream of a batch when the hand-over
     // list overflowed, which would change the last bits of calls that did not need it.  Such a batch is redone call by call
     // from the inputs, exactly as lone pvol_li calls.
-    const uint32_t gate = *reinterpret_cast<const uint32_t *>(c->coHostOut + oGate);
+    const uint32_t gate = *reinterpret_cast<const uint32_t *>(co.hostOut.get() + oGate);
     if (gate != 0u && n > 1) {
         count(c, 4, 1);
         for (uint32_t i = 0; i < n; ++i) req[i]->rc = pvol_li_lone(c, req[i]->ray, req[i]->mt, req[i]->mti, req[i]->Lv, req[i]->T);
         return;
     }
-    const float *hOut = reinterpret_cast<const float *>(c->coHostOut);
-    const uint32_t *hFinal = reinterpret_cast<const uint32_t *>(c->coHostOut + oStatesOut);
-    const int32_t *hStatus = reinterpret_cast<const int32_t *>(c->coHostOut + oStatus);
+    const float *hOut = reinterpret_cast<const float *>(co.hostOut.get());
+    const uint32_t *hFinal = reinterpret_cast<const uint32_t *>(co.hostOut.get() + oStatesOut);
+    const int32_t *hStatus = reinterpret_cast<const int32_t *>(co.hostOut.get() + oStatus);
     uint64_t failed = 0;
     for (uint32_t i = 0; i < n; ++i) {
         LiRequest &r = *req[i];
@@ -137,29 +128,30 @@ static void run_batch(pvol_ctx *c, LiRequest *const *req, uint32_t n) {
 // requests from the front of the queue), the others wait for theirs to be done or for the leadership to come free.
 int pvol_li_coalesced(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, float *Lv, float *T) {
     LiRequest r = {ray, mt, mti, Lv, T, PVOL_OK, false};
-    std::unique_lock<std::mutex> lk(c->coMu);
-    if (c->coBusy) c->coStats[3] += 1;
-    c->coQueue.push_back(&r);
-    c->coMore.notify_one();
+    LiCoalescer &co = c->co;
+    std::unique_lock<std::mutex> lk(co.mu);
+    if (co.busy) co.stats[3] += 1;
+    co.queue.push_back(&r);
+    co.more.notify_one();
     std::vector<LiRequest *> batch;
     while (!r.done) {
-        if (c->coBusy) { c->coDone.wait(lk); continue; }
-        c->coBusy = true;
-        const uint32_t maxB = std::max(1u, c->coMaxBatch.load(std::memory_order_relaxed));
-        if (c->coMaxWaitUs && c->coQueue.size() < maxB)   // idle leader: a moment for more callers to join
-            c->coMore.wait_for(lk, std::chrono::microseconds(c->coMaxWaitUs), [&] { return c->coQueue.size() >= maxB; });
-        const size_t n = std::min<size_t>(c->coQueue.size(), maxB);
-        batch.assign(c->coQueue.begin(), c->coQueue.begin() + n);
-        c->coQueue.erase(c->coQueue.begin(), c->coQueue.begin() + n);
+        if (co.busy) { co.done.wait(lk); continue; }
+        co.busy = true;
+        const uint32_t maxB = std::max(1u, co.maxBatch.load(std::memory_order_relaxed));
+        if (co.maxWaitUs && co.queue.size() < maxB)   // idle leader: a moment for more callers to join
+            co.more.wait_for(lk, std::chrono::microseconds(co.maxWaitUs), [&] { return co.queue.size() >= maxB; });
+        const size_t n = std::min<size_t>(co.queue.size(), maxB);
+        batch.assign(co.queue.begin(), co.queue.begin() + n);
+        co.queue.erase(co.queue.begin(), co.queue.begin() + n);
         lk.unlock();
         run_batch(c, batch.data(), (uint32_t)n);
         lk.lock();
         for (LiRequest *q : batch) q->done = true;
-        c->coStats[0] += n;
-        c->coStats[1] += 1;
-        c->coStats[2] = std::max<uint64_t>(c->coStats[2], n);
-        c->coBusy = false;
-        c->coDone.notify_all();   // the served callers return; one of the rest leads the next batch
+        co.stats[0] += n;
+        co.stats[1] += 1;
+        co.stats[2] = std::max<uint64_t>(co.stats[2], n);
+        co.busy = false;
+        co.done.notify_all();   // the served callers return; one of the rest leads the next batch
     }
     return r.rc;
 }
@@ -189,17 +181,17 @@ int pvol_li_many(pvol_ctx *c, const pvol_ray *rays, uint32_t n, uint32_t *mt, in
 
 int pvol_set_li_coalescing(pvol_ctx *c, uint32_t max_batch, uint32_t max_wait_us) {
     if (max_batch > PVOL_LI_MAX_BATCH || max_wait_us > PVOL_LI_MAX_WAIT_US || !c) return PVOL_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->coMu);
-    c->coMaxBatch.store(max_batch > 1 ? max_batch : 0u, std::memory_order_relaxed);
-    c->coMaxWaitUs = max_wait_us;
+    std::lock_guard<std::mutex> lk(c->co.mu);
+    c->co.maxBatch.store(max_batch > 1 ? max_batch : 0u, std::memory_order_relaxed);
+    c->co.maxWaitUs = max_wait_us;
     return PVOL_OK;
 }
 
 int pvol_get_li_coalescing_stats(pvol_ctx *c, uint64_t *out6, int reset) {
     if (!c || !out6) return PVOL_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->coMu);
-    memcpy(out6, c->coStats, sizeof(c->coStats));
-    if (reset) memset(c->coStats, 0, sizeof(c->coStats));
+    std::lock_guard<std::mutex> lk(c->co.mu);
+    memcpy(out6, c->co.stats, sizeof(c->co.stats));
+    if (reset) memset(c->co.stats, 0, sizeof(c->co.stats));
     return PVOL_OK;
 }
 

@@ -30,7 +30,7 @@ uint32_t pvol_lphoton_slice(uint64_t bound) {
 int pvol_lphoton_set_scratch_bound(pvol_ctx *c, uint64_t bytes) {
     if (!c) return PVOL_E_INVALID;
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
-    c->lpScratchBound = std::min<uint64_t>(bytes, PVOL_LPHOTON_SCRATCH_BYTES);   // the hook only lowers the bound
+    c->lp.bound = std::min<uint64_t>(bytes, PVOL_LPHOTON_SCRATCH_BYTES);   // the hook only lowers the bound
     return PVOL_OK;
 }
 
@@ -58,9 +58,9 @@ int pvol_lphoton_batch_device(pvol_ctx *c, const float *dP, const float *dW, uin
         return PVOL_OK;
     }
     // an earlier call's kernels, on whatever stream, may still read the ordering scratch
-    if (!c->lpFence.wait(stream)) return PVOL_E_NO_DEVICE;
-    const uint32_t slice = std::min(n, pvol_lphoton_slice(c->lpScratchBound));
-    const bool sort = !c->lpNoSort;
+    if (!c->lp.fence.wait(stream)) return PVOL_E_NO_DEVICE;
+    const uint32_t slice = std::min(n, pvol_lphoton_slice(c->lp.bound));
+    const bool sort = !c->knobs.lpNoSort;
     size_t tempBytes = 0;
     uint32_t *work = 0;
     if (sort) {
@@ -76,7 +76,7 @@ int pvol_lphoton_batch_device(pvol_ctx *c, const float *dP, const float *dW, uin
     A.spectral = spectral;
     A.out = dOut; A.nFound = dNFound; A.radius2 = dRadius2;
     const RegionLaunchers &launch = pvol_launchers(c->hs.volKind);
-    const uint32_t maxWaves = (uint32_t)std::max(1, c->nCU * c->fixWavesPerCU);
+    const uint32_t maxWaves = (uint32_t)std::max(1, c->nCU * c->knobs.fixWavesPerCU);
     // the slices follow one another on the stream, so each may reuse the scratch of the one before
     for (uint32_t q0 = 0; q0 < n; q0 += slice) {
         const uint32_t m = std::min(slice, n - q0);
@@ -90,7 +90,7 @@ int pvol_lphoton_batch_device(pvol_ctx *c, const float *dP, const float *dW, uin
         const uint32_t nWaves = std::min(maxWaves, (nRuns + 7u) / 8u);
         if (!ok(launch.lphotonPoints(&A, c->hs.candCap, nWaves, stream))) return PVOL_E_NO_DEVICE;
     }
-    return c->lpFence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return c->lp.fence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 int pvol_lphoton_batch(pvol_ctx *c, const float *p, const float *w, uint32_t n, int outputKind, float *out, uint32_t *nFound, float *radius2) {

@@ -148,9 +148,9 @@ int pvol_finish_map(pvol_ctx *c, uint32_t n, const float *hostPositions) {
     // the 4 x 4 x 4 second level.  PVOL_SUBGRID=0/1 forces it off/on.
     const size_t ncells = G.cells();
     double sq = 0.0;
-    const char *ev = getenv("PVOL_SUBGRID");
+    const int forced = pvol_env_subgrid(pvol_env_get);
     bool want = false;
-    if (ev) want = atoi(ev) != 0;
+    if (forced >= 0) want = forced != 0;
     else if (ok(pvol_grid_occupancy(G.cellStart.get(), (uint32_t)ncells, &sq, 0))) want = sq / (double)n > 64.0;
     // (no room for the table: the coarse level alone is complete)
     if (want && ncells * 64 < 0xfffffff0ull && G.subStart.alloc(ncells * 64 + 1)) {

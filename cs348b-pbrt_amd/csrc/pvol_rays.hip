@@ -80,7 +80,7 @@ int pvol_radiance_slice_streams(const pvol_stream *streams, uint32_t nStreams, u
 int pvol_radiance_set_scratch_bound(pvol_ctx *c, uint64_t bytes) {
     if (!c) return PVOL_E_INVALID;
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
-    c->rrScratchBound = std::min<uint64_t>(bytes, PVOL_RADIANCE_SCRATCH_BYTES);   // the hook only lowers the bound
+    c->rr.bound = std::min<uint64_t>(bytes, PVOL_RADIANCE_SCRATCH_BYTES);   // the hook only lowers the bound
     return PVOL_OK;
 }
 
@@ -106,11 +106,11 @@ static int radiance_slices(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, p
     const uint32_t maxSeg = pvol_radiance_max_segments(specOn, c->hs.surf.maxSpecularDepth);
     // A slice is sized for rays that spawn nothing, counted, and cut back to the longest run of its rays whose blocks fit the bound: sizing
     // it for the worst case (30 spawned rays each at depth 5) would make slices of a few thousand rays, launches too small for the device
-    const uint64_t budget = c->rrScratchBound ? c->rrScratchBound : PVOL_RADIANCE_SCRATCH_BYTES;
+    const uint64_t budget = c->rr.bound ? c->rr.bound : PVOL_RADIANCE_SCRATCH_BYTES;
     const uint64_t perExpanded = (uint64_t)PVOL_RADIANCE_RAY_SCRATCH + (gather ? PVOL_RADIANCE_GATHER_SCRATCH(gather->g.n_samples) : 0u);
     const uint32_t slice = std::min(nRays, gather ? pvol_radiance_gather_slice(gather->g.n_samples, budget) : pvol_radiance_slice(0, budget));
     // an earlier call's kernels, on whatever stream, may still read the scratch
-    if (!c->rrFence.wait(stream)) return PVOL_E_NO_DEVICE;
+    if (!c->rr.fence.wait(stream)) return PVOL_E_NO_DEVICE;
     size_t tempBytes = 0;
     if (!ok(hipcub::DeviceScan::ExclusiveSum((void *)0, tempBytes, (const uint32_t *)0, (uint32_t *)0, (int)(slice + 1u), stream))) return PVOL_E_NO_DEVICE;
     if (!pvol_reserve(c->buf[PVOL_BUF_RR_COUNT], sizeof(uint32_t) * 2 * ((size_t)slice + 1), stream) ||
@@ -203,7 +203,7 @@ static int radiance_slices(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRays, p
         if (!ok(pvol_launch_rays_compose(&A, dTable, ns, dStreams + s0, stream))) return PVOL_E_NO_DEVICE;
         r0 = r1;
     }
-    return c->rrFence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
+    return c->rr.fence.record(stream) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
 
 extern "C" {

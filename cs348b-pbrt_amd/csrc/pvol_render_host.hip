@@ -127,13 +127,13 @@ namespace {
 // pvol_get_phase_ms would charge the gap up to the next call's first mark to it: every exit but the one that sets `keep` closes it.
 struct PhaseClose {
     pvol_ctx *c; hipStream_t stream; size_t marks0; bool keep = false;
-    static size_t marks(pvol_ctx *c) { std::lock_guard<std::mutex> g(c->mu); return c->phaseMarks.size(); }
+    static size_t marks(pvol_ctx *c) { std::lock_guard<std::mutex> g(c->timer.mu); return c->phases.marks.size(); }
     ~PhaseClose() {
         if (keep) return;
         bool open;
         {
-            std::lock_guard<std::mutex> g(c->mu);
-            open = c->phaseMarks.size() > marks0 && c->phaseMarks.back().first != PVOL_PHASE_END;
+            std::lock_guard<std::mutex> g(c->timer.mu);
+            open = c->phases.marks.size() > marks0 && c->phases.marks.back().first != PVOL_PHASE_END;
         }
         if (open) pvol_phase_mark(c, stream, PVOL_PHASE_END);
     }
@@ -206,7 +206,7 @@ extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *c
     if (plan.rc != PVOL_OK) return plan.rc;
 #ifdef PVOL_TIMING_KNOBS   // timing experiments only (tools/tile_debug_*.sh build with it): every knob gives WRONG images and stream
                            // positions, so the shipped library does not read the variable at all
-    if (const char *dbg = getenv("PVOL_TILE_DEBUG")) plan.tile.debugSkip = (uint32_t)atoi(dbg);
+    pvol_env_tile_debug(pvol_env_get, &plan.tile.debugSkip);
 #endif
     std::lock_guard<std::recursive_mutex> api(c->apiMu);   // the work buffers and launch scratch live in the context
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;

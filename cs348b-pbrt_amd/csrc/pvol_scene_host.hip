@@ -282,16 +282,15 @@ static int upload_bvh(const pvol_scene *s, const SceneImage &img, DevPtr<float4>
                 ok(hipMemcpy(dMat.get(), img.primMat.data(), (size_t)n * 4, hipMemcpyHostToDevice)) &&
                 ok(hipMemcpy(dFlip.get(), fl.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     if (good) {
-        hipEvent_t e0, e1;
-        hipEventCreate(&e0); hipEventCreate(&e1);
-        hipEventRecord(e0, 0);
+        DevEvent e0, e1;
+        e0.create(true); e1.create(true);
+        hipEventRecord(e0.get(), 0);
         good = ok(pvol_build_bvh(dTri.get(), dMat.get(), dFlip.get(), n, img.bvhPad, tris.get(), nodes.get(), 0));
-        hipEventRecord(e1, 0);
-        hipEventSynchronize(e1);
+        hipEventRecord(e1.get(), 0);
+        hipEventSynchronize(e1.get());
         float t = 0.f;
-        hipEventElapsedTime(&t, e0, e1);
+        hipEventElapsedTime(&t, e0.get(), e1.get());
         *ms = t;
-        hipEventDestroy(e0); hipEventDestroy(e1);
     }
     return good ? PVOL_OK : PVOL_E_NO_MEMORY;
 }

@@ -21,6 +21,7 @@
 // The path is VALU/latency bound; the only compulsory HBM traffic is the 144-B photon record.
 #include <stdlib.h>
 #include <algorithm>
+#include "pvol_env.h"
 #include "pvol_rng_dev.h"
 #include "pvol_light_dev.h"
 #include "pvol_shoot_args.h"
@@ -755,7 +756,7 @@ extern "C" hipError_t pvol_launch_shoot(const ShootArgs *a, hipStream_t stream) 
                             (a->gridVolume ? (size_t)GRID_KMAX * LANES * 4 : 0);
     // registers: the path state is ~240 wave-uniform values; 2 waves per SIMD hold them without spills, 4 spill ~160 of
     // them to scratch but hide more latency (PVOL_SHOOT_WPE picks; measured in profiles/)
-    static const int wpe = [] { const char *e = getenv("PVOL_SHOOT_WPE"); const int v = e ? atoi(e) : 2; return (v == 4 || v == 3) ? v : 2; }();
+    static const int wpe = pvol_env_shoot_wpe(pvol_env_get);
     if (wpe == 4) hipLaunchKernelGGL((shoot_kernel<4>), dim3(a->nTasks), dim3(LANES), ldsBytes, stream, *a);
     else if (wpe == 3) hipLaunchKernelGGL((shoot_kernel<3>), dim3(a->nTasks), dim3(LANES), ldsBytes, stream, *a);
     else hipLaunchKernelGGL((shoot_kernel<2>), dim3(a->nTasks), dim3(LANES), ldsBytes, stream, *a);

@@ -291,12 +291,10 @@ int shoot_rounds(pvol_ctx *c, uint32_t rank, Exchange &X, ShootMerge &merge, Sto
     // one is REDONE with a larger pool from the saved RNG states (the round is a pure function of them): nothing is dropped
     // and nothing is sized for the worst case.
     uint32_t capMax = (uint32_t)std::min<size_t>(65536, std::max<size_t>(256, ((size_t)48 << 30) / ((size_t)Ls * 144)));
-    // Test knobs, a positive value lowers: PVOL_SHOOT_RANK_CAP_MAX this rank's largest block pool, on a single GPU too (set on one rank,
-    // that rank alone fails); PVOL_SHOOT_POOL_START the pools' starting sizes (1: every pool is outgrown and the round redone)
-    const auto lowered = [](uint32_t v, const char *knob) { const char *e = getenv(knob); const long x = e ? atol(e) : 0; return x > 0 ? (uint32_t)std::min<long>(v, x) : v; };
-    capMax = lowered(capMax, "PVOL_SHOOT_RANK_CAP_MAX");
+    const ShootKnobs knobs = pvol_env_shoot(pvol_env_get);   // test knobs, a positive value lowers (pvol_env.h)
+    capMax = env_lowered(capMax, knobs.rankCapMax);
     uint32_t cap = std::min<uint32_t>(256, capMax), capS = keep ? std::min<uint32_t>(256, capMax) : 1, capR = keep ? 64 : 1;
-    cap = lowered(cap, "PVOL_SHOOT_POOL_START"); capS = lowered(capS, "PVOL_SHOOT_POOL_START"); capR = lowered(capR, "PVOL_SHOOT_POOL_START");
+    cap = env_lowered(cap, knobs.poolStart); capS = env_lowered(capS, knobs.poolStart); capR = env_lowered(capR, knobs.poolStart);
     Buffers B;
     int &localRc = *localRcOut;   // reported to all at the next exchange
     if (!(B.stateA.alloc(SW * Ls) && B.stateB.alloc(SW * Ls) && B.halton.alloc(48 * (size_t)Ls) && B.flags.alloc(Ls) && B.localCounts.alloc(8 * (size_t)Ls) &&
