@@ -30,6 +30,10 @@
 // instead of running the exact wave-cooperative lookup inline, and li_fixup_kernel adds those terms afterwards
 // (lphoton(), always exact).  The hot kernel therefore carries neither lphoton's registers nor its LDS: three waves
 // per SIMD.
+//
+// Source layout: GrpLdsPlan / grp_carve (the LDS plan), GrpRow / grp_row / grp_row4 (the constant rows), grp_order_chunk (chunk ordering),
+// grp_step_len (optical length of a march step, pre-loop and march), grp_centre (centre and spread of the served lanes), stage_bucket,
+// grp_pass1, grp_find_kth (prefix scan), grp_theta, grp_pass2; the other phases are li_group_kernel's own text.
 #define GRP_CH 512  // rays per chunk (ordered by scatter_u, then cut into groups of 64)
 #define GRP_CAP 256   // bucket capacity (photons)
 #define GRP_NW (GRP_CAP / 32)     // 32-bit mask words per lane
@@ -54,13 +58,27 @@
 // nused > GRP_PLAN_KMAX (C3: 500) keeps only the fixed-radius plan: when everything within maxDist fits the bucket the lanes
 // with fewer than nused photons are served here (most of C3's lookups: < 10 photons -> 0), the dense ones go to li_fixup_kernel.
 
+// The constant rows of GroupLds::cst, 32 floats each (30 bins and two zeros), in the order li_group_kernel fills them
+enum GrpRow { GRP_ROW_SIGA, GRP_ROW_SIGS, GRP_ROW_LE, GRP_ROW_ALBEDO, GRP_ROW_LIGHT0, GRP_ROW_RCP_SIGS, GRP_ROW_CIEX, GRP_ROW_CIEY, GRP_ROW_CIEZ,
+              GRP_ROW_SIGT, GRP_ROW_SIGA_LE, GRP_ROW_ALBEDO_RCP_SIGS, GRP_ROWS };
+// LDS plan (11.7 KB: twelve waves per CU), byte offsets: prevRk | order | bucket | U | cst | trows | lint.  grp_carve hands out the pointers,
+// pvol_group_lds_bytes returns the total: the kernel and its launcher read one description.
+struct GrpLdsPlan {
+    static constexpr size_t prevRk = 0, order = prevRk + (size_t)PREV_N * 4, bucket = order + GRP_CH * 2, U = bucket + (size_t)GRP_PITCH * 16,
+                            cst = U + GRP_U_BYTES, trows = cst + GRP_ROWS * 32 * 4, lint = trows + GRP_TRI_ROWS * 64, total = lint + PVOL_MAX_LIGHTS * 32 * 4;
+};
+static_assert(GrpLdsPlan::total == (size_t)PREV_N * 4 + GRP_CH * 2 + (size_t)GRP_PITCH * 16 + GRP_U_BYTES + 12 * 32 * 4 + GRP_TRI_ROWS * 64 + PVOL_MAX_LIGHTS * 32 * 4,
+              "the plan's total is what the launcher has always passed");
+static_assert(GrpLdsPlan::bucket % 16 == 0 && GrpLdsPlan::U % 16 == 0 && GrpLdsPlan::cst % 16 == 0 && GrpLdsPlan::lint % 16 == 0, "16-byte reads of the bucket and the rows");
+
 struct GroupLds {
+    float *prevRk;          // PREV_N: mean k-th distance^2 of the previous group at each march step
     float *pos;             // bucket, SoA: x[GRP_PITCH] | y | z | photon index bits
     uint32_t *hist;         // [GRP_BINS / 8 + 1][64] packed 4-bit counters, one column per lane (U region)
     float *miniD;           // [GRP_MINI][64] values of the k-th's bin, one column per lane (U region)
     float *ubuf;            // GRP_CH scatter offsets (U region)
     unsigned short *order;  // GRP_CH: chunk-local ray index by rank of scatter offset
-    float *cst;             // 12 x 32 floats: sigA, sigS, le, albedo, light-0 intensity, 1/sigS, CIE X, Y, Z weights, sigT, sigA le, albedo / sigS
+    float *cst;             // GRP_ROWS x 32 floats: the constant rows, see GrpRow (grp_row, grp_row4)
     float *trows;           // GRP_TRI_ROWS x 16 floats: per-triangle shadow-ray precomputation for a distant light
     float *lint;            // PVOL_MAX_LIGHTS x 32 floats: every light's intensity spectrum (REPLAY: the light differs per lane and step)
 };
@@ -328,6 +346,119 @@ __device__ __forceinline__ uint32_t nib_sum(uint32_t w) {   // sum of the eight 
 #define GRP_OUT_XYZ 0
 #define GRP_OUT_SPECTRAL 1
 #define GRP_OUT_MOMENTS 2
+// ---- the phases of li_group_kernel that are functions of their own (all inlined; DESIGN.md 4.1, "Source layout", says why the others are not)
+
+__device__ __forceinline__ GroupLds grp_carve(unsigned char *lds, Gather &G) {
+    GroupLds L;
+    L.prevRk = reinterpret_cast<float *>(lds + GrpLdsPlan::prevRk);
+    L.order = reinterpret_cast<unsigned short *>(lds + GrpLdsPlan::order);
+    L.pos = reinterpret_cast<float *>(lds + GrpLdsPlan::bucket);
+    unsigned char *U = lds + GrpLdsPlan::U;
+    G.cap = 0; G.cd = 0; G.ci = 0;
+    G.paint = reinterpret_cast<uint32_t *>(U);
+    L.hist = reinterpret_cast<uint32_t *>(U);
+    L.miniD = reinterpret_cast<float *>(U);
+    L.ubuf = reinterpret_cast<float *>(U);
+    L.cst = reinterpret_cast<float *>(lds + GrpLdsPlan::cst);
+    L.trows = reinterpret_cast<float *>(lds + GrpLdsPlan::trows);
+    L.lint = reinterpret_cast<float *>(lds + GrpLdsPlan::lint);
+    return L;
+}
+__device__ __forceinline__ float *grp_row(const GroupLds &L, GrpRow row) { return L.cst + 32 * row; }
+__device__ __forceinline__ const f4 *grp_row4(const GroupLds &L, GrpRow row) { return reinterpret_cast<const f4 *>(L.cst + 32 * row); }
+
+// order the chunk's rays by scatter offset: lanes of a group then march in near lock-step positions
+__device__ __forceinline__ void grp_order_chunk(const LiArgs &A, const DevScene &S, const GroupLds &L, unsigned long long r0, int nIn, int lane) {
+    __syncthreads();
+    // key = step count + scatter offset: rays of one pixel whose lengths straddle a step-count boundary march with
+    // different step lengths and drift apart by up to a step; keeping equal counts together keeps the groups compact
+    for (int i = lane; i < GRP_CH; i += LANES) {
+        float key = 3.0e9f;
+        if (i < nIn) {
+            const pvol_ray kr = A.rays[r0 + i];
+            RayD rr;
+            rr.o = v3(kr.o[0], kr.o[1], kr.o[2]); rr.d = v3(kr.d[0], kr.d[1], kr.d[2]); rr.mint = kr.mint; rr.maxt = kr.maxt;
+            float ka = 0.f, kb = 0.f;
+            const bool kh = S.volKind != PVOL_VOLUME_NONE && vol_intersect(S, rr, &ka, &kb) && (kb - ka) != 0.f;
+            key = (kh ? ceilf((kb - ka) / S.stepSize) : 0.f) + kr.scatter_u;
+        }
+        L.ubuf[i] = key;
+    }
+    __syncthreads();
+    for (int i = lane; i < nIn; i += LANES) {
+        const float ui = L.ubuf[i];
+        int rank = 0;
+        for (int j = 0; j < nIn; ++j) {
+            const float uj = L.ubuf[j];
+            rank += (uj < ui || (uj == ui && j < i)) ? 1 : 0;
+        }
+        L.order[rank] = (unsigned short)i;
+    }
+    __syncthreads();
+}
+
+// Optical length of the march step from pPrev along dseg (tau of the step = sigma_t x this): DensityRegion::tau with the recorded offset u
+// (photonvolume.cpp:154), the segment itself where both ends lie inside the extent, else the part of it inside
+template <bool GRID>
+__device__ __forceinline__ float grp_step_len(const DevScene &S, V3 pPrev, V3 dseg, bool bothInside, float u) {
+    if (GRID) return grid_tau_lane(S, pPrev, dseg, 0.f, 1.f, .5f * S.stepSize, u);
+    if (bothInside) { const V3 a = pPrev + dseg * 0.f, b = pPrev + dseg * 1.f; return len(a - b); }
+    return analytic_tau_length(S, pPrev, dseg, 0.f, 1.f);
+}
+
+struct GrpCentre { V3 lo, hi, c; float rho; };
+// bounds, centre and spread of the query points of the lanes that are `on`
+__device__ __forceinline__ GrpCentre grp_centre(V3 p, bool on) {
+    const float big = 3.0e38f;
+    float lx = on ? p.x : big, ly = on ? p.y : big, lz = on ? p.z : big;
+    float hx = on ? p.x : -big, hy = on ? p.y : -big, hz = on ? p.z : -big;
+    lx = -wave_max(-lx); ly = -wave_max(-ly); lz = -wave_max(-lz);
+    hx = wave_max(hx); hy = wave_max(hy); hz = wave_max(hz);
+    GrpCentre B;
+    B.lo = v3(lx, ly, lz); B.hi = v3(hx, hy, hz);
+    B.c = v3(0.5f * (lx + hx), 0.5f * (ly + hy), 0.5f * (lz + hz));
+    B.rho = wave_max(on ? len(p - B.c) : 0.f);
+    return B;
+}
+
+struct GrpKth {
+    int cum, inRange;               // sum of the counters, slots below Tl
+    int wsel, bstarI;               // word and bin of the kq-th (-1: not found)
+    int cumBelow, binCount;         // values below bin b*, values in it
+};
+// prefix scan over the lane's histogram: word of the kq-th, then its nibble
+__device__ __forceinline__ GrpKth grp_find_kth(const uint32_t *histLane, int kq, int Mb) {
+    GrpKth K;
+    int cum = 0, wsel = -1, cumWord = 0;
+    uint32_t selBits = 0u;
+#pragma unroll
+    for (int wd = 0; wd < GRP_BINS / 8; ++wd) {
+        const uint32_t w = histLane[wd * LANES];
+        const int t = (int)nib_sum(w);
+        const bool here = wsel < 0 && cum + t >= kq;
+        wsel = here ? wd : wsel;
+        selBits = here ? w : selBits;
+        cumWord = here ? cum : cumWord;
+        cum += t;
+    }
+    K.inRange = ((Mb + 3) & ~3) - (int)histLane[(GRP_BINS / 8) * LANES];
+    int bstarI = -1, cumBelow = 0, binCount = 0;
+    {
+        int c2 = cumWord;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int cb = (int)((selBits >> (4 * s)) & 15u);
+            const bool here = bstarI < 0 && c2 + cb >= kq;
+            bstarI = here ? 8 * wsel + s : bstarI;
+            cumBelow = here ? c2 : cumBelow;
+            binCount = here ? cb : binCount;
+            c2 += cb;
+        }
+    }
+    K.cum = cum; K.wsel = wsel; K.bstarI = bstarI; K.cumBelow = cumBelow; K.binCount = binCount;
+    return K;
+}
+
 template <bool STATS, int OUT, bool REPLAY, bool GRID>
 __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
     constexpr bool SPECTRAL = OUT == GRP_OUT_SPECTRAL, MOMENTS = OUT == GRP_OUT_MOMENTS;
@@ -335,22 +466,9 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
     extern __shared__ __align__(16) unsigned char lds[];
     const DevScene &S = *A.scene;
     const int lane = threadIdx.x;
-    // LDS plan (11.7 KB: twelve waves per CU): prevRk | order | bucket | U | cst | trows
-    float *prevRk = reinterpret_cast<float *>(lds);
-    GroupLds L;
-    L.order = reinterpret_cast<unsigned short *>(prevRk + PREV_N);
-    L.pos = reinterpret_cast<float *>(L.order + GRP_CH);
-    unsigned char *U = reinterpret_cast<unsigned char *>(L.pos + 4 * GRP_PITCH);
     Gather G;
-    G.cap = 0; G.cd = 0; G.ci = 0;
-    G.paint = reinterpret_cast<uint32_t *>(U);
-    L.hist = reinterpret_cast<uint32_t *>(U);
-    L.miniD = reinterpret_cast<float *>(U);
-    L.ubuf = reinterpret_cast<float *>(U);
-    L.cst = reinterpret_cast<float *>(U + GRP_U_BYTES);
-    L.trows = L.cst + 12 * 32;
-    L.lint = L.trows + GRP_TRI_ROWS * 16;
-    for (int i = lane; i < PREV_N; i += LANES) prevRk[i] = 0.f;
+    const GroupLds L = grp_carve(lds, G);
+    for (int i = lane; i < PREV_N; i += LANES) L.prevRk[i] = 0.f;
     const int q = lane & 7;
     const f4 sigA4 = ld4(S.sigA, q), sigS4 = ld4(S.sigS, q);
     const f4 sigT4 = sigA4 + sigS4;
@@ -365,22 +483,22 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
     sigTmax = wave_max(sigTmax);
     if (lane < 32) {
         const float a = S.sigA[lane], s = S.sigS[lane];
-        L.cst[lane] = a;
-        L.cst[32 + lane] = s;
-        L.cst[64 + lane] = S.le[lane];
-        L.cst[96 + lane] = lane < 30 ? __fdividef(s, a + s) : 0.f;
-        L.cst[128 + lane] = nLights > 0 ? S.lights[0].intensity[lane] : 0.f;
-        L.cst[160 + lane] = lane < 30 ? __builtin_amdgcn_rcpf(s) : 0.f;
-        L.cst[192 + lane] = lane < 30 ? S.cieX[lane] : 0.f;
-        L.cst[224 + lane] = lane < 30 ? S.cieY[lane] : 0.f;
-        L.cst[256 + lane] = lane < 30 ? S.cieZ[lane] : 0.f;
-        L.cst[288 + lane] = a + s;
-        L.cst[320 + lane] = a * S.le[lane];
-        L.cst[352 + lane] = lane < 30 ? __fdividef(s, a + s) * __builtin_amdgcn_rcpf(s) : 0.f;
+        grp_row(L, GRP_ROW_SIGA)[lane] = a;
+        grp_row(L, GRP_ROW_SIGS)[lane] = s;
+        grp_row(L, GRP_ROW_LE)[lane] = S.le[lane];
+        grp_row(L, GRP_ROW_ALBEDO)[lane] = lane < 30 ? __fdividef(s, a + s) : 0.f;
+        grp_row(L, GRP_ROW_LIGHT0)[lane] = nLights > 0 ? S.lights[0].intensity[lane] : 0.f;
+        grp_row(L, GRP_ROW_RCP_SIGS)[lane] = lane < 30 ? __builtin_amdgcn_rcpf(s) : 0.f;
+        grp_row(L, GRP_ROW_CIEX)[lane] = lane < 30 ? S.cieX[lane] : 0.f;
+        grp_row(L, GRP_ROW_CIEY)[lane] = lane < 30 ? S.cieY[lane] : 0.f;
+        grp_row(L, GRP_ROW_CIEZ)[lane] = lane < 30 ? S.cieZ[lane] : 0.f;
+        grp_row(L, GRP_ROW_SIGT)[lane] = a + s;
+        grp_row(L, GRP_ROW_SIGA_LE)[lane] = a * S.le[lane];
+        grp_row(L, GRP_ROW_ALBEDO_RCP_SIGS)[lane] = lane < 30 ? __fdividef(s, a + s) * __builtin_amdgcn_rcpf(s) : 0.f;
     }
     __syncthreads();
-    const f4 *cA = reinterpret_cast<const f4 *>(L.cst), *cS = cA + 8, *cI = cA + 32;
-    const f4 *cX = cA + 48, *cY = cA + 56, *cZ = cA + 64, *cT = cA + 72, *cAL = cA + 80, *cAR = cA + 88;
+    const f4 *cA = grp_row4(L, GRP_ROW_SIGA), *cS = grp_row4(L, GRP_ROW_SIGS), *cI = grp_row4(L, GRP_ROW_LIGHT0), *cX = grp_row4(L, GRP_ROW_CIEX), *cY = grp_row4(L, GRP_ROW_CIEY);
+    const f4 *cZ = grp_row4(L, GRP_ROW_CIEZ), *cT = grp_row4(L, GRP_ROW_SIGT), *cAL = grp_row4(L, GRP_ROW_SIGA_LE), *cAR = grp_row4(L, GRP_ROW_ALBEDO_RCP_SIGS);
     const bool rowsOK = !REPLAY && nLights > 0 && S.lights[0].kind == PVOL_LIGHT_DISTANT && S.nTris <= GRP_TRI_ROWS && !S.bvhNodes && !S.nSpheres;
     if (rowsOK) tri_rows_prepare(S, v3(S.lights[0].dir[0], S.lights[0].dir[1], S.lights[0].dir[2]), L.trows, lane);
     const int k = S.nUsed;
@@ -395,6 +513,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
     const float *bX = L.pos, *bY = L.pos + GRP_PITCH, *bZ = L.pos + 2 * GRP_PITCH, *bI = L.pos + 3 * GRP_PITCH;
     uint32_t *histLane = L.hist + lane;
     for (;;) {
+        // the chunk fetch: in place, not a function ("Source layout")
         uint32_t chunk = 0;
         if (lane == 0) chunk = atomicAdd(A.chunkCounter, 1u);
         chunk = (uint32_t)lane_i((int)chunk, 0);
@@ -417,35 +536,10 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
             r0 = (unsigned long long)first + begin + l0;
             slot0 = (size_t)sidx * A.sliceM + l0;
         }
-        // ---- order the chunk's rays by scatter offset: lanes of a group then march in near lock-step positions
-        __syncthreads();
-        // key = step count + scatter offset: rays of one pixel whose lengths straddle a step-count boundary march with
-        // different step lengths and drift apart by up to a step; keeping equal counts together keeps the groups compact
-        for (int i = lane; i < GRP_CH; i += LANES) {
-            float key = 3.0e9f;
-            if (i < nIn) {
-                const pvol_ray kr = A.rays[r0 + i];
-                RayD rr;
-                rr.o = v3(kr.o[0], kr.o[1], kr.o[2]); rr.d = v3(kr.d[0], kr.d[1], kr.d[2]); rr.mint = kr.mint; rr.maxt = kr.maxt;
-                float ka = 0.f, kb = 0.f;
-                const bool kh = S.volKind != PVOL_VOLUME_NONE && vol_intersect(S, rr, &ka, &kb) && (kb - ka) != 0.f;
-                key = (kh ? ceilf((kb - ka) / S.stepSize) : 0.f) + kr.scatter_u;
-            }
-            L.ubuf[i] = key;
-        }
-        __syncthreads();
-        for (int i = lane; i < nIn; i += LANES) {
-            const float ui = L.ubuf[i];
-            int rank = 0;
-            for (int j = 0; j < nIn; ++j) {
-                const float uj = L.ubuf[j];
-                rank += (uj < ui || (uj == ui && j < i)) ? 1 : 0;
-            }
-            L.order[rank] = (unsigned short)i;
-        }
-        __syncthreads();
+        grp_order_chunk(A, S, L, r0, nIn, lane);
 #pragma unroll 1
         for (int g0 = 0; g0 < nIn; g0 += LANES) {
+            // a lane's ray set-up: in place, not a function ("Source layout")
             const bool have = g0 + lane < nIn;
             const uint32_t local = have ? (uint32_t)L.order[g0 + lane] : 0u;
             const size_t ri = (size_t)r0 + local;
@@ -474,17 +568,9 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                     if (j < nS) {
                         const V3 p = o + d * tc;
                         tc += step;
-                        const V3 dseg = p - pP;
-                        float lenStep;
-                        if (GRID) {
-                            lenStep = grid_tau_lane(S, pP, dseg, 0.f, 1.f, .5f * S.stepSize, rec.stepU[2 * j]);   // photonvolume.cpp:154
-                        } else {
-                            const bool inP = box_inside(S.extLo, S.extHi, xform_point(S.w2v, p));
-                            if (inP0 && inP) { const V3 a = pP + dseg * 0.f, b = pP + dseg * 1.f; lenStep = len(a - b); }
-                            else lenStep = analytic_tau_length(S, pP, dseg, 0.f, 1.f);
-                            inP0 = inP;
-                        }
-                        totalLen += lenStep;
+                        const bool inP = !GRID && box_inside(S.extLo, S.extHi, xform_point(S.w2v, p));
+                        totalLen += grp_step_len<GRID>(S, pP, p - pP, inP0 && inP, GRID ? rec.stepU[2 * j] : 0.f);
+                        inP0 = inP;
                         pP = p;
                     }
                 }
@@ -511,19 +597,12 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                 const bool inP = dens != 0.f;
                 float lenStep = 0.f;   // tau of the step = sigma_t x lenStep
                 if (act) {
-                    const V3 dseg = p - pPrev;
-                    if (GRID) {
-                        lenStep = grid_tau_lane(S, pPrev, dseg, 0.f, 1.f, .5f * S.stepSize, rec.stepU[2 * j]);
-                    } else if (inPrev && inP) {
-                        const V3 a = pPrev + dseg * 0.f, b = pPrev + dseg * 1.f;
-                        lenStep = len(a - b);
-                    } else {
-                        lenStep = analytic_tau_length(S, pPrev, dseg, 0.f, 1.f);
-                    }
+                    lenStep = grp_step_len<GRID>(S, pPrev, p - pPrev, inPrev && inP, GRID ? rec.stepU[2 * j] : 0.f);
                     if (!REPLAY && !(lenStep * sigTmax < 6.8f)) bad = true;   // the roulette could fire: sequential kernel (photonvolume.cpp:156-161)
                     cumLen += lenStep;
                 }
                 // ---- direct lighting geometry (photonvolume.cpp:178-203), light 0 (at most one light here)
+                // in place, not a function: see DESIGN.md 4.1, "Source layout"
                 float fallReg = 1.f, d2Reg = 1.f, exitLen = 0.f, ph = 0.f;
                 bool lit = false, distant = true;
                 const int ln = REPLAY ? (act ? (int)(rec.stepByte[j] & 7u) : 0) : 0;   // the light this step samples (photonvolume.cpp:181-183)
@@ -573,7 +652,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                     // photons asks again with a radius scaled from the count it saw, a bucket overflow halves everybody's radius.
                     // What is still open afterwards is handed to li_fixup_kernel.
                     float guessBase = lastRk;
-                    if (j < PREV_N) guessBase = fmaxf(guessBase, prevRk[j]);
+                    if (j < PREV_N) guessBase = fmaxf(guessBase, L.prevRk[j]);
                     const bool measured = guessBase > 0.f;   // a k-th distance^2 that was found, not one of the cold fallbacks below
                     {   // cold: what the other lanes found at their previous step, else the map-wide estimate
                         const float nbr = wave_max(lastRk);
@@ -581,6 +660,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                     }
                     float Twant = need ? ((!fixedR && guessBase * A.grpGuess < S.maxDistSq) ? guessBase * A.grpGuess : S.maxDistSq) : 0.f;
                     int lastFail = 0;   // stats: 1 = bucket overflow, 2 = too few photons inside the radius, 3 = other
+                    // the attempt loop: in the kernel, not a function of its own ("Source layout")
                     for (int attempt = 0; attempt < 3; ++attempt) {
                         bool needP = need && !done && Twant > 0.f;
                         if (!__ballot(needP)) break;
@@ -593,34 +673,23 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                         bool fullR = !(Tl < S.maxDistSq);
                         float T = needP ? Tl : 0.f;
                         T = wave_max(T);
-                        // centre and spread of the query points
-                        const float big = 3.0e38f;
-                        float lx = needP ? p.x : big, ly = needP ? p.y : big, lz = needP ? p.z : big;
-                        float hx = needP ? p.x : -big, hy = needP ? p.y : -big, hz = needP ? p.z : -big;
-                        lx = -wave_max(-lx); ly = -wave_max(-ly); lz = -wave_max(-lz);
-                        hx = wave_max(hx); hy = wave_max(hy); hz = wave_max(hz);
-                        V3 c = v3(0.5f * (lx + hx), 0.5f * (ly + hy), 0.5f * (lz + hz));
-                        float rho = needP ? len(p - c) : 0.f;
-                        rho = wave_max(rho);
-                        if (attempt < 2 && rho > 0.3f * sqrtf(T)) {
+                        GrpCentre B = grp_centre(p, needP);   // centre and spread of the query points
+                        if (attempt < 2 && B.rho > 0.3f * sqrtf(T)) {
                             // the query points are spread over a good part of the search radius (rays that march with different step
                             // lengths): serve the half below the centre along the widest axis now, the rest in the next attempt
-                            const float ex = hx - lx, ey = hy - ly, ez = hz - lz;
-                            const float side = (ex >= ey && ex >= ez) ? p.x - c.x : (ey >= ez ? p.y - c.y : p.z - c.z);
+                            const float ex = B.hi.x - B.lo.x, ey = B.hi.y - B.lo.y, ez = B.hi.z - B.lo.z;
+                            const float side = (ex >= ey && ex >= ez) ? p.x - B.c.x : (ey >= ez ? p.y - B.c.y : p.z - B.c.z);
                             needP = needP && !(side > 0.f);
                             T = wave_max(needP ? Tl : 0.f);
-                            lx = needP ? p.x : big; ly = needP ? p.y : big; lz = needP ? p.z : big;
-                            hx = needP ? p.x : -big; hy = needP ? p.y : -big; hz = needP ? p.z : -big;
-                            lx = -wave_max(-lx); ly = -wave_max(-ly); lz = -wave_max(-lz);
-                            hx = wave_max(hx); hy = wave_max(hy); hz = wave_max(hz);
-                            c = v3(0.5f * (lx + hx), 0.5f * (ly + hy), 0.5f * (lz + hz));
-                            rho = wave_max(needP ? len(p - c) : 0.f);
+                            B = grp_centre(p, needP);
                         }
+                        const V3 c = B.c;
+                        const float rho = B.rho;
                         const float Rs = (sqrtf(T) + rho) * 1.0001f + 1e-6f;   // superset by the triangle inequality, with rounding slack
                         // The settled class, first attempt only: theta = kappa x the smallest guess among the served lanes
                         // is meant to lie below every served lane's k-th distance^2; a photon within precore_bound(theta, rho) of the centre is
                         // then a member for all of them and stays out of both passes.  Wave-uniform.  Only guesses that were measured count
-                        // (lastRk, prevRk[j]), and no served lane may reach the full radius, even after the widening below: the EXACT
+                        // (lastRk, L.prevRk[j]), and no served lane may reach the full radius, even after the widening below: the EXACT
                         // compilation of the passes and the short sets never meet a settled slot.
                         float theta = 0.f;
                         if (GRP_CORE_MIN < GRP_CAP && attempt == 0 && !fixedR && A.grpPrecore > 0.f && __ballot(needP) &&
@@ -663,47 +732,23 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                         const unsigned long long tpa = (STATS && GRP_PHASE_DIAG == 1) ? stamp() : 0ull;
                         if (STATS && GRP_PHASE_DIAG == 1) wc.diag1 += tpa - tp1;
                         // ---- prefix scan: word of the k-th, then its nibble
-                        int cum = 0, wsel = -1, cumWord = 0;
-                        uint32_t selBits = 0u;
-#pragma unroll
-                        for (int wd = 0; wd < GRP_BINS / 8; ++wd) {
-                            const uint32_t w = histLane[wd * LANES];
-                            const int t = (int)nib_sum(w);
-                            const bool here = wsel < 0 && cum + t >= kq;
-                            wsel = here ? wd : wsel;
-                            selBits = here ? w : selBits;
-                            cumWord = here ? cum : cumWord;
-                            cum += t;
-                        }
-                        const int inRange = ((Mb + 3) & ~3) - (int)histLane[(GRP_BINS / 8) * LANES];
-                        int bstarI = -1, cumBelow = 0, binCount = 0;
-                        {
-                            int c2 = cumWord;
-#pragma unroll
-                            for (int s = 0; s < 8; ++s) {
-                                const int cb = (int)((selBits >> (4 * s)) & 15u);
-                                const bool here = bstarI < 0 && c2 + cb >= kq;
-                                bstarI = here ? 8 * wsel + s : bstarI;
-                                cumBelow = here ? c2 : cumBelow;
-                                binCount = here ? cb : binCount;
-                                c2 += cb;
-                            }
-                        }
+                        const GrpKth K = grp_find_kth(histLane, kq, Mb);
                         // a 4-bit counter that wrapped makes the counters' total fall short of the in-range count: not trusted
-                        const bool sane = needP && cum == inRange;
-                        bool ok = sane && wsel >= 0 && bstarI >= 0 && binCount <= GRP_MINI;
+                        const bool sane = needP && K.cum == K.inRange;
+                        bool ok = sane && K.wsel >= 0 && K.bstarI >= 0 && K.binCount <= GRP_MINI;
                         // the full radius holds fewer than k photons: all of them count, r^2 = the farthest (photonvolume.cpp:76-105)
-                        const bool shortSet = sane && fullR && inRange + nPre < k;
-                        const bool tooFew = needP && !fullR && cum + nPre < k;
+                        const bool shortSet = sane && fullR && K.inRange + nPre < k;
+                        const bool tooFew = needP && !fullR && K.cum + nPre < k;
                         if (STATS && !GRP_PHASE_DIAG && attempt == 0) wc.diag0 += __popcll(__ballot(needP && !ok && !shortSet));
+                        // in place, not a function: see DESIGN.md 4.1, "Source layout"
                         if (needP) {   // what to ask for next time (0 = nothing: crowded bin or wrapped counter, the exact lookup takes it)
                             Twant = 0.f;
                             lastFail = tooFew ? 2 : 3;
                             // crowded bin (more values than the mini list ranks) or a wrapped counter: a radius that ends just behind
                             // the k-th's bin still holds k photons and spreads them over finer bins
-                            if (!tooFew && !ok && !shortSet) Twant = (sane && bstarI >= 0) ? Tl * ((float)(bstarI + 1) * (1.f / GRP_BINS)) * 1.001f : 0.6f * Tl;
+                            if (!tooFew && !ok && !shortSet) Twant = (sane && K.bstarI >= 0) ? Tl * ((float)(K.bstarI + 1) * (1.f / GRP_BINS)) * 1.001f : 0.6f * Tl;
                             if (tooFew) {   // the count seen inside Tl gives the local density: k photons need ~ (k / count)^(2/3) x Tl
-                                const float grow = cum + nPre > 0 ? 1.35f * __builtin_amdgcn_exp2f(0.6666667f * __builtin_amdgcn_logf((float)k / (float)(cum + nPre))) : 1.0e9f;
+                                const float grow = K.cum + nPre > 0 ? 1.35f * __builtin_amdgcn_exp2f(0.6666667f * __builtin_amdgcn_logf((float)k / (float)(K.cum + nPre))) : 1.0e9f;
                                 Twant = fminf(S.maxDistSq, Tl * fmaxf(1.5f, grow));
                             }
                         }
@@ -714,7 +759,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                             // ---- pass 2: member bits
                             uint32_t mem[GRP_NW], le[GRP_NW];
                             float dmax = 0.f;
-                            const uint32_t bstar = shortSet ? (uint32_t)GRP_BINS : (ok ? (uint32_t)bstarI : 0u);
+                            const uint32_t bstar = shortSet ? (uint32_t)GRP_BINS : (ok ? (uint32_t)K.bstarI : 0u);
                             float th1, th2;
                             bool thOK = true;
                             if (exact) { th1 = grp_theta<true>(bstar, scale, Tl, &thOK); th2 = grp_theta<true>(bstar + 1u, scale, Tl, &thOK); }
@@ -726,6 +771,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                             const unsigned long long tpc = (STATS && GRP_PHASE_DIAG == 1) ? stamp() : 0ull;
                             if (STATS && GRP_PHASE_DIAG == 1) wc.diag3 += tpc - tpb;
                             // ---- the photons of bin b*: their exact values into the lane's mini list (slot order)
+                            // in place, not a function: see DESIGN.md 4.1, "Source layout"
                             int nb = 0;
 #pragma unroll
                             for (int wd = 0; wd < GRP_NW; ++wd) {
@@ -754,7 +800,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                     sv[t] = lo; sv[t + 1] = hi;
                                 }
                             }
-                            const int m = kq - cumBelow;   // 1-based rank of the k-th inside its bin
+                            const int m = kq - K.cumBelow;   // 1-based rank of the k-th inside its bin
                             float rkC = sv[0];
 #pragma unroll
                             for (int t = 1; t < GRP_MINI; ++t) rkC = (m == t + 1) ? sv[t] : rkC;
@@ -762,7 +808,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
 #pragma unroll
                             for (int t = 0; t < GRP_MINI; ++t) nLessIn += (sv[t] < rkC) ? 1 : 0;
                             int quota = m - nLessIn;   // ties at rkC are taken in bucket order
-                            ok = ok && nb == binCount && rkC < INFINITY;
+                            ok = ok && nb == K.binCount && rkC < INFINITY;
                             {   // the verification of the settled class: strict, so no settled slot ties with the k-th.  A lane that fails it asks
                                 // again for the same radius (the next attempt has the rule off)
                                 const bool unverified = ok && !(rkC >= theta);
@@ -792,6 +838,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                             const unsigned long long tp3 = STATS ? stamp() : 0ull;
                             if (STATS) wc.cySelect += tp3 - tp1;
                             if (STATS && GRP_PHASE_DIAG == 1) wc.diag4 += tp3 - tpc;
+                            // flux, both forms with their shared-member blocks: in place, not functions ("Source layout")
                             // ---- flux on the matrix pipe.  A = alpha rows (lane l: bin l & 31 of the slot of its half-wave: one coalesced
                             // 128-B row per half-wave and load), B = member bits of ray l & 31 for that slot as 0.f / 1.f (the upper
                             // half-wave's copy of a ray's word comes from ONE v_permlane32_swap per 32 slots): D = A B + C adds a row to exactly
@@ -997,11 +1044,12 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                                 }
                             }
                             }   // !MOMENTS
-                            if (ok) { done = true; rk = rkC; if (shortSet) nFoundLane = inRange + nPre; }
+                            if (ok) { done = true; rk = rkC; if (shortSet) nFoundLane = K.inRange + nPre; }
                             if (STATS) { wc.kept += (unsigned long long)k * __popcll(__ballot(ok)); wc.cyFlux += stamp() - tp3; }
                         }
                     }   // attempt
                     // ---- lanes the plan did not serve: their term is added by li_fixup_kernel (exact lookup), nothing else waits for it
+                    // (the hand-over: in place, not a function; DESIGN.md 4.1, "Source layout")
                     const uint64_t todo = __ballot(need && !done);
                     if (todo) {
                         // A.fixGroup: whole 64-slot runs, one per group-step (li_fixup_group_kernel shares a bucket per run);
@@ -1029,10 +1077,11 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                     const float rkGuess = (need && done) ? (nFoundLane >= k ? rk : S.maxDistSq) : 0.f;
                     {   // mean k-th distance^2 of the group at this step -> guess of the next group
                         const float sr = wave_sum(rkGuess), sn = (float)__popcll(__ballot(rkGuess > 0.f));
-                        if (j < PREV_N && lane == 0 && sn > 0.f) prevRk[j] = sr / sn;
+                        if (j < PREV_N && lane == 0 && sn > 0.f) L.prevRk[j] = sr / sn;
                     }
                     if (need) lastRk = rkGuess;
                 }
+                // in place, not a function: see DESIGN.md 4.1, "Source layout"
                 // ---- this step's term of  Lv = sum_j w_j exp(-sigma_t R_j)  (photonvolume.cpp:150-218), 30 bins per lane:
                 //   w_j  = sigma_a Le step + sigma_s step (L_d + albedo L_ii)
                 //   L_ii = Sum(alpha) * phase / (4/3 pi r^3 sigma_s)                        (:99-105; acc holds the raw sum)
@@ -1127,6 +1176,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
                 if (STATS && GRP_PHASE_DIAG == 2) wc.diag3 += stamp() - tq2;
             }
             // ---- outputs
+            // in place, not functions, and the draw count written twice: see DESIGN.md 4.1, "Source layout"
             if (have) {
                 if (bad) {
                     atomicOr(A.needSeq, 1u);
@@ -1138,7 +1188,7 @@ __global__ __launch_bounds__(LANES, GRP_WPE) void li_group_kernel(LiArgs A) {
 #pragma unroll
                         for (int b = 0; b < 30; ++b) {
                             op[b] = Lv[b];
-                            op[30 + b] = hit ? __builtin_amdgcn_exp2f((L.cst[b] + L.cst[32 + b]) * kLast) : 1.f;
+                            op[30 + b] = hit ? __builtin_amdgcn_exp2f((grp_row(L, GRP_ROW_SIGA)[b] + grp_row(L, GRP_ROW_SIGS)[b]) * kLast) : 1.f;
                         }
                     } else {
                         float ty = 0.f;
@@ -1267,7 +1317,7 @@ __global__ __launch_bounds__(LANES, (NREG > 4 ? PVOL_WPE_BIG : PVOL_WPE)) void l
 
 extern "C" size_t pvol_group_lds_bytes(int candCap) {
     (void)candCap;
-    return (size_t)PREV_N * 4 + GRP_CH * 2 + (size_t)GRP_PITCH * 16 + GRP_U_BYTES + 12 * 32 * 4 + GRP_TRI_ROWS * 64 + PVOL_MAX_LIGHTS * 32 * 4;
+    return GrpLdsPlan::total;
 }
 
 // replay: 0 = ray-parallel scenes (li_par_kernel's conditions), 1 = records of the RNG pre-pass, homogeneous, 2 = records, VolumeGrid
