@@ -22,6 +22,7 @@ VOLUME_NONE, VOLUME_HOMOGENEOUS, VOLUME_GRID, VOLUME_RAINBOW, VOLUME_EXPONENTIAL
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT = 0, 1, 2
 MATERIAL_MATTE, MATERIAL_GLASS = 0, 1
 OUT_SPECTRAL, OUT_XYZ = 0, 1
+VOLINT_PHOTON, VOLINT_SINGLE = 0, 1   # PVOL_VOLINT_*: pvol_set_volume_integrator
 
 
 class Spectrum(C.Structure):
@@ -287,6 +288,18 @@ class PhotonArray(C.Structure):   # pvol_photon_array: one surface map handed to
 
 class LPhotonCheck(C.Structure):   # the arguments pvol_check_lphoton judges (csrc/pvol_host.h): pvol_lphoton_batch*'s pointers and numbers
     _fields_ = [("p", C.c_void_p), ("w", C.c_void_p), ("n", C.c_uint32), ("output_kind", C.c_int32), ("out", C.c_void_p)]
+
+
+class SinglePlanIn(C.Structure):   # the inputs of pvol_single_plan (csrc/pvol_host.h): a batch under VolumeIntegrator "single"
+    _fields_ = [("vol_kind", C.c_int32), ("n_lights", C.c_int32), ("roulette_ray", C.c_int32), ("has_init", C.c_int32), ("force_seq", C.c_int32),
+                ("has_tile", C.c_int32), ("spec_on", C.c_int32), ("gather", C.c_int32)]
+
+
+class SinglePlan(C.Structure):   # ... and its answer: status, form (SINGLE_SEQ / SINGLE_PAR), kernel name
+    _fields_ = [("rc", C.c_int32), ("form", C.c_int32), ("kernel", C.c_char_p)]
+
+
+SINGLE_SEQ, SINGLE_PAR = 0, 1
 
 
 LPHOTON_SCRATCH_BYTES = 64 << 20   # PVOL_LPHOTON_SCRATCH_BYTES

@@ -347,6 +347,47 @@ static bool roulette_possible(const pvol_ctx *c) {
     return !(c->hs.stepSize * m * dens < 6.8f);
 }
 
+// ---- VolumeIntegrator "single" (pvol_host.h): pure up to single_plan_input
+int pvol_single_roulette_possible(int volKind, double diag, float maxSigmaT, float maxDensity) {
+    if (volKind == PVOL_VOLUME_NONE) return 0;
+    const double dens = is_density_region(volKind) ? 1.5 * (double)maxDensity : 1.0;
+    return !(diag * (double)maxSigmaT * dens < 6.8);
+}
+
+void pvol_single_plan(const SinglePlanIn *in, SinglePlan *out) {
+    SinglePlan p = {PVOL_OK, PVOL_SINGLE_SEQ, "single_seq_kernel"};
+    const bool extent = in->volKind == PVOL_VOLUME_HOMOGENEOUS || in->volKind == PVOL_VOLUME_NONE;
+    const bool par = in->nLights <= 1 && extent && !in->hasInit && !in->forceSeq;
+    if (in->volKind == PVOL_VOLUME_RAINBOW) p.rc = PVOL_E_UNSUPPORTED;   // rainbowReflection is the photon integrator's own
+    else if (in->gather) p.rc = PVOL_E_UNSUPPORTED;
+    else if (in->hasTile && (in->nLights > 1 || is_density_region(in->volKind) || in->specOn || in->rouletteRay)) p.rc = PVOL_E_UNSUPPORTED;
+    else if (par) { p.form = PVOL_SINGLE_PAR; p.kernel = "single_par_kernel"; }
+    else if (in->hasTile) p.rc = PVOL_E_UNSUPPORTED;
+    *out = p;
+}
+
+static SinglePlanIn single_plan_input(const pvol_ctx *c, bool hasInit, bool hasTile, bool specOn) {
+    const DevScene &h = c->hs;
+    float m = 0.f;
+    for (int i = 0; i < PVOL_NBINS; ++i) m = std::max(m, h.sigA[i] + h.sigS[i]);
+    SinglePlanIn in = {};
+    in.volKind = h.volKind; in.nLights = h.nLights;
+    in.rouletteRay = pvol_single_roulette_possible(h.volKind, h.volKind == PVOL_VOLUME_NONE ? 0.0 : extent_world_diagonal(h), m, c->maxDensity);
+    in.hasInit = hasInit; in.forceSeq = c->knobs.forceSeq; in.hasTile = hasTile; in.specOn = specOn;
+    return in;
+}
+
+static int single_limit_status(const pvol_ctx *c, bool forceSeqCounts) {
+    if (!c || c->volInt != PVOL_VOLINT_SINGLE || !c->haveScene) return PVOL_OK;
+    SinglePlanIn in = single_plan_input(c, false, true, c->hs.surf.enabled != 0 && c->specOn);
+    if (!forceSeqCounts) in.forceSeq = 0;
+    SinglePlan p;
+    pvol_single_plan(&in, &p);
+    return p.rc;
+}
+int pvol_single_render_status(const pvol_ctx *c) { return single_limit_status(c, true); }
+int pvol_single_caller_status(const pvol_ctx *c) { return single_limit_status(c, false); }
+
 static PlanIn plan_input(const pvol_ctx *c, const BatchArgs &b) {
     const DevScene &h = c->hs;
     PlanIn in = {};
@@ -513,6 +554,21 @@ static int run_sliced(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArg
     return PVOL_OK;
 }
 
+// VolumeIntegrator "single": the ray-parallel form backed by the sequential one behind the needSeq gate, or the sequential form alone
+static int run_single(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a, int form) {
+    const RegionLaunchers &K = pvol_launchers(c->hs.volKind);
+    hipError_t e = hipSuccess;
+    if (form == PVOL_SINGLE_PAR) {
+        e = K.singlePar(&a, p.nWaves, b.stream);
+        a.gated = 1;
+    } else if (!ok(hipMemsetAsync(c->dWords.get(), 0, 4 * sizeof(uint32_t), b.stream))) {   // the gate word a coalesced batch reads back
+        return PVOL_E_NO_DEVICE;
+    }
+    if (ok(e)) e = K.singleSeq(&a, p.ldsResolve, b.stream);
+    a.gated = 0;
+    return ok(e) ? PVOL_OK : PVOL_E_NO_DEVICE;
+}
+
 static int run_seq(pvol_ctx *c, const BatchArgs &b, const BatchPlan &p, LiArgs &a) {
     return ok(pvol_launchers(c->hs.volKind).liSeq(&a, p.ldsSeq, c->hs.candCap, c->statsOn, b.stream)) ? PVOL_OK : PVOL_E_NO_DEVICE;
 }
@@ -531,8 +587,21 @@ static int reserve_scratch(pvol_ctx *c, const BatchPlan &p, hipStream_t stream) 
 
 int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
     PlanIn in = plan_input(c, b);
+    // Transmittance() is the same function under both integrators (single.cpp:48-63 is photonvolume.cpp:15-30)
+    const bool single = c->volInt == PVOL_VOLINT_SINGLE && !b.transOnly;
+    SinglePlan sp = {};
+    if (single) {
+        const SinglePlanIn si = single_plan_input(c, in.hasInit != 0, in.hasTile != 0, in.specOn != 0);
+        pvol_single_plan(&si, &sp);
+        if (sp.rc != PVOL_OK) return sp.rc;
+        in.roulette = si.rouletteRay;   // the COUNT pre-pass's 4 + 6n + n + u is exact where the ACCUMULATED Tr.y() stays above 1e-3
+    }
     BatchPlan p = plan_path(in);
     if (p.rc != PVOL_OK) return p.rc;
+    if (single) {   // no map is read: no bucket form, no records; a SLICED answer takes the sequential form (never with a tile)
+        p.path = sp.form == PVOL_SINGLE_PAR ? PVOL_PATH_PAR : PVOL_PATH_SEQ;
+        p.groupForm = 0; p.fixGroup = 0; p.liteResolve = 0; p.resolve = 0; p.kernel = sp.kernel;
+    }
     const hipStream_t stream = b.stream;
     BatchTimer &timer = c->timer;
     BatchTimer::Pair taken;
@@ -576,7 +645,8 @@ int pvol_launch_batch(pvol_ctx *c, const BatchArgs &b) {
     }
     hipEventRecord(ev.first.get(), stream);
     pvol_phase_mark(c, stream, PVOL_PHASE_MARCH);
-    rc = p.path == PVOL_PATH_PAR ? run_par(c, b, p, a) : p.path == PVOL_PATH_SLICED ? run_sliced(c, b, p, a, &tile) : run_seq(c, b, p, a);
+    rc = single ? run_single(c, b, p, a, sp.form)
+                : p.path == PVOL_PATH_PAR ? run_par(c, b, p, a) : p.path == PVOL_PATH_SLICED ? run_sliced(c, b, p, a, &tile) : run_seq(c, b, p, a);
     if (rc != PVOL_OK) return rc;
     hipEventRecord(ev.second.get(), stream);
     pvol_phase_mark(c, stream, PVOL_PHASE_END);
@@ -681,6 +751,21 @@ int pvol_li_lone(pvol_ctx *c, const pvol_ray *ray, uint32_t *mt, int32_t *mti, f
     memcpy(T, out + 30, sizeof(float) * 30);
     memcpy(mt, state, sizeof(uint32_t) * 624);
     *mti = (int32_t)state[624];
+    return PVOL_OK;
+}
+
+int pvol_set_volume_integrator(pvol_ctx *c, int kind) {
+    if (!c || (kind != PVOL_VOLINT_PHOTON && kind != PVOL_VOLINT_SINGLE)) return PVOL_E_INVALID;
+    std::lock_guard<std::recursive_mutex> api(c->apiMu);
+    if (!ok(hipSetDevice(c->params.device)) || !ok(hipDeviceSynchronize())) return PVOL_E_NO_DEVICE;   // batches in flight keep their integrator
+    c->volInt = kind;
+    return PVOL_OK;
+}
+
+int pvol_get_volume_integrator(pvol_ctx *c, int *kind) {
+    if (!c || !kind) return PVOL_E_INVALID;
+    std::lock_guard<std::recursive_mutex> api(c->apiMu);
+    *kind = c->volInt;
     return PVOL_OK;
 }
 

@@ -174,6 +174,10 @@ extern "C" hipError_t pvol_launch_rays_count(const RaysArgs *a, hipStream_t stre
 extern "C" hipError_t pvol_launch_rays_emit(const RaysArgs *a, pvol_stream *st, uint32_t nStreams, const pvol_stream *continued, hipStream_t stream);
 extern "C" hipError_t pvol_launch_rays_patch(const RaysArgs *a, hipStream_t stream);
 extern "C" hipError_t pvol_launch_rays_compose(const RaysArgs *a, const pvol_stream *st, uint32_t nStreams, pvol_stream *caller, hipStream_t stream);
+// VolumeIntegrator "single" (pvol_single.hip): the sequential form (one wave per stream; ldsBytes = BatchPlan::ldsResolve) and
+// the ray-parallel one (one wave per ray, one march step per lane; chunkCounter and needSeq zeroed by the caller)
+extern "C" hipError_t pvol_launch_single_seq(const LiArgs *args, size_t ldsBytes, hipStream_t stream);
+extern "C" hipError_t pvol_launch_single_par(const LiArgs *args, uint32_t nWaves, hipStream_t stream);
 // The launchers of one compilation of the marching kernels: VolumeGridDensity (and every medium that is no density region) or, from
 // pvol_march_exp.hip, ExponentialDensity (pvol_region_exp.h).  The host asks pvol_launchers(kind) wherever a launched kernel may
 // evaluate a density; launchers that never do (spec_compose, spec_fill) are called directly.
@@ -186,6 +190,8 @@ struct RegionLaunchers {
     decltype(&pvol_launch_surface) surface;
     decltype(&pvol_launch_tile) tile;
     decltype(&pvol_launch_lphoton_points) lphotonPoints;
+    decltype(&pvol_launch_single_seq) singleSeq;
+    decltype(&pvol_launch_single_par) singlePar;
 };
 #if !PVOL_REGION_EXP   /* undefined or 0: the first compilation and the host units */
 extern "C" hipError_t pvol_launch_li_seq_exp(const LiArgs *args, size_t ldsBytes, int candCap, bool stats, hipStream_t stream);
@@ -200,11 +206,14 @@ extern "C" hipError_t pvol_launch_surface_exp(const SurfArgs *a, uint32_t nWaves
 extern "C" hipError_t pvol_launch_tile_exp(const LiArgs *args, const TileArgs *tile, bool fused, size_t ldsBytes, int candCap, hipStream_t stream,
                                            int wavesPerTask, bool plain, const char **form);
 extern "C" hipError_t pvol_launch_lphoton_points_exp(const PointsArgs *args, int candCap, uint32_t nWaves, hipStream_t stream);
+extern "C" hipError_t pvol_launch_single_seq_exp(const LiArgs *args, size_t ldsBytes, hipStream_t stream);
+extern "C" hipError_t pvol_launch_single_par_exp(const LiArgs *args, uint32_t nWaves, hipStream_t stream);
 static inline const RegionLaunchers &pvol_launchers(int volKind) {
     static const RegionLaunchers base = {pvol_launch_li_seq, pvol_launch_li_slice, pvol_launch_li_group, pvol_launch_li_replay, pvol_launch_li_par,
-                                         pvol_launch_surface, pvol_launch_tile, pvol_launch_lphoton_points};
+                                         pvol_launch_surface, pvol_launch_tile, pvol_launch_lphoton_points, pvol_launch_single_seq, pvol_launch_single_par};
     static const RegionLaunchers expo = {pvol_launch_li_seq_exp, pvol_launch_li_slice_exp, pvol_launch_li_group_exp, pvol_launch_li_replay_exp,
-                                         pvol_launch_li_par_exp, pvol_launch_surface_exp, pvol_launch_tile_exp, pvol_launch_lphoton_points_exp};
+                                         pvol_launch_li_par_exp, pvol_launch_surface_exp, pvol_launch_tile_exp, pvol_launch_lphoton_points_exp,
+                                         pvol_launch_single_seq_exp, pvol_launch_single_par_exp};
     return volKind == PVOL_VOLUME_EXPONENTIAL ? expo : base;
 }
 #endif
@@ -326,6 +335,7 @@ struct PVOL_LOCAL SliceScratch { uint64_t bound = 0; ScratchFence fence; };
 
 struct pvol_ctx {
     pvol_params params = {};
+    int volInt = PVOL_VOLINT_PHOTON;   // pvol_set_volume_integrator: which Li() the batches run (PVOL_VOLINT_*)
     CtxKnobs knobs;          // the environment as pvol_create found it (pvol_env.h)
     int nCU = 256;
     // One batch at a time per context: the launches of a batch share dWords / dCounters and the scratch in `buf`.  Host entry points hold it from upload to copy-back (VolumeIntegrator::Li is called from every
@@ -454,6 +464,33 @@ struct TilePlainIn {
 };
 static_assert(sizeof(TilePlainIn) == 40, "tests/test_tile_plain_gate.py mirrors it");
 extern "C" int pvol_tile_plain_gate(const TilePlainIn *in);
+// The plan of a batch under VolumeIntegrator "single" (DESIGN.md 24), a pure function beside plan_path (pvol_api.hip): no HIP call, no context, no
+// environment; its own input struct, as pvol_tile_plain_gate has.  It decides in this order:
+//   1. the refusals (rc = PVOL_E_UNSUPPORTED): a rainbow medium; a final gather (pvol_radiance_gather_batch*); then, with a tile (the render
+//      driver; pvol_radiance_batch* is held to the same limit): more than one light, a density region, a specular material under the surface integrator, R'
+//   2. PVOL_SINGLE_PAR (single_par_kernel): at most one light, a homogeneous extent or no medium, no caller RNG state, PVOL_FORCE_SEQ unset
+//      (and, with a tile, !R', which 1. has left)
+//   3. PVOL_SINGLE_SEQ (single_seq_kernel) for everything else without a tile -- also where plan_path, fed R' as PlanIn::roulette, answers
+//      SLICED, which has no kernel here; with a tile what 2. does not take is refused (PVOL_E_UNSUPPORTED)
+// R' (rouletteRay): a ray can reach the roulette on the ACCUMULATED Tr.y() -- pvol_single_roulette_possible.
+enum { PVOL_SINGLE_SEQ = 0, PVOL_SINGLE_PAR = 1 };
+struct SinglePlanIn {
+    int32_t volKind, nLights;
+    int32_t rouletteRay;        // R'
+    int32_t hasInit, forceSeq;  // PlanIn::hasInit, PlanIn::forceSeq
+    int32_t hasTile, specOn;    // PlanIn::hasTile, PlanIn::specOn
+    int32_t gather;             // the caller wants a final gather
+};
+struct SinglePlan { int32_t rc, form; const char *kernel; };
+static_assert(sizeof(SinglePlanIn) == 32 && sizeof(SinglePlan) == 16, "tests/test_single_plan.py mirrors both");
+extern "C" void pvol_single_plan(const SinglePlanIn *in, SinglePlan *out);
+// R': not true exactly when diag * maxSigmaT * (1.5 maxDensity for a density region, else 1) < 6.8 -- the bound of roulette_possible
+// (pvol_api.hip) over the longest segment a ray can spend inside the extent instead of one step.  No medium: never.
+extern "C" int pvol_single_roulette_possible(int volKind, double diag, float maxSigmaT, float maxDensity);
+// PVOL_OK, or what the render driver answers under the context's volume integrator before it launches or writes anything
+extern "C" int pvol_single_render_status(const pvol_ctx *c);
+// ... and pvol_radiance_batch*, which is held to the same limit (its batch has no tile, so PVOL_FORCE_SEQ does not enter)
+extern "C" int pvol_single_caller_status(const pvol_ctx *c);
 // The gate of the moment form, a pure function (pvol_api.hip): the number N in 1..3 of Taylor terms of exp(-delta_b L) whose truncation
 // bound x^N / N! e^x, x = max_b |delta_b| pathBound, is below 2^-25, or 0 = none is (keep the 30-bin path).  sigA / sigS: 30 values;
 // delta_b = sigma_t_b - the midrange of sigma_t; pathBound: a bound on the optical path length of a ray inside the medium.

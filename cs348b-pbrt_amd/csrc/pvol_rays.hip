@@ -215,6 +215,8 @@ int pvol_radiance_batch_device(pvol_ctx *c, const pvol_ray *dRays, uint32_t nRay
     std::lock_guard<std::recursive_mutex> api(c->apiMu);   // the context's state is read under the lock only
     const int rc0 = check_ctx(c, &a);
     if (rc0 != PVOL_OK) return rc0;
+    // VolumeIntegrator "single": served within the render driver's limit, refused beyond it before anything is launched or written
+    if (const int rs = pvol_single_caller_status(c)) return rs;
     if (!nRays || !nStreams) return PVOL_OK;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
     hipStream_t stream = (hipStream_t)hipStream;
@@ -232,6 +234,8 @@ int pvol_radiance_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays, pvol_
     std::lock_guard<std::recursive_mutex> api(c->apiMu);   // from the upload to the copy-back: the launches share the context's scratch
     int rc = check_ctx(c, &a);
     if (rc != PVOL_OK) return rc;
+    // VolumeIntegrator "single": served within the render driver's limit, refused beyond it before anything is launched or written
+    if (const int rs = pvol_single_caller_status(c)) return rs;
     if (!nRays || !nStreams) return PVOL_OK;
     if (!streams_partition(streams, nStreams, nRays, 0)) return PVOL_E_INVALID;
     if (!ok(hipSetDevice(c->params.device))) return PVOL_E_NO_DEVICE;
@@ -253,6 +257,7 @@ int pvol_radiance_gather_batch_device(pvol_ctx *c, const pvol_ray *dRays, uint32
     const RadianceGatherCheck a = {dRays, dStreams, nRays, nStreams, outputKind, out, gather};
     if (!c) return check_ctx(0, &a);
     std::lock_guard<std::recursive_mutex> api(c->apiMu);
+    if (c->volInt == PVOL_VOLINT_SINGLE) return PVOL_E_UNSUPPORTED;   // no final gather under VolumeIntegrator "single" 
     const int rc0 = check_ctx(c, &a);
     if (rc0 != PVOL_OK) return rc0;
     if (!nRays || !nStreams) return PVOL_OK;
@@ -272,6 +277,7 @@ int pvol_radiance_gather_batch(pvol_ctx *c, const pvol_ray *rays, uint32_t nRays
     const RadianceGatherCheck a = {rays, streams, nRays, nStreams, outputKind, out, gather};
     if (!c) return check_ctx(0, &a);
     std::lock_guard<std::recursive_mutex> api(c->apiMu);   // from the upload to the copy-back
+    if (c->volInt == PVOL_VOLINT_SINGLE) return PVOL_E_UNSUPPORTED;   // no final gather under VolumeIntegrator "single" 
     int rc = check_ctx(c, &a);
     if (rc != PVOL_OK) return rc;
     if (!nRays || !nStreams) return PVOL_OK;

@@ -29,6 +29,9 @@
 #define merge_kernel merge_kernel_exp
 #define merge_surface_kernel merge_surface_kernel_exp
 #define place_rows_kernel place_rows_kernel_exp
+#define single_seq_kernel single_seq_kernel_exp
+#define single_par_kernel single_par_kernel_exp
+#define single_stream_begin_kernel single_stream_begin_kernel_exp
 // launchers and size helpers
 #define pvol_launch_li_seq pvol_launch_li_seq_exp
 #define pvol_launch_li_par pvol_launch_li_par_exp
@@ -48,6 +51,8 @@
 #define pvol_launch_merge_surface pvol_launch_merge_surface_exp
 #define pvol_launch_place_rows pvol_launch_place_rows_exp
 #define pvol_shoot_state_words pvol_shoot_state_words_exp
+#define pvol_launch_single_seq pvol_launch_single_seq_exp
+#define pvol_launch_single_par pvol_launch_single_par_exp
 // pvol_rays_dev.h (pvol_radiance_batch*) reads no density and is left out of the second compilation altogether (pvol_march.hip); its names
 // stand here so that nothing of the sources compiled twice is off the list
 #define rays_count_kernel rays_count_kernel_exp

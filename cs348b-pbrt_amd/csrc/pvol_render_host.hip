@@ -204,6 +204,11 @@ extern "C" int pvol_render_tasks_window_device(pvol_ctx *c, const pvol_camera *c
     RenderPlan plan = pvol_render_plan(camera, film, window, smp, taskIds, nTaskIds, dPixels != 0, c->haveScene, c->hs.surf.enabled != 0, c->specOn,
                                        pvol_read_knobs().tileBatchRays);
     if (plan.rc != PVOL_OK) return plan.rc;
+    {   // VolumeIntegrator "single": what the driver does not serve is refused before anything is launched or written
+        std::lock_guard<std::recursive_mutex> api(c->apiMu);
+        const int rc = pvol_single_render_status(c);
+        if (rc != PVOL_OK) return rc;
+    }
 #ifdef PVOL_TIMING_KNOBS   // timing experiments only (tools/tile_debug_*.sh build with it): every knob gives WRONG images and stream
                            // positions, so the shipped library does not read the variable at all
     pvol_env_tile_debug(pvol_env_get, &plan.tile.debugSkip);
@@ -235,6 +240,11 @@ int render_share(pvol_ctx *c, const pvol_camera *camera, const pvol_film *film, 
     std::vector<uint32_t> ids(n);
     pvol_partition_tasks(smp->n_tasks, rank, nRanks, ids.data(), n, &n);
     const pvol_film_window w = pvol_window_or_full(film, window);
+    {   // ... the film's zeroing included
+        std::lock_guard<std::recursive_mutex> api(c->apiMu);
+        const int rc = pvol_single_render_status(c);
+        if (rc != PVOL_OK) return rc;
+    }
     if (!ok(hipMemsetAsync(dPixels, 0, sizeof(float) * 4 * (size_t)w.x_pixel_count * w.y_pixel_count, stream))) return PVOL_E_NO_DEVICE;
     return pvol_render_tasks_window_device(c, camera, film, window, smp, ids.data(), n, dPixels, 0, stream);
 }

@@ -625,7 +625,7 @@ def _run(path, b, depth=0):
             b.surf = named()
         elif word == "VolumeIntegrator":
             b.vol = named()
-            if b.vol[0] != "photonvolume":
+            if b.vol[0] not in ("photonvolume", "single"):   # core/api.cpp:575-581 builds "emission" too: no device path
                 raise Unsupported('VolumeIntegrator "%s"' % b.vol[0])
         elif word == "Camera":
             name, ps = named()
@@ -727,6 +727,8 @@ def load(path):
     # nused: the VOLUME integrator's default is 250 (photonvolume.cpp:226); 50 is the surface integrator's (photonmap.cpp:323)
     d["params.i"] = np.array([vp.i("nused", 250), vp.i("volumephotons", 0), sp.i("maxphotondepth", 5), sp.i("causticphotons", 20000),
                               sp.i("indirectphotons", 10000), int(sp.b("finalgather", True))], np.int32)
+    if b.vol[0] == "single":   # optional key: CreateSingleScatteringIntegrator reads "stepsize" alone (single.cpp:142-145, default 1);
+        d["vol.integrator"] = "single"   # PhotonVolume.set_volume_integrator takes the name.  Absent: "photonvolume"
     # the surface integrator's own parameters (integrators/photonmap.cpp:336-363) for pvol_set_surface_integrator
     d["surf.name"] = b.surf[0]
     d["surf.params.i"] = np.array([sp.i("nused", 50), sp.i("maxspeculardepth", 5), int(sp.b("finalgather", True)),

@@ -131,6 +131,11 @@ def lib():
         L.pvol_transmittance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _f32p]
         L.pvol_get_stats.argtypes = [C.c_void_p, C.POINTER(abi.Stats), C.c_int]
         L.pvol_enable_stats.argtypes = [C.c_void_p, C.c_int]
+        L.pvol_set_volume_integrator.argtypes = [C.c_void_p, C.c_int]
+        L.pvol_get_volume_integrator.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.pvol_single_plan.argtypes = [C.POINTER(abi.SinglePlanIn), C.POINTER(abi.SinglePlan)]
+        L.pvol_single_plan.restype = None
+        L.pvol_single_roulette_possible.argtypes = [C.c_int, C.c_double, C.c_float, C.c_float]
         L.pvol_kernel_time_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
         L.pvol_get_shoot_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.pvol_march_kernel_name.argtypes = [C.c_void_p]
@@ -255,7 +260,10 @@ EXPORTS = ["pvol_abi_version", "pvol_strerror", "pvol_device_count", "pvol_defau
            "pvol_build_gather_map", "pvol_build_gather_map_arrays", "pvol_gather_map_count", "pvol_gather_photons",
            "pvol_gather_photons_device", "pvol_gather_directions", "pvol_gather_directions_device", "pvol_final_gather",
            "pvol_final_gather_device", "pvol_lphoton_batch", "pvol_lphoton_batch_device", "pvol_radiance_batch",
-           "pvol_radiance_batch_device", "pvol_radiance_gather_batch", "pvol_radiance_gather_batch_device"]
+           "pvol_radiance_batch_device", "pvol_radiance_gather_batch", "pvol_radiance_gather_batch_device",
+           "pvol_set_volume_integrator", "pvol_get_volume_integrator"]
+
+VOLUME_INTEGRATORS = {"photonvolume": abi.VOLINT_PHOTON, "single": abi.VOLINT_SINGLE}   # core/api.cpp:575-581 by name
 
 SHOOT_STAT_NAMES = ["paths", "follow_calls", "no_hit", "march_steps", "interactions", "absorbed", "stored_volume",
                     "stored_caustic", "stored_direct", "stored_indirect", "split_children", "nshot"]
@@ -740,8 +748,19 @@ class PhotonVolume:
                "pvol_download_photons")
         return p, wi, alpha
 
+    def set_volume_integrator(self, name):
+        """pvol_set_volume_integrator: "photonvolume" (the default) or "single" (SingleScatteringIntegrator::Li: no photon map)."""
+        if name not in VOLUME_INTEGRATORS:
+            raise ValueError('volume integrator %r: "photonvolume" or "single"' % (name,))
+        _check(lib().pvol_set_volume_integrator(self._h, VOLUME_INTEGRATORS[name]), "pvol_set_volume_integrator")
+
+    def volume_integrator(self):
+        kind = C.c_int()
+        _check(lib().pvol_get_volume_integrator(self._h, C.byref(kind)), "pvol_get_volume_integrator")
+        return {v: k for k, v in VOLUME_INTEGRATORS.items()}[kind.value]
+
     def li(self, rays, streams, output_kind=abi.OUT_SPECTRAL):
-        """PhotonVolumeIntegrator::Li for a batch; returns (out[n, 60|4], draws[n]); streams['end_draw'] is updated."""
+        """The context's VolumeIntegrator::Li (PhotonVolumeIntegrator unless set_volume_integrator chose another) for a batch; returns (out[n, 60|4], draws[n]); streams['end_draw'] is updated."""
         rays = np.ascontiguousarray(rays)
         assert rays.dtype == abi.RAY_DTYPE and streams.dtype == abi.STREAM_DTYPE and streams.flags["C_CONTIGUOUS"]
         n = len(rays)

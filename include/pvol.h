@@ -739,6 +739,23 @@ int pvol_get_li_coalescing_stats(pvol_ctx *ctx, uint64_t *out6, int reset);
 int pvol_transmittance_batch(pvol_ctx *ctx, const pvol_ray *rays, uint32_t n_rays,
                              pvol_stream *streams, uint32_t n_streams, float *out);
 
+/* Which VolumeIntegrator the context's Li() is (core/api.cpp:575-581).  PVOL_VOLINT_PHOTON, the default at pvol_create:
+ * PhotonVolumeIntegrator::Li (photonvolume.cpp:112-222).  PVOL_VOLINT_SINGLE: SingleScatteringIntegrator::Li (single.cpp:66-139) --
+ * the same march, light samples and RNG traffic, Tr accumulated over the steps, Lv += Tr Lve + Tr sigma_s p Ld nLights / pdf, no
+ * photon map (one that is uploaded stays and is ignored).  The setter waits for the context's work in flight and uploads nothing.
+ * PVOL_E_INVALID: a NULL argument or an unknown kind.
+ * Under SINGLE: pvol_li_batch, pvol_li_batch_device, pvol_li and pvol_li_many are served with every medium but the rainbow, any
+ * number of lights and the roulette; pvol_transmittance_batch is the same function under both integrators.  The render driver
+ * (pvol_render_tasks*_device, the rank and group frames) and pvol_radiance_batch* are served within one limit: at most one light, a
+ * homogeneous extent or no medium in which no ray can reach the roulette (the extent's world-space diagonal times the largest
+ * sigma_t below 6.8), no specular material under the surface integrator.  PVOL_E_UNSUPPORTED, before anything is launched or
+ * written: a rainbow medium; everything beyond that limit in the render driver and pvol_radiance_batch*;
+ * pvol_radiance_gather_batch*, whatever else the call is (its other checks come behind this one). */
+#define PVOL_VOLINT_PHOTON 0
+#define PVOL_VOLINT_SINGLE 1
+int pvol_set_volume_integrator(pvol_ctx *ctx, int kind);
+int pvol_get_volume_integrator(pvol_ctx *ctx, int *kind);
+
 /* Work counters accumulated since the last reset (feeds the algorithmic-bytes formula
  * B_lookup = 20*V + 132*K of SURVEY 8(d)). */
 int pvol_get_stats(pvol_ctx *ctx, pvol_stats *out, int reset);
@@ -749,7 +766,8 @@ int pvol_enable_stats(pvol_ctx *ctx, int on);
  * the last reset, measured with HIP events on the launch stream. */
 int pvol_kernel_time_ms(pvol_ctx *ctx, double *avg_ms, uint64_t *launches, int reset);
 /* Name of the march+gather kernel the last batch was dispatched to ("li_group_kernel", "li_par_kernel",
- * "li_replay_kernel", "li_seq_kernel"; "" before the first batch): the kernel the time above belongs to. */
+ * "li_replay_kernel", "li_seq_kernel"; under PVOL_VOLINT_SINGLE "single_par_kernel", "single_seq_kernel"; "" before the first batch): the
+ * kernel the time above belongs to. */
 const char *pvol_march_kernel_name(pvol_ctx *ctx);
 /* Form of the tile pre-pass the context's last pvol_render_tasks_device batch that ran one actually launched: "tile_kernel<count>",
  * "tile_kernel<fused>", "tile_mw_kernel<2>", "<4>", "<8>" or "<16>" (the multi-wave COUNT form; a requested wave count is rounded down

@@ -4,7 +4,7 @@
 image film) -> RGB.
 
     python tools/render_pbrt.py SCENE.pbrt OUT.pfm [--xres N --yres N --spp N --photons N --shoot-tasks N --no-surface --devices 0,1,...
-                                                    --cropwindow X0 X1 Y0 Y1]
+                                                    --cropwindow X0 X1 Y0 Y1 --volume-integrator single|photonvolume]
 
 The file's own Film / Sampler / integrator parameters are used unless overridden.  A crop window (the file's `"float cropwindow"`
 or --cropwindow, fractions of the frame as in the reference's ImageFilm) renders only that part: the image and the PFM have the
@@ -14,7 +14,9 @@ caustic estimate on matte surfaces) is switched on when the scene
 covers it (matte and glass surfaces -- the specular recursion included --, a homogeneous or rainbow medium at any nused and
 phase function, or no medium; an indirect map only with `finalgather false`, where it adds its own LPhoton estimate); otherwise (a
 VolumeGrid or exponential medium, the final gather over an indirect map) Ls = 0 and the image holds the
-volume term alone -- the tool says which.  info["render_s"]: wall seconds of the frame's render_tasks (shoot excluded)."""
+volume term alone -- the tool says which.  The volume integrator is the file's (`VolumeIntegrator "single"`: single scattering, no
+photon map) unless --volume-integrator names one; the shoot is skipped when neither integrator wants a map (single, and no surface
+integrator in use).  info["render_s"]: wall seconds of the frame's render_tasks (shoot excluded)."""
 import argparse
 import importlib
 import os
@@ -41,8 +43,9 @@ def apply_surface_integrator(pvs, scene, stored_indirect):
 
 
 def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_tasks=2048, surface=True, log=print, caustic_photons=None,
-                      devices=None, cropwindow=None, phases=False, indirect_photons=None):
+                      devices=None, cropwindow=None, phases=False, indirect_photons=None, volume_integrator=None):
     """cropwindow: (x0, x1, y0, y1) overrides the file's; None keeps it (the whole frame when the file names none).
+    volume_integrator: "single" or "photonvolume" overrides the file's.
     phases: info["phase_ms"] gets the first context's device milliseconds per phase of the frame (tile pre-pass, march + gather,
     surface, film) from HIP events, which serialise the phases a little: not for the frame's own timing.
     devices: None renders on one context (params.device 0); a list of HIP device ordinals (repeats allowed: [0, 0] runs the
@@ -82,7 +85,12 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
         holder = abi.SceneHolder(scene)
         for q in pvs:
             q.set_scene(holder)
-        if int(scene["lights.kind"].size):
+        vol_int = volume_integrator or scene.get("vol.integrator", "photonvolume")
+        for q in pvs:
+            q.set_volume_integrator(vol_int)
+        want_surface = surface and scene["surf.name"] == "photonmap"
+        # "single" reads no volume map; the caustic and indirect maps are the surface integrator's
+        if int(scene["lights.kind"].size) and (vol_int != "single" or want_surface):
             if group:
                 pvol.preprocess_group(pvs, shoot_tasks)
             else:
@@ -91,7 +99,9 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
         log("photon map: %d volume, %d caustic, %d indirect photons from %d paths" % (st["stored_volume"], st["stored_caustic"], st["stored_indirect"],
                                                                                         st["paths"]))
         used_surface = False
-        if surface and scene["surf.name"] == "photonmap":
+        if surface and scene["surf.name"] != "photonmap":
+            log('SurfaceIntegrator "%s" has no device path: the image holds the volume term only' % scene["surf.name"])
+        if want_surface:
             try:
                 apply_surface_integrator(pvs, scene, st["stored_indirect"])
                 used_surface = True
@@ -148,7 +158,7 @@ def render_scene_file(path, xres=None, yres=None, spp=None, photons=None, shoot_
             torch.cuda.synchronize()
         for q in pvs:
             q.check_errors()
-        info = {"xres": xres, "yres": yres, "spp": spp, "surface_integrator": used_surface, "kernel": pv.march_kernel_name(),
+        info = {"xres": xres, "yres": yres, "spp": spp, "surface_integrator": used_surface, "volume_integrator": vol_int, "kernel": pv.march_kernel_name(),
                 "photons": int(st["stored_volume"]), "caustic_photons": int(st["stored_caustic"]), "indirect_photons": int(st["stored_indirect"]), "render_s": render_s}
         if group:
             info["devices"] = devices
@@ -183,9 +193,11 @@ if __name__ == "__main__":
                                       "default: one context on device 0")
     ap.add_argument("--cropwindow", type=float, nargs=4, metavar=("X0", "X1", "Y0", "Y1"),
                     help="render this part of the frame only (fractions of the frame, as Film \"float cropwindow\"); overrides the file's")
+    ap.add_argument("--volume-integrator", choices=("single", "photonvolume"), help="overrides the file's VolumeIntegrator")
     ap.add_argument("--phases", action="store_true", help="also report device milliseconds per phase of the frame")
     a = ap.parse_args()
     devices = [int(d) for d in a.devices.split(",")] if a.devices else None
-    img, info = render_scene_file(a.scene, a.xres, a.yres, a.spp, a.photons, a.shoot_tasks, not a.no_surface, devices=devices, cropwindow=a.cropwindow, phases=a.phases)
+    img, info = render_scene_file(a.scene, a.xres, a.yres, a.spp, a.photons, a.shoot_tasks, not a.no_surface, devices=devices, cropwindow=a.cropwindow, phases=a.phases,
+                                  volume_integrator=a.volume_integrator)
     write_pfm(a.out, img)
     print(info, "mean rgb", img.mean(axis=(0, 1)))
